@@ -13,15 +13,25 @@ leaving in a second, point-to-point exchange per step (--no-ring: the ordered fo
 resident in HBM before the timed region.
 
 Prints ONE JSON line on rank 0.  `value` = body-updates/s = N * steps / s of the whole job, STRICT arithmetic (the
-reference's own, bit for bit) unless --mode fast.  `roofline` prices the pair-fold kernel against the fp32 vector peak
-(the binding roofline: SURVEY.md section 8d) at the reference's 18 flop per interaction, and carries the rate
-this device's vector ALU was measured to issue in the same process (`measured_issue_ceiling`).  `cpu_baseline` is the CPU
-oracle (a C restatement of the reference's Rust; kind "port") timed on the host cores this process may really use.
-`targets` says which mode meets which line of BASELINE.json's north_star: no single mode meets both.
+reference's own, bit for bit) unless --mode fast; `ms_per_step` = milliseconds of one timed step.  `roofline` prices the
+pair-fold kernel against the fp32 vector peak (the binding roofline: SURVEY.md section 8d) at the reference's 18 flop
+per interaction, from the kernel times of the timed steps themselves.  `targets` says which mode meets which line of
+BASELINE.json's north_star: no single mode meets both.
 
-Exit code: 0; 3 when an informational leg (other mode, 3-D data, boids, CPU baseline) hung -- the headline line is still printed,
-with `aux_error` naming the leg; 4 when the line's own `parity_check` failed (STRICT: some bit of the final state differs from the
-golden checksums of that step; FAST: one step further from STRICT than its tolerance) -- the line is printed all the same.
+A plain run does what the headline needs and nothing else: set up, preheat, warm up, time exactly --steps steps, print the line.
+Every leg starts its warm-up from the initial state (the preheat's steps are undone), so with the same arguments the state the last
+timed step leaves is the same from run to run; --dump-outputs DIR writes it as DIR/positions.npy and DIR/velocities.npy (float32,
+(n, 3); above 64 MB in all, a fixed seeded sample of the rows).
+
+--full adds everything else, after the headline: the line's own `parity_check`, the other mode, the 3-D data, the boids controller,
+the unpreheated legs, the per-call drop-in latency, the rate this device's vector ALU was measured to issue in the same process
+(`roofline.measured_issue_ceiling`), and `cpu_baseline`: the CPU oracle (a C restatement of the reference's Rust; kind "port") timed
+on the host cores this process may really use (--no-secondary / --no-cpu-baseline leave parts of it out).
+
+Exit code: 0; with --full, 3 when an informational leg (other mode, 3-D data, boids, CPU baseline) hung -- the headline line is still
+printed, with `aux_error` naming the leg -- and 4 when the line's own `parity_check` failed (STRICT: some bit of the final state
+differs from the golden checksums of that step; FAST: one step further from STRICT than its tolerance) -- the line is printed all the
+same.
 """
 import argparse
 import json
@@ -36,8 +46,8 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-PEAK_FP32_VECTOR_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
-PEAK_HBM_GBPS = 8000.0            # same guide: HBM3E ~8 TB/s
+PEAK_FP32_VECTOR_TFLOPS = 157.3   # MI355X chip-level parameters (vendor specification)
+PEAK_HBM_GBPS = 8000.0            # same specification: HBM3E ~8 TB/s
 SPEC_LANE_OPS_PER_S = PEAK_FP32_VECTOR_TFLOPS * 1e12 / 2.0   # one vector operation per lane per cycle (the flop peak counts an FMA twice)
 BYTES_PER_BODY_STEP = 64          # algorithmic HBM bytes: 16-B position + 16-B velocity record, read and written once
 FLOP_PER_INTERACTION = 18         # src/main.rs:428-430 as written: 3 sub, 3 mul + 2 add, 1 add, 3 mul, 3 div, 3 add
@@ -103,6 +113,27 @@ def state_checksums(positions, velocities):
         out_x.append(int(np.bitwise_xor.reduce(u)) if u.size else 0)
         out_s.append(int(u.sum(dtype=np.uint64) & 0xFFFFFFFF))
     return out_x, out_s
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # --dump-outputs: what all arrays may hold together (under 64 MB with the .npy headers)
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every (n, k) array as out_dir/<name>.npy in float32.  Where all of them together pass `limit` bytes, the same
+    fixed, seeded sample of rows (sorted) is written of each.  Returns the rows written (None: all).  Pure numpy
+    (tests/test_bench_math.py)."""
+    import numpy as np
+
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float32) for name, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    rows = None
+    if n * row_bytes > limit:
+        rows = np.sort(np.random.default_rng(1234).choice(n, size=limit // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if rows is None else a[rows])
+    return rows
 
 
 def parity_against_golden(n, seed, steps_done, positions, velocities, path=None):
@@ -194,17 +225,19 @@ def preheat(step, torch, dist, world, dev, ms):
 
 
 def time_mode(nb, torch, dist, args, mode, rank, world, pos, vel, steps=None, warmup=None, overlap=False, ring=None, preheat_ms=None,
-              ring_overlap=None, choose=False, parity=False, exchange_kind=None):
+              ring_overlap=None, choose=False, parity=False, exchange_kind=None, dump=None):
     """ring: None = the library's plan (FAST on equal ranks of a multi-GPU job: every unordered pair once, two exchanges per
     step), False = the ordered fold with its one exchange.  ring_overlap: the pairs form in phases, its exchanges behind compute.
     choose: FAST at world > 1 -- let ShardedScene.choose_form time every form this shape can take and keep the fastest (the
     timed region then runs that form; `form` in the result says which and what each cost).  parity: check the final state (STRICT:
-    every bit against the golden checksums of that step; FAST: one step against STRICT)."""
+    every bit against the golden checksums of that step; FAST: one step against STRICT).  dump: a directory -- rank 0 writes the
+    positions and velocities the last timed step left there (write_outputs)."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     params = nb.default_params(mode=mode)
     sc = nb.ShardedScene(pos, vel, params, overlap=overlap, ring=ring, ring_overlap=ring_overlap)
     dev = sc.device
+    initial = (sc.pos[0].clone(), sc.pos[1].clone(), sc.vel.clone())
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -246,6 +279,16 @@ def time_mode(nb, torch, dist, args, mode, rank, world, pos, vel, steps=None, wa
                         "sequence / behind compute (nb_launch_ring_fold_phase), the ordered fold with its one exchange; the timed region runs "
                         "the fastest"}
     pre = preheat(sc.step, torch, dist, world, dev, args.preheat_ms if preheat_ms is None else preheat_ms)
+    if pre:
+        # the preheat's step count follows the wall clock: undo its steps, so that the warm-up starts from the initial state and the
+        # state the timed steps leave depends on the arguments alone (every rank: no pull of a peer's buffer is in flight around it)
+        sc._wait_pending()
+        fence()
+        for buf, saved in zip((sc.pos[0], sc.pos[1], sc.vel), initial):
+            buf.copy_(saved)
+        sc.cur, sc.steps_done, sc.velfull_valid, sc._own_ready = 0, 0, False, None
+        fence()
+    del initial
     for _ in range(warmup):
         sc.step()
     # kernel-only timing: events on the stream the kernels are launched on (torch's current stream), around every launch call of
@@ -280,6 +323,10 @@ def time_mode(nb, torch, dist, args, mode, rank, world, pos, vel, steps=None, wa
     for name in calls:
         setattr(sc.backend, name, real[name])
     sc.sync()  # nb_launch_status: a kernel-reported failure fails the bench instead of timing garbage
+    if dump is not None:
+        outputs = {"positions": sc.positions(), "velocities": sc.velocities()}   # (world > 1: the velocities are gathered: every rank)
+        if rank == 0:
+            write_outputs(dump, outputs)
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
@@ -346,7 +393,15 @@ def main():
     ap.add_argument("--aux-timeout", type=float, default=180.0,
                     help="seconds the informational legs (other mode, 3-D data, boids, CPU baseline) may take before the headline "
                          "is printed without them and the run exits 3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also everything else: the line's parity check, the other mode, 3-D data, boids, the "
+                         "unpreheated legs, the drop-in calls, the issue-ceiling streams, the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the positions and velocities the last timed step left as DIR/positions.npy and DIR/velocities.npy "
+                         "(float32; above 64 MB in all, a fixed seeded sample of the rows)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started bare with --gpus N: run the N ranks as CHILD processes of a parent that never touches the GPU (no torch
@@ -418,7 +473,8 @@ def main():
         args.no_ring = True
     named = {"pairs": False, "pairs_overlapped": True}.get(args.fast_form)   # None: auto / ordered
     res = time_mode(nb, torch, dist, args, primary, rank, world, pos, vel, ring=False if args.no_ring else None, ring_overlap=named,
-                    choose=primary == nb.NB_MODE_FAST and not args.no_ring and args.fast_form == "auto", parity=True)
+                    choose=primary == nb.NB_MODE_FAST and not args.no_ring and args.fast_form == "auto", parity=args.full,
+                    dump=args.dump_outputs)
 
     headline_exchange = (res["exchange"] or {}).get("chosen", "collective") if world > 1 else None
 
@@ -467,7 +523,8 @@ def main():
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "preheat": {"ms": args.preheat_ms, "steps": res["preheat_steps"],
                     "what": "untimed steps in front of the warm-up steps of every leg, until the clock ramp that follows an idle gap is over "
-                            "(--preheat-ms 0: none); the timed region is exactly `steps` steps"},
+                            "(--preheat-ms 0: none), then undone: the warm-up starts from the initial state; the timed region is exactly "
+                            "`steps` steps"},
         "ms_per_step": s["ms_per_step"],
         "higher_is_better": True,
         "scaling": "strong",
@@ -497,8 +554,8 @@ def main():
                             "STRICT's own input diverges as fast (tests/test_gpu_parity.py)"},
     }
 
-    # Everything after this point is informational.  If it wedges (a collective that never completes, say), the
-    # headline measured above must still be reported -- and the run must NOT look clean: the watchdog prints the line
+    # Everything after this point is informational, and runs with --full only.  If it wedges (a collective that never completes,
+    # say), the headline measured above must still be reported -- and the run must NOT look clean: the watchdog prints the line
     # with the leg that was running and ends this rank with exit code 3.
     import threading
 
@@ -512,9 +569,10 @@ def main():
 
     watchdog = threading.Timer(args.aux_timeout, give_up)
     watchdog.daemon = True
-    watchdog.start()
+    if args.full:
+        watchdog.start()
 
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         other_mode = nb.NB_MODE_FAST if primary == nb.NB_MODE_STRICT else nb.NB_MODE_STRICT
         leg["name"] = "other_mode"
         try:
@@ -698,7 +756,7 @@ def main():
             except Exception as e:  # pragma: no cover
                 line["dropin_call_us"] = {"error": repr(e)}
 
-    if world == 1:
+    if args.full and world == 1:
         # Last of the GPU legs: these streams load the vector ALU harder than any kernel here, and the part answers a
         # sustained load by lowering its clock for tens of milliseconds -- timed before the other legs they slow them down.
         leg["name"] = "measured_issue_ceiling"
@@ -762,7 +820,7 @@ def main():
         except Exception as e:  # pragma: no cover
             line["roofline"]["measured_issue_ceiling"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         leg["name"] = "cpu_baseline"
         import oracle  # cpu_baseline leg: the oracle is timed here, never used by the product path
 

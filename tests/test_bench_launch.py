@@ -32,11 +32,46 @@ def test_bare_gpus_2_starts_two_ranks_and_propagates_their_exit_code():
     assert "WORLD_SIZE=1" not in r.stderr
 
 
+def test_steps_and_warmup_are_checked_and_the_new_options_are_there():
+    """--steps is the number of timed steps: at least one (ms_per_step divides by it); --full and --dump-outputs exist.  Checked
+    before anything imports torch or touches a device."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
+    r = subprocess.run([sys.executable, BENCH, "--help"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_what_its_last_step_left(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: one line with the headline, none of the informational legs; with
+    --dump-outputs the state after the warm-up and the timed steps (the preheat's steps undone) as float32 arrays -- for STRICT every
+    bit of it the CPU oracle's at step W + K (tests/golden/nbody_golden_c3.npz), so two runs and two builds compare."""
+    import numpy as np
+
+    import bench
+
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["unit"] == "body-updates/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 2
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["value"] == pytest.approx(131072 * 1e3 / line["ms_per_step"], rel=1e-9)
+    assert line["preheat"]["steps"] > 0 and line["parity_check"] is None
+    assert not {"other_mode", "force_3d", "boids_controller", "unpreheated", "dropin_call_us", "cpu_baseline"} & set(line)
+    assert "measured_issue_ceiling" not in line["roofline"]
+    p, v = np.load(out / "positions.npy"), np.load(out / "velocities.npy")
+    assert p.dtype == v.dtype == np.float32 and p.shape == v.shape == (131072, 3)
+    assert bench.parity_against_golden(131072, 1234, 1 + 2, p, v)["bits_equal"] is True
+
+
 @pytest.mark.gpu
 def test_bare_gpus_2_rehearsal_prints_one_json_line():
     """Exactly the driver's command shape at N = 2, on the one GPU of the test box: two ranks share the device and exchange
     through gloo (NB_BENCH_BACKEND=gloo), which the line must own up to in `data`.  No scaling number is claimed."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        env=_env(NB_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -55,10 +90,11 @@ def test_bare_gpus_2_rehearsal_prints_one_json_line():
     assert over["partners"] == 1 and over["value"] > 0 and over["kernel_ms"] > 0
     chosen = line["fast_form_chosen_by_timing"]
     assert chosen["chosen"] in ("pairs", "pairs_overlapped", "ordered") and set(chosen["ms_per_step"]) == {"pairs", "pairs_overlapped", "ordered"}
-    # the line proves its own parity: after preheat + warm-up + timed steps on TWO ranks every bit of the state is the CPU oracle's at
-    # that step (tests/golden/nbody_golden_c3.npz), and it says what the communicator saw
+    # the line proves its own parity: after warm-up + timed steps on TWO ranks (the preheat's steps undone) every bit of the state is
+    # the CPU oracle's at that step (tests/golden/nbody_golden_c3.npz), and it says what the communicator saw
     pc = line["parity_check"]
-    assert pc["bits_equal"] is True and pc["k"] == line["preheat"]["steps"] + 1 + 2 and pc["checksums"]["xor"] == pc["checksums"]["golden_xor"]
+    assert line["preheat"]["steps"] > 0
+    assert pc["bits_equal"] is True and pc["k"] == 1 + 2 and pc["checksums"]["xor"] == pc["checksums"]["golden_xor"]
     comm = line["comm"]
     assert comm["backend"] == "gloo" and comm["world"] == 2 and comm["distinct_devices"] == 1 and len(comm["device_uuids"]) == 2
     # both kinds of exchange were verified on a pattern and timed; on a shared card the pulls over IPC beat gloo's detour through the host
@@ -74,7 +110,7 @@ def test_gpus_4_mode_fast_rehearsal_takes_the_pairs_form_as_the_headline():
     step's exchanges go through gloo -- the all-gather and the point-to-point one to the TWO ranks in front.  The headline of that
     line is the pairs form on shards; no scaling number is claimed."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--mode", "fast", "--fast-form", "pairs", "--steps", "2", "--warmup", "1",
-                        "--preheat-ms", "20", "--no-cpu-baseline", "--no-secondary"],
+                        "--preheat-ms", "20", "--no-cpu-baseline", "--no-secondary", "--full"],
                        env=_env(NB_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -101,7 +137,8 @@ def test_gpus_4_mode_fast_rehearsal_chooses_its_form_by_timing_and_runs_the_phas
     timed region runs the fastest, and the line says which and what each cost.  Then the same with the overlapped form named: the
     step in phases as the headline.  (Four ranks: the pool's process guard allows six processes on a card, so the world of eight is
     rehearsed as threads -- tests/test_gpu_native_shard.py -- and over gloo on the CPU -- tests/test_dist_gloo.py.)"""
-    base = [sys.executable, BENCH, "--gpus", "4", "--mode", "fast", "--steps", "2", "--warmup", "1", "--preheat-ms", "20", "--no-cpu-baseline", "--no-secondary"]
+    base = [sys.executable, BENCH, "--gpus", "4", "--mode", "fast", "--steps", "2", "--warmup", "1", "--preheat-ms", "20", "--no-cpu-baseline", "--no-secondary",
+            "--full"]
     r = subprocess.run(base, env=_env(NB_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -122,14 +159,15 @@ def test_gpus_5_strict_ragged_rehearsal_proves_its_parity():
     """`bench.py --gpus 5` over gloo on the one card (five ranks + this process: the pool's process guard allows six on a card): a
     world that does not divide 131 072 -- slots of 26 215 bodies, the last rank short --, every rank in the block chain, the in-place
     all-gather verified on a pattern first, and the line's own parity check: after preheat + warm-up + timed steps every bit of the
-    state is the CPU oracle's at that step (STRICT does not depend on the world)."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "5", "--steps", "3", "--warmup", "1", "--preheat-ms", "30", "--no-cpu-baseline", "--no-secondary"],
+    state is the CPU oracle's at that step (STRICT does not depend on the world; the preheat's steps are undone)."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "5", "--steps", "3", "--warmup", "1", "--preheat-ms", "30", "--no-cpu-baseline", "--no-secondary",
+                        "--full"],
                        env=_env(NB_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert line["n_gpus"] == 5 and "x5" in line["config"]["sharding"] and line["config"]["mode"] == "strict"
     pc = line["parity_check"]
-    assert pc["bits_equal"] is True and pc["k"] == line["preheat"]["steps"] + 1 + 3
+    assert line["preheat"]["steps"] > 0 and pc["bits_equal"] is True and pc["k"] == 1 + 3
     assert line["comm"]["world"] == 5 and line["comm"]["distinct_devices"] == 1 and len(line["comm"]["device_uuids"]) == 5
     assert line["comm"]["exchange_paths"]["verified"] and line["comm"]["exchange_paths"]["all_gather"] in ("peers", "in_place")
     assert line["comm"]["exchange"]["mapped"] is True
@@ -155,7 +193,9 @@ def _preheat_rank(rank, world, port, out_dir):
         dist.all_reduce(t)
         calls.append(float(t.item()))
 
-    count = bench.preheat(step, torch, dist, world, torch.device("cpu"), 60.0)
+    dist.barrier()   # (the ranks start together: the two steps the preheat times are steps, not the others' start-up)
+    # a span of many steps, so that a loaded host that slows every step several times over still leaves more than the two timed ones
+    count = bench.preheat(step, torch, dist, world, torch.device("cpu"), 500.0)
     dist.barrier()
     with open(os.path.join(out_dir, f"rank{rank}.json"), "w") as f:
         json.dump({"count": count, "calls": len(calls), "sums": sorted(set(calls))}, f)

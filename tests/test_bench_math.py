@@ -106,3 +106,21 @@ def test_the_bench_lines_own_parity_check(oracle):
     for k, n, seed in ((0, N, 1234), (1001, N, 1234), (5, 4096, 1234), (5, N, 99)):
         r = bench.parity_against_golden(n, seed, k, p[:n], v[:n])
         assert r["bits_equal"] is None and "why" in r
+
+
+def test_dumped_outputs_are_float32_files_and_a_fixed_sample_above_the_limit(tmp_path):
+    """--dump-outputs (write_outputs): every array as <name>.npy in float32; where they pass the size limit together, the same
+    seeded rows of each, the same rows from run to run."""
+    import numpy as np
+
+    p = np.arange(30, dtype=np.float32).reshape(10, 3)
+    v = -np.arange(30, dtype=np.float64).reshape(10, 3)
+    assert bench.write_outputs(str(tmp_path / "all"), {"positions": p, "velocities": v}) is None
+    got_p, got_v = np.load(tmp_path / "all" / "positions.npy"), np.load(tmp_path / "all" / "velocities.npy")
+    assert got_p.dtype == got_v.dtype == np.float32 and (got_p == p).all() and (got_v == v).all()
+    rows = bench.write_outputs(str(tmp_path / "a"), {"positions": p, "velocities": v}, limit=4 * 24)
+    assert len(rows) == 4 and (np.diff(rows) > 0).all()
+    assert (np.load(tmp_path / "a" / "positions.npy") == p[rows]).all() and (np.load(tmp_path / "a" / "velocities.npy") == v[rows]).all()
+    again = bench.write_outputs(str(tmp_path / "b"), {"positions": p, "velocities": v}, limit=4 * 24)
+    assert (again == rows).all()
+    assert (tmp_path / "a" / "positions.npy").stat().st_size + (tmp_path / "a" / "velocities.npy").stat().st_size < 4 * 24 + 2 * 256

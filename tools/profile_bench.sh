@@ -3,7 +3,7 @@
 #   OUTDIR/stats_{strict,fast}  rocprofv3 --kernel-trace --stats of `bench.py --mode M --no-secondary --steps 100`: ONE arithmetic per run, so
 #                               a kernel's average duration is that of the bench's own timed launches (the 3-D leg of the full
 #                               bench runs the same kernel template on slower data and would skew it)
-#   OUTDIR/stats_all            the same of the full default bench command (boids, 3-D legs, the issue-ceiling streams)
+#   OUTDIR/stats_all            the same of `bench.py --full` (boids, 3-D legs, the issue-ceiling streams)
 #   OUTDIR/pmc/M_pN             one --pmc pass per counter set and arithmetic (never combined with a trace domain other than
 #                               --kernel-trace), over a short bench run; tools/pmc_summary.py reduces them (and writes
 #                               profiles/hbm_traffic.json)
@@ -19,7 +19,7 @@ for mode in strict fast; do
     echo "stats $mode rc=$?"
 done
 mkdir -p "$OUT/stats_all"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats_all" -- python3 "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/bench_all_under_rocprof.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats_all" -- python3 "$ROOT/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --full > "$OUT/bench_all_under_rocprof.log" 2>&1
 echo "stats all rc=$?"
 for mode in strict fast; do
     i=0
