@@ -60,6 +60,8 @@ def load() -> ctypes.CDLL:
         lib.nbo_run_f64.restype = i
         lib.nbo_step_range_dv_f64.argtypes = [vp, vp, u32, u32, u32, ctypes.c_double, ctypes.c_double, ctypes.c_double]
         lib.nbo_step_range_dv_f64.restype = None
+        lib.nbo_step_range_dv_cond_f64.argtypes = [vp, vp, vp, u32, u32, u32, ctypes.c_double, ctypes.c_double, ctypes.c_double, i]
+        lib.nbo_step_range_dv_cond_f64.restype = None
         lib.nbo_cameras.argtypes = [vp, vp, vp, vp, vp, u32]
         lib.nbo_cameras.restype = None
         lib.nbo_random_step_range.argtypes = [vp, vp, vp, u32, u32, u64, u64]
@@ -177,6 +179,18 @@ def step_range_dv_f64(old_pos, first: int, count: int, dt=0.1, g=0.001, bias=0.0
     dv = np.empty((count, 3), np.float64)
     load().nbo_step_range_dv_f64(old.ctypes.data, dv.ctypes.data, len(old), first, count, float(dt), float(g), float(bias))
     return dv
+
+
+def step_range_dv_cond_f64(old_pos, first: int, count: int, dt=DT, g=G, bias=BIAS, threads: int = 0):
+    """(dv, S) of bodies [first, first+count), both (count, 3) binary64: dv = dt * sum_j t_ij and S = sum_j |t_ij|, the condition of
+    the sum, with t_ij = ((p_j - p_i) * G) / (|p_j - p_i|^2 + bias) in binary64 from the binary32 snapshot.  The defaults are the
+    binary32 roundings of the reference's constants -- the values a binary32 kernel computes with."""
+    old = np.ascontiguousarray(old_pos, np.float32)
+    dv = np.empty((count, 3), np.float64)
+    cond = np.empty((count, 3), np.float64)
+    load().nbo_step_range_dv_cond_f64(old.ctypes.data, dv.ctypes.data, cond.ctypes.data, len(old), first, count, float(dt), float(g),
+                                      float(bias), threads or ncores())
+    return dv, cond
 
 
 def boids_params() -> BoidsParams:

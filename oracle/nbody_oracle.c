@@ -707,3 +707,61 @@ NBO_API void nbo_step_range_dv_f64(const float *old_pos3, double *dv3_out, uint3
         dv3_out[3 * (size_t)l + 2] = sz * dt;
     }
 }
+
+/* nbo_step_range_dv_f64 with the condition of each sum: for bodies [first, first+count), dv3_out = dt * sum_j t_ij and
+ * cond3_out = sum_j |t_ij| per component, t_ij = ((p_j - p_i) * G) / (|p_j - p_i|^2 + bias) in binary64 from the binary32
+ * snapshot.  Pass the binary32 roundings of dt, G and bias (the kernel's constants) to measure a binary32 step against it.
+ * nthreads workers split the bodies (the sums of one body stay on one thread, in index order). */
+typedef struct {
+    const float *old_pos3;
+    double *dv3, *cond3;
+    uint32_t n_total, first, count;
+    double dt, G, bias;
+} nbo_cond_job;
+
+static void *nbo_cond_worker(void *arg)
+{
+    const nbo_cond_job *j = (const nbo_cond_job *)arg;
+    for (uint32_t l = 0; l < j->count; ++l) {
+        const size_t b = (size_t)j->first + l;
+        const double px = j->old_pos3[3 * b], py = j->old_pos3[3 * b + 1], pz = j->old_pos3[3 * b + 2];
+        double s[3] = {0, 0, 0}, c[3] = {0, 0, 0};
+        for (uint32_t i = 0; i < j->n_total; ++i) {
+            const double v[3] = {(double)j->old_pos3[3 * (size_t)i] - px, (double)j->old_pos3[3 * (size_t)i + 1] - py,
+                                 (double)j->old_pos3[3 * (size_t)i + 2] - pz};
+            const double dist = ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + j->bias;
+            for (int k = 0; k < 3; ++k) {
+                const double t = (v[k] * j->G) / dist;
+                s[k] += t;
+                c[k] += fabs(t);
+            }
+        }
+        for (int k = 0; k < 3; ++k) {
+            j->dv3[3 * (size_t)l + k] = s[k] * j->dt;
+            j->cond3[3 * (size_t)l + k] = c[k];
+        }
+    }
+    return NULL;
+}
+
+NBO_API void nbo_step_range_dv_cond_f64(const float *old_pos3, double *dv3_out, double *cond3_out, uint32_t n_total, uint32_t first,
+                                        uint32_t count, double dt, double G, double bias, int nthreads)
+{
+    if (nthreads < 1) nthreads = 1;
+    if ((uint32_t)nthreads > count) nthreads = count ? (int)count : 1;
+    pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nthreads);
+    nbo_cond_job *jobs = (nbo_cond_job *)malloc(sizeof(nbo_cond_job) * (size_t)nthreads);
+    for (int t = 0; t < nthreads; ++t) {
+        const uint32_t lo = (uint32_t)(((uint64_t)count * (uint64_t)t) / (uint64_t)nthreads);
+        const uint32_t hi = (uint32_t)(((uint64_t)count * (uint64_t)(t + 1)) / (uint64_t)nthreads);
+        jobs[t] = (nbo_cond_job){old_pos3, dv3_out + 3 * (size_t)lo, cond3_out + 3 * (size_t)lo, n_total, first + lo, hi - lo, dt, G, bias};
+        if (nthreads == 1)
+            nbo_cond_worker(&jobs[t]);
+        else
+            pthread_create(&th[t], NULL, nbo_cond_worker, &jobs[t]);
+    }
+    if (nthreads > 1)
+        for (int t = 0; t < nthreads; ++t) pthread_join(th[t], NULL);
+    free(jobs);
+    free(th);
+}

@@ -14,7 +14,7 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def ring_steps_on_one_gpu(nb, pos, vel, world, params, steps=1, keep=None, phases=False):
+def ring_steps_on_one_gpu(nb, pos, vel, world, params, steps=1, keep=None, phases=False, corrupt=None):
     """`steps` steps of an n-body set cut into `world` equal ranks, every rank's fold and finish on the one GPU, the second
     exchange and the all-gather by hand.  Returns (positions, velocities).  keep: a dict that receives the ranks' `sums`.
     phases: False = nb_launch_ring_fold; True = the step in phases (nb_launch_ring_fold_phase) in the order a host with the
@@ -71,6 +71,8 @@ def ring_steps_on_one_gpu(nb, pos, vel, world, params, steps=1, keep=None, phase
         for r in range(world):
             for d in range(1, D + 1):
                 recv[r][(d - 1) * S:d * S] = sums[(r - d) % world][d * S:(d + 1) * S]
+        if corrupt is not None:
+            corrupt(step, recv)
         for r in range(world):
             if fused:
                 be.ring_finish_phase(params, n, r * S, S, cur, nxt, vels[r], None if in_finish else sums[r], recv[r], scratch[r])
