@@ -46,9 +46,23 @@ def reference(oracle, pos, vel, schedule):
 SCHEDULE = (("nbody", 2), ("boids", 2), ("nbody", 1), ("boids", 1))
 
 
-def drive(sh, schedule):
-    for what, k in schedule:
-        sh.step(k) if what == "nbody" else sh.step_boids(k)
+def drive(sh, schedule, after_each=None):
+    """schedule: (what, k) or (what, k, boids constants as a dict); after_each(sh) is called after every entry"""
+    import nenbody_amd
+
+    for what, k, *consts in schedule:
+        if what == "nbody":
+            sh.step(k)
+        else:
+            bp = None
+            if consts:
+                bp = nenbody_amd.default_boids_params()
+                for name, value in consts[0].items():
+                    setattr(bp, name, value)
+            sh.step_boids(k, bp)
+        if after_each is not None:
+            sh.sync()
+            after_each(sh)
     sh.sync()
 
 
@@ -150,7 +164,10 @@ def _hip_runtime():
 
 
 def _rank_worker(rank, world, port, n, mode, out_dir, overlap=False, schedule=None, with_ring=False, seed=None, force_pairs=False,
-                 verify=None, peers=False):
+                 verify=None, peers=False, boids_split=False, state=None, nbody=None):
+    """one rank of a world on the one GPU; state = (pos, vel) replaces the generated one, nbody = {dt, G, bias} the n-body
+    constants, boids_split=True the boids step's split form; with `state`, the positions and local velocities after every schedule
+    entry are saved as pos_<k>, vel_<k>"""
     import sys
 
     from conftest import ROOT
@@ -208,10 +225,13 @@ def _rank_worker(rank, world, port, n, mode, out_dir, overlap=False, schedule=No
             dist.all_gather_object(every, blob)
             return b"".join(every)
 
-        pos, vel = state3d(oracle, n, seed=n) if seed is None else oracle.init_state(n, seed)
-        with nenbody_amd.NativeShard(pos, vel, nenbody_amd.default_params(mode=mode), rank=rank, world=world,
+        pos, vel = state if state is not None else state3d(oracle, n, seed=n) if seed is None else oracle.init_state(n, seed)
+        params = nenbody_amd.default_params(mode=mode)
+        for name, value in (nbody or {}).items():
+            setattr(params, name, value)
+        with nenbody_amd.NativeShard(pos, vel, params, rank=rank, world=world,
                                      gather=None if peers == "only" else gather, overlap=overlap, ring=ring if (with_ring and peers != "only") else None,
-                                     peers=swap_blobs if peers else None) as sh:
+                                     peers=swap_blobs if peers else None, boids_split=boids_split) as sh:
             extra = {}
             if verify in ("lossy_pulls", "stale_pulls"):   # pulls that lose a record on rank 0 / that deliver the first time only (the second
                 # pattern round catches those): every rank goes back to the host's exchanges, in both
@@ -240,7 +260,10 @@ def _rank_worker(rank, world, port, n, mode, out_dir, overlap=False, schedule=No
                 extra = dict(chosen=chosen, ms=np.array(ms))
                 calls.clear(), ring_calls.clear()
             partners, overlapped = sh.partners, sh.pairs_overlapped
-            drive(sh, schedule or SCHEDULE)
+            every = []
+            drive(sh, schedule or SCHEDULE, (lambda sh_: every.append((sh_.positions(), sh_.local_velocities()))) if state is not None else None)
+            for k, (p_k, v_k) in enumerate(every):
+                extra[f"pos_{k}"], extra[f"vel_{k}"] = p_k, v_k
             np.savez(os.path.join(out_dir, f"rank{rank}.npz"), pos=sh.positions(), vel=sh.local_velocities(),
                      inst=sh.local_instances(), first=sh.first, count=sh.count, calls=len(calls), ring_calls=len(ring_calls),
                      partners=partners, overlapped=overlapped, **extra)

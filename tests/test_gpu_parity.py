@@ -1232,7 +1232,10 @@ def test_instances_edge_cases(nb, oracle):
 # several ranks on the one GPU of this box (gloo, positions gathered through the host): the real multi-rank
 # control flow with the real HIP kernels.  RCCL itself needs one GPU per rank and is the driver's to run.
 # ---------------------------------------------------------------------------------------------------------
-def _rank_worker(rank, world, port, n, k, mode, out_dir, overlap=False):
+def _rank_worker(rank, world, port, n, k, mode, out_dir, overlap=False, boids_split=False, state=None, schedule=None, nbody=None):
+    """one rank of a ShardedScene world on the one GPU: k n-body steps; or with `schedule` ((what, k) or (what, k, boids constants
+    as a dict)) those steps, boids through step_boids(split=boids_split), on state = (pos, vel) with n-body constants `nbody`
+    ({dt, G, bias}), the state after every entry saved as pos_<i>, vel_<i>"""
     import sys
 
     from conftest import ROOT
@@ -1248,13 +1251,34 @@ def _rank_worker(rank, world, port, n, k, mode, out_dir, overlap=False):
         import nenbody_amd
 
         torch.cuda.set_device(0)
-        pos, vel = nenbody_amd.init_state(n, 99)
-        pos[:, 2] = np.linspace(-50, 50, n, dtype=np.float32)
-        sc = nenbody_amd.ShardedScene(pos, vel, nenbody_amd.default_params(mode=mode), overlap=overlap)
+        if state is None:
+            pos, vel = nenbody_amd.init_state(n, 99)
+            pos[:, 2] = np.linspace(-50, 50, n, dtype=np.float32)
+        else:
+            pos, vel = state
+        params = nenbody_amd.default_params(mode=mode)
+        for name, value in (nbody or {}).items():
+            setattr(params, name, value)
+        sc = nenbody_amd.ShardedScene(pos, vel, params, overlap=overlap)
         assert sc.overlap == (overlap and mode == nenbody_amd.NB_MODE_FAST)
-        sc.step_n(k)
-        sc.sync()
-        np.savez(os.path.join(out_dir, f"rank{rank}.npz"), pos=sc.positions(), vel=sc.velocities())
+        every = {}
+        for i, (what, steps, *consts) in enumerate(schedule or (("nbody", k),)):
+            if what == "nbody":
+                sc.step_n(steps)
+            else:
+                bp = nenbody_amd.default_boids_params()
+                for name, value in (consts[0] if consts else {}).items():
+                    setattr(bp, name, value)
+                for _ in range(steps):
+                    sc.step_boids(bp, split=boids_split)
+                scratch = getattr(sc, "_boids_partial", None)
+                if boids_split and scratch is not None:   # the split form's scratch: its size and the step's flag word at its end
+                    nbytes = scratch.numel()
+                    every[f"scratch_{i}"] = nbytes
+                    every[f"flags_{i}"] = int(scratch[nbytes - 64:nbytes - 60].cpu().numpy().view(np.uint32)[0])
+            sc.sync()
+            every[f"pos_{i}"], every[f"vel_{i}"] = sc.positions(), sc.velocities()
+        np.savez(os.path.join(out_dir, f"rank{rank}.npz"), pos=sc.positions(), vel=sc.velocities(), **every)
     finally:
         dist.destroy_process_group()
 
