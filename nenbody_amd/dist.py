@@ -239,6 +239,7 @@ class ShardedScene:
         self.gather_in_place = True      # RCCL all-gather with this rank's slot of the receive buffer as the send buffer
         self.ring_grouped = True         # the second exchange as ONE group of sends and receives (else: one group per distance)
         self.exchange_report = None
+        self._collective_verdict = None  # the latest verify_exchanges() verdict on the collectives' paths (the pulls have their own)
         # "collective": torch.distributed (RCCL over xGMI: all-gather, grouped send / receive); "peers": pulls over xGMI ordered by
         # stream value waits (nb_peers_*, include/nenbody.h: no collective kernel, no second stream) for the position replicas and
         # `sums` -- everything else (velocities on demand, the boids controller's staging buffer) stays collective
@@ -413,10 +414,14 @@ class ShardedScene:
         in-place all-gather and the grouped sends / receives of the pairs form had run on a one-rank communicator and over gloo
         only when this was written (no multi-GPU box in the build); a mismatch moves the exchange to its fallback -- the all-gather
         from a copy of the slot, the second exchange as one group per distance, and, should that fail too, the ordered fold with its
-        one exchange -- without restarting anything.  Returns (and keeps as ``exchange_report``) which paths the steps will take.
+        one exchange -- without restarting anything.  With pulls over xGMI (``exchange == "peers"``) the pulls are checked first;
+        should either exchange not arrive through them, both go back to the collectives, which are then verified as above.  A check
+        of the pulls leaves the collectives' paths (``gather_in_place``, ``ring_grouped``) as an earlier verdict set them.
+        Returns (and keeps as ``exchange_report``) which paths the steps will take; its "collective" entry is the latest verdict on
+        the collectives (None: not verified yet), kept apart from the verdict on the pulls.
         Buffers used: the scratch side of the position ping-pong, ``sums`` / ``recv`` (every step overwrites them)."""
         torch, dist = self.torch, self.dist
-        rep = {"world": self.world, "all_gather": None, "ring_exchange": None, "verified": False}
+        rep = {"world": self.world, "all_gather": None, "ring_exchange": None, "verified": False, "collective": None}
         if self.world == 1:
             self.exchange_report = rep
             return rep
@@ -432,50 +437,56 @@ class ShardedScene:
             i = torch.arange(records, dtype=torch.float32, device=self.device)
             return torch.stack([i + 1000.0 * rank + salt, -i, torch.full_like(i, float(rank)), torch.full_like(i, float(salt))], dim=1)
 
-        # -- the all-gather: every slot of the buffer must hold its rank's pattern
-        buf = self.pos[self.cur ^ 1]
-        # (with pulls over xGMI the first attempt is the pulls; a mismatch sends BOTH exchanges back to the collectives.  The pulls are
-        # checked TWICE from the same buffers with different patterns: a reader that kept lines of a peer's memory in a cache would pass
-        # the first round and show the first pattern again in the second.  The agreement between the rounds is also the barrier that
-        # lets a rank rewrite a buffer its peers have pulled from.)
-        for attempt in (("peers",) if self.exchange == "peers" else ()) + ("in_place", "out_of_place"):
-            if attempt != "peers":
-                self.exchange = "collective"
-            self.gather_in_place = attempt != "out_of_place"
-            bad = False
-            for salt in (7.0, 9.0) if attempt == "peers" else (7.0,):
+        def gather_delivers(salts) -> bool:   # the all-gather: every slot of the buffer must hold its rank's pattern
+            buf = self.pos[self.cur ^ 1]
+            ok = True
+            for salt in salts:
                 want = torch.cat([pattern(r, self.slot, salt) for r in range(self.world)])
                 buf.fill_(float("nan"))
                 buf[self.rank * self.slot:(self.rank + 1) * self.slot] = want[self.rank * self.slot:(self.rank + 1) * self.slot]
                 self._all_gather_slots(buf)
-                bad = agree(not torch.equal(buf, want))
-                if bad:
+                if agree(not torch.equal(buf, want)):
+                    ok = False
                     break
-            if not bad:
+            buf.zero_()
+            return ok
+
+        def ring_delivers(salts) -> bool:   # the pairs form's second exchange: chunk d - 1 of recv must hold chunk d of rank - d's sums
+            S = self.count
+            for salt in salts:
+                want = torch.cat([pattern((self.rank - d) % self.world, S, salt + d) for d in range(1, self.partners + 1)])
+                self.sums[:S].zero_()
+                for d in range(1, self.partners + 1):
+                    self.sums[d * S:(d + 1) * S] = pattern(self.rank, S, salt + d)
+                self.recv.fill_(float("nan"))
+                self._ring_exchange()
+                if agree(not torch.equal(self.recv, want)):
+                    return False
+            return True
+
+        # -- the pulls: each exchange checked TWICE from the same buffers with different patterns (a reader that kept lines of a
+        # peer's memory in a cache would pass the first round and show the first pattern again in the second; the agreement between
+        # the rounds is also the barrier that lets a rank rewrite a buffer its peers have pulled from).  One kind of exchange per step:
+        # if either exchange does not arrive, both go back to the collectives.
+        if self.exchange == "peers":
+            if gather_delivers((7.0, 9.0)) and (not self.partners or (self._peers_sums and ring_delivers((0.0, 16.0)))):
+                rep.update(all_gather="peers", ring_exchange="peers" if self.partners else None, verified=True)
+                rep["collective"] = dict(self._collective_verdict) if self._collective_verdict else None
+                self.exchange_report = rep
+                return rep
+            self.exchange = "collective"
+        # -- the collectives
+        for attempt in ("in_place", "out_of_place"):
+            self.gather_in_place = attempt == "in_place"
+            if gather_delivers((7.0,)):
                 rep["all_gather"] = attempt
                 break
-        buf.zero_()
         if rep["all_gather"] is None:
             raise _lib.NbError(_lib.NB_ERR_STATE, "verify_exchanges: the all-gather does not deliver every rank's slot, in place or from a copy")
-        # -- the pairs form's second exchange: chunk d - 1 of recv must hold chunk d of rank - d's sums
         if self.partners:
-            S = self.count
-            for attempt in (("peers",) if self.exchange == "peers" and self._peers_sums else ()) + ("grouped", "per_distance"):
-                if attempt != "peers" and self.exchange == "peers":
-                    self.exchange = "collective"   # (the all-gather goes back too: one kind of exchange per step; it was verified above as pulls, the collective is re-verified by the next call)
-                self.ring_grouped = attempt != "per_distance"
-                bad = False
-                for salt in (0.0, 16.0) if attempt == "peers" else (0.0,):   # (pulls: twice from the same buffers, as above)
-                    want = torch.cat([pattern((self.rank - d) % self.world, S, salt + d) for d in range(1, self.partners + 1)])
-                    self.sums[:S].zero_()
-                    for d in range(1, self.partners + 1):
-                        self.sums[d * S:(d + 1) * S] = pattern(self.rank, S, salt + d)
-                    self.recv.fill_(float("nan"))
-                    self._ring_exchange()
-                    bad = agree(not torch.equal(self.recv, want))
-                    if bad:
-                        break
-                if not bad:
+            for attempt in ("grouped", "per_distance"):
+                self.ring_grouped = attempt == "grouped"
+                if ring_delivers((0.0,)):
                     rep["ring_exchange"] = attempt
                     break
             if rep["ring_exchange"] is None:   # neither form delivers: the ordered fold and its one exchange
@@ -485,6 +496,8 @@ class ShardedScene:
                 sb = self.backend.scratch_bytes(self.params, self.n, self.count) if self.count else 0
                 self.scratch = torch.empty((sb,), dtype=torch.uint8, device=self.device) if sb else None
         rep["verified"] = True
+        self._collective_verdict = {"all_gather": rep["all_gather"], "ring_exchange": rep["ring_exchange"]}
+        rep["collective"] = dict(self._collective_verdict)
         self.exchange_report = rep
         return rep
 
@@ -656,10 +669,11 @@ class ShardedScene:
 
     def choose_exchange(self, steps: int = 6, warm: int = 2) -> str:
         """Which exchange is faster on THIS machine for the form the steps take now: the collectives (RCCL's all-gather and grouped
-        send / receive) or pulls over xGMI ordered by stream value waits (``setup_peers``)?  Verifies the pulls on a pattern first,
-        times ``steps`` steps each way on the state in hand (slowest rank; collective), keeps the faster, puts the state back.
+        send / receive) or pulls over xGMI ordered by stream value waits (``setup_peers``)?  Verifies the pulls on a pattern first
+        (and the collectives, unless an earlier ``verify_exchanges`` did: they are timed on the paths that verdict chose), times
+        ``steps`` steps each way on the state in hand (slowest rank; collective), keeps the faster, puts the state back.
         Returns "peers" or "collective" (``exchange_times``: seconds per step of each; None where the ranks could not map each
-        other's buffers -- another node, no IPC)."""
+        other's buffers -- another node, no IPC); ``exchange_report`` describes the paths of the exchange kept."""
         torch = self.torch
         self.exchange_times = None
         if self.world == 1:
@@ -667,11 +681,16 @@ class ShardedScene:
         self._wait_pending()
         if not self.setup_peers():
             return self.exchange
-        before = self.exchange
+        if self._collective_verdict is None:
+            # the collectives are timed, and may be kept, on the paths a pattern has been seen to arrive through: verify them first
+            self.exchange = "collective"
+            self.verify_exchanges()
         self.exchange = "peers"
-        if self.verify_exchanges()["all_gather"] != "peers" or self.exchange != "peers":   # the pattern did not arrive through the pulls
+        peers_report = self.verify_exchanges()
+        if peers_report["all_gather"] != "peers" or self.exchange != "peers":   # the pattern did not arrive through the pulls
             self.exchange_times = {"peers": None, "collective": None}
             return self.exchange
+        collective_report = dict(peers_report, **peers_report["collective"])   # what the steps take if the collectives are kept
         saved = (self.pos[0].clone(), self.pos[1].clone(), self.vel.clone(), self.cur, self.steps_done, self.velfull_valid)
         times = {}
         for kind in ("collective", "peers"):
@@ -699,7 +718,7 @@ class ShardedScene:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
         self.exchange_times = {"collective": float(t[0]), "peers": float(t[1])}
         self.exchange = "peers" if self.exchange_times["peers"] < self.exchange_times["collective"] else "collective"
-        del before
+        self.exchange_report = peers_report if self.exchange == "peers" else collective_report
         return self.exchange
 
     def close(self) -> None:

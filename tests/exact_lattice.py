@@ -20,7 +20,13 @@ bit for bit, and one dropped or doubled cross-site pair moves the bodies of that
 computed here in integers in O(n), never from a pair loop.
 
 Two steps stay exact if every body of site t starts with w - a_t dt: after the first step every velocity is w, the lattice has
-moved by w undeformed and the second step has the same closed form.
+moved by w undeformed and the second step has the same closed form.  That second step cannot tell a stale record from a fresh one:
+its pair terms are those of the first step, so a rank that reads last step's forces, last step's positions of a whole slot, or a
+slot of its own one step late still reproduces it.  `permute` = pi, a permutation of the kind's sites that moves every occupied
+one, closes that gap: the bodies of site t start with w + (P_pi(t) - P_t) - a_t dt, so the first step carries every site onto
+ANOTHER site (plus w).  Distinct sites stay distinct and equidistant, so every value stays on the grid, but the second step's
+closed form is K'_t = sum_u c_u (P_pi(u) - P_pi(t)), which `lattice` requires to differ from the first step's K_t on every
+occupied site: one stale record then moves its bodies.  (tetra_mixed: bodies also change layer, planar and 3-D, between steps.)
 
 `lattice` refuses (ValueError) any parameters for which a value of either step would leave the exact range.
 """
@@ -62,6 +68,11 @@ class Lattice:
     v_exp: np.ndarray
     site: np.ndarray           # (n,) site of every body
     counts: np.ndarray         # bodies per site
+    K: np.ndarray              # (T, 3) integers: the first step's acceleration of site t, sum_u c_u (P_u - P_t) / s
+    K2: np.ndarray             # (T, 3) the second step's (steps=2; None for one): K'_t = sum_u c_u (P_pi(u) - P_pi(t)) / s
+    permute: tuple             # pi (steps=2 with `permute`), else None
+    p_mid: np.ndarray          # (n, 3) binary32: the exact state after the first step
+    v_mid: np.ndarray
     unit: float                # the grid every position and velocity lies on
     dv_pair: float             # |dv| one cross-site pair adds in a component where its sites differ
     margin_bits: float         # log2(2^24 / the largest integer in units of `unit` or of the terms)
@@ -74,11 +85,11 @@ class Lattice:
 
     def describe(self) -> str:
         return (f"lattice(n={len(self.pos)}, kind={self.kind}, scale=2^{_pow2(self.scale, 'scale')}, G={float(self.G)!r}, "
-                f"dt={float(self.dt)!r}, steps={self.steps}, counts={self.counts.tolist()}, margin {self.margin_bits:.1f} bits)")
+                f"dt={float(self.dt)!r}, steps={self.steps}, counts={self.counts.tolist()}, permute={self.permute}, margin {self.margin_bits:.1f} bits)")
 
 
 def lattice(n: int, seed: int = 0, kind: str = "tetra", scale: float = 1.0, G0: float = -2.0 ** -3, dt: float = 2.0 ** -1,
-            steps: int = 1, runs: int = 0, empty=(), skew=None, vmax: int = 1 << 10, sites=None) -> Lattice:
+            steps: int = 1, runs: int = 0, empty=(), skew=None, vmax: int = 1 << 10, sites=None, permute=None) -> Lattice:
     """The exact state described in the module docstring.
 
     runs:  0 = every body's site drawn at random; r > 0 = one site per run of r consecutive bodies (whole tiles, blocks or ranks
@@ -86,6 +97,8 @@ def lattice(n: int, seed: int = 0, kind: str = "tetra", scale: float = 1.0, G0: 
     empty: sites that get no body.   skew: relative weights of the sites (default: equal).
     vmax:  one step: velocities are random multiples of the unit in [-vmax, vmax]; two steps: w is.
     sites: the site of every body, given outright (overrides runs, empty and skew).
+    permute: steps=2 only: pi, the site every site moves onto in the first step (module docstring).  Refused unless it is a
+           permutation of the kind's sites that moves every occupied site and changes the acceleration of every occupied site.
     """
     if kind not in KINDS:
         raise ValueError(f"unknown kind {kind!r}")
@@ -93,6 +106,8 @@ def lattice(n: int, seed: int = 0, kind: str = "tetra", scale: float = 1.0, G0: 
         raise ValueError("steps must be 1 or 2")
     if n < 1:
         raise ValueError("n must be positive")
+    if permute is not None and steps != 2:
+        raise ValueError("permute needs steps=2: it moves the sites between the two steps")
     sites_u, offset_u, bias_u, den_u = KINDS[kind]
     sites_u = np.array(sites_u, np.int64)
     T = len(sites_u)
@@ -133,6 +148,21 @@ def lattice(n: int, seed: int = 0, kind: str = "tetra", scale: float = 1.0, G0: 
 
     # integer counts: K[t] = sum_u c_u (P_u - P_t) / s, the acceleration of site t in units of G0 s / den_u
     K = (counts[:, None, None] * (sites_u[:, None, :] - sites_u[None, :, :])).sum(axis=0)    # (T, 3): [t] = sum_u c_u (P_u - P_t)
+    perm = np.arange(T)
+    if permute is not None:
+        perm = np.asarray(permute)
+        if perm.shape != (T,) or perm.dtype.kind not in "iu" or sorted(perm.tolist()) != list(range(T)):
+            raise ValueError(f"permute = {permute!r} is not a permutation of the {T} sites of {kind}")
+        fixed = [t for t in range(T) if perm[t] == t and counts[t]]
+        if fixed:
+            raise ValueError(f"permute = {permute!r} leaves occupied site(s) {fixed} in place")
+    moved = sites_u[perm]                             # the site every site stands on in the second step
+    K2 = (counts[:, None, None] * (moved[:, None, :] - moved[None, :, :])).sum(axis=0)        # [t] = sum_u c_u (P_pi(u) - P_pi(t))
+    if permute is not None:
+        same = [t for t in range(T) if counts[t] and (K2[t] == K[t]).all()]
+        if same:
+            raise ValueError(f"permute = {permute!r}: occupied site(s) {same} keep their acceleration in the second step "
+                             f"(K'_t == K_t: a stale record of them would be invisible)")
     sgn = int(np.sign(G0) * np.sign(dt))
     r = int(round(vunit / unit))                  # velocity units per grid unit (a power of two >= 1)
     q = int(round(s / unit))                      # grid units per s
@@ -148,15 +178,15 @@ def lattice(n: int, seed: int = 0, kind: str = "tetra", scale: float = 1.0, G0: 
         w = rng.integers(-vmax, vmax + 1, size=3).astype(np.int64) * r
         if planar_z:
             w[2] = 0
-        v0 = w[None, :] - (sgn * K * r)[site]
+        v0 = w[None, :] + (P[perm] - P)[site] - (sgn * K * r)[site]
     dv = (sgn * K * r)[site]                        # per body, grid units
     p0 = P[site]
     v1 = v0 + dv
     p1 = p0 + v1
     vals = [p0, v0, v1, p1]
     if steps == 2:
-        assert (v1 == w[None, :]).all()
-        v2 = v1 + dv
+        assert (p1 == P[perm][site] + w[None, :]).all()
+        v2 = v1 + (sgn * K2 * r)[site]
         p2 = p1 + v2
         vals += [v2, p2]
     biggest = max(int(np.abs(a).max()) for a in vals)
@@ -167,11 +197,14 @@ def lattice(n: int, seed: int = 0, kind: str = "tetra", scale: float = 1.0, G0: 
         raise ValueError("a position or velocity overflows binary32")
     to_f = lambda a: (a.astype(np.float64) * unit).astype(np.float32)   # exact: |a| < 2^24 and unit a power of two
     pos, vel = to_f(p0), to_f(v0)
-    p_exp, v_exp = (to_f(p1), to_f(v1)) if steps == 1 else (to_f(p2), to_f(v2))
-    for a, b in ((pos, p0), (vel, v0), (p_exp, p1 if steps == 1 else p2)):
+    p_mid, v_mid = to_f(p1), to_f(v1)
+    p_exp, v_exp = (p_mid, v_mid) if steps == 1 else (to_f(p2), to_f(v2))
+    for a, b in ((pos, p0), (vel, v0), (p_mid, p1), (v_mid, v1), (p_exp, p1 if steps == 1 else p2)):
         assert (a.astype(np.float64) / unit == b).all()
     return Lattice(pos=pos, vel=vel, dt=np.float32(dt), G=np.float32(G), bias=np.float32(bias), steps=steps, p_exp=p_exp, v_exp=v_exp,
-                   site=site, counts=counts, unit=unit, dv_pair=vunit, margin_bits=float(np.log2(F32_EXACT / max(biggest, 1))), kind=kind, scale=s)
+                   site=site, counts=counts, K=K, K2=K2 if steps == 2 else None,
+                   permute=tuple(int(x) for x in perm) if permute is not None else None, p_mid=p_mid, v_mid=v_mid, unit=unit,
+                   dv_pair=vunit, margin_bits=float(np.log2(F32_EXACT / max(biggest, 1))), kind=kind, scale=s)
 
 
 def wrong_bodies(lat: Lattice, p, v, first: int = 0, count: int = None) -> np.ndarray:

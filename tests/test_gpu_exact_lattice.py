@@ -198,7 +198,8 @@ def test_step_in_two_phases_bit_exact(nb, monkeypatch, waves, n, first, count, j
         assert_exact(lat, nxt[first:first + count, :3].cpu().numpy(), v[:, :3].cpu().numpy(), f"phases {kind}", first, count)
 
 
-# -- 5. the pairs form across ranks (nb_launch_ring_*), two steps: the fused finish's second step included -------------------------
+# -- 5. the pairs form across ranks (nb_launch_ring_*), two steps: the fused finish's second step included (a stale hand-off between
+#    the steps shows on the permuted lattices only) ------------------------------------------------------------------------------
 RING_SHAPES = [(2048, 2, 4, 0, 0), (1536, 3, 4, 0, 0), (4096, 4, 4, 1, 4), (4096, 8, 4, 0, 8), (3072, 3, 2, 2, 0), (2560, 2, 2, 3, 12),
                (8192, 2, 4, 0, 0), (12288, 3, 4, 5, 0)]
 RING_PHASE_SHAPES = [(2048, 2, 4, 0, 0, 0), (1536, 3, 4, 0, 0, 0), (4096, 8, 4, 0, 0, 0), (4096, 4, 4, 4, 8, 4), (3072, 3, 2, 4, 4, 8),
@@ -211,6 +212,10 @@ def _ring_lattices(n, world):
     yield lattice(n, seed=n + world + 1, kind="tetra_mixed", scale=2.0 ** 29, steps=2, runs=S)        # whole ranks of one site
     yield lattice(n, seed=n + world + 2, kind="planar", scale=2.0 ** -20, steps=2, runs=256)
     yield lattice(n, seed=n + world + 3, kind="line", scale=2.0 ** 31, steps=2, skew=(9, 1))
+    # permuted: the first step carries every site onto another, so the second step's terms differ from the first's and a record
+    # (received halves, sums, the fused finish's own-slot planes) left over from the first step shows
+    yield lattice(n, seed=n + world + 4, kind="tetra", scale=2.0 ** -20, steps=2, permute=(1, 2, 3, 0))
+    yield lattice(n, seed=n + world + 5, kind="tetra_mixed", scale=2.0 ** 29, steps=2, runs=S, permute=(2, 3, 0, 1))
 
 
 @pytest.mark.parametrize("n,world,np_,ga,wpb", RING_SHAPES)
@@ -249,6 +254,10 @@ def test_every_rank_of_configs_4_and_5_bit_exact(nb, n, world, phases):
     lat = lattice(n, seed=world, kind="tetra", G0=2.0 ** -3, dt=2.0 ** -1, steps=2)
     p, v = ring_steps_on_one_gpu(nb, lat.pos, lat.vel, world, params_of(nb, lat), 2, phases=phases)
     assert_exact(lat, p, v, f"n={n} ranks={world} phases={phases}")
+    if phases:   # the second step of the phases starts from the planes the first one's finish left: on the permuted lattice too
+        lat = lattice(n, seed=world + 1, kind="tetra", G0=2.0 ** -3, dt=2.0 ** -1, steps=2, permute=(1, 2, 3, 0))
+        p, v = ring_steps_on_one_gpu(nb, lat.pos, lat.vel, world, params_of(nb, lat), 2, phases=phases)
+        assert_exact(lat, p, v, f"permuted n={n} ranks={world} phases={phases}")
 
 
 @pytest.mark.parametrize("phases", [False, "fused"])
@@ -277,15 +286,21 @@ def test_ring_control_arm_one_corrupted_record(nb, monkeypatch, phases):
 # -- 6. native shards: eight ranks as threads of one process, FAST in the pairs form and overlapped, two steps ------------------------
 @pytest.mark.parametrize("overlap", [False, True], ids=["pairs", "pairs_overlapped"])
 def test_eight_native_shards_as_threads_bit_exact(nb, monkeypatch, overlap):
+    world, n = 8, 32768
+    monkeypatch.setenv("NB_RING", "1")
+    nb.load()
+    for lat in (lattice(n, seed=8, kind="tetra_mixed", steps=2, runs=1024),
+                lattice(n, seed=9, kind="tetra_mixed", steps=2, permute=(2, 3, 0, 1))):   # (permuted: bodies change layer between steps)
+        _eight_native_shards_two_steps(nb, lat, overlap)
+
+
+def _eight_native_shards_two_steps(nb, lat, overlap):
     import threading
 
     from test_gpu_native_shard import _hip_runtime
 
-    world, n = 8, 32768
-    monkeypatch.setenv("NB_RING", "1")
-    lat = lattice(n, seed=8, kind="tetra_mixed", steps=2, runs=1024)
+    world = 8
     params = params_of(nb, lat)
-    nb.load()
     hip = _hip_runtime()
     barrier = threading.Barrier(world, timeout=120)
     slots, halves, results, errors = {}, {}, {}, []

@@ -1354,7 +1354,9 @@ def _peers_worker(rank, world, port, n, k, mode, out_dir, what):
             before = (sc.positions().copy(), sc.velocities().copy())
             chosen = sc.choose_exchange(steps=2, warm=1)
             assert chosen in ("peers", "collective") and set(sc.exchange_times) == {"peers", "collective"} and sc.exchange == chosen
-            assert sc.exchange_report["all_gather"] == "peers" and sc.exchange_report["verified"]
+            # (the report describes the exchange kept; the collectives were verified first, on their own)
+            assert sc.exchange_report["all_gather"] == ("peers" if chosen == "peers" else "in_place") and sc.exchange_report["verified"]
+            assert sc.exchange_report["collective"] == {"all_gather": "in_place", "ring_exchange": None}, sc.exchange_report
             assert (sc.positions() == before[0]).all() and (sc.velocities() == before[1]).all()
             sc.step_n(k - 1)
         elif what in ("ring_lossy", "ring_stale"):   # rank 0's pulls lose a record / deliver only the first time (a stale cache: the SECOND
