@@ -144,6 +144,21 @@ int nb_cameras(nb_ctx *ctx, const float *up_xyz, const float *cp16, float *out_1
  * aspect_ratio, src/gfx.rs:381).  Host arithmetic, no device needed; NB_ERR_INVALID where cgmath's assertions would panic. */
 int nb_camera_constant(float vertical_fov_deg, float aspect_ratio, float near_plane, float far_plane, float *cp16);
 
+/* Every entity's eye view: what the reference's depth attachment holds after its eye pass -- one 1 x width
+ * layer per entity, the camera on the entity looking along its velocity (src/main.rs:939, 585-647, 962-998), every instance drawn
+ * in index order as the LineStrip 0-1-2-0 of its triangle (:130-138, 249), Depth32Float cleared to 1.0, compare Less (:256-260,
+ * 626) -- and which instance wrote each pixel.  Per column: the nearest body's id (ties: the lower index) and its depth, or
+ * NB_EYES_NONE and 1.0f.  The eye's own body is skipped unless NB_EYES_SEE_SELF (the `n != i` of the controllers).  Colour, MSAA
+ * and the texture are not reproduced.  Bit-exact: a fixed binary32 rule, clip = cp * view * (model * vertex). */
+#define NB_EYES_NONE 0xFFFFFFFFu
+#define NB_EYES_SEE_SELF 1u
+#define NB_EYES_MAX_WIDTH 4096u
+/* eyes of bodies [first, first+count) of the context's current state: cameras from (up, cp16) as nb_cameras (the reference's eye
+ * constant: nb_camera_constant(90.0f / width, width / 1.0f, 1, 10000)), the rule above; ids / depth: host, count*width each,
+ * either may be NULL (not both).  count = 0 is a no-op.  Device rows are allocated on the context at first use. */
+int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width, uint32_t flags,
+            uint32_t *ids, float *depth);
+
 /* Device -> host, after waiting for queued steps.  Any of the three may be NULL.
  * inst_16n, when given, receives the model matrices of the current state (src/main.rs:437-439),
  * produced on demand by a separate kernel: they never feed back into the dynamics. */
@@ -311,6 +326,12 @@ int nb_launch_instances(uint32_t count, const void *pos, const void *vel, void *
  * out receives 16 floats per entity. */
 int nb_launch_cameras(uint32_t count, const void *eyes, const void *dirs, const float *up_xyz, const float *cp16, void *out_16n,
                       void *stream);
+
+/* nb_eyes' rule, stateless, on caller-owned device memory: cams_16 = count cameras (eye e is body first+e), inst_16n = n_total model
+ * matrices (both 16-byte aligned); ids (uint32) / depth (float): count*width each, either may be NULL (not both).  The outputs
+ * must not alias each other or an input.  count = 0 is a no-op. */
+int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
+                   uint32_t flags, void *ids, void *depth, void *stream);
 
 /* One random-walk step (main.rs:381-402) in place for `count` bodies whose global indices start at `first`. */
 int nb_launch_random_step(uint32_t first, uint32_t count, void *pos, void *vel, uint64_t seed, uint64_t step, void *stream);

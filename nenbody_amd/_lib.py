@@ -30,6 +30,10 @@ NB_PHASE_RANGE = 0
 NB_PHASE_REST = 1
 # phases of the pairs form on shards (nb_launch_ring_fold_phase)
 NB_RING_OWN, NB_RING_REST, NB_RING_SUMS, NB_RING_OWN_READY = 1, 2, 3, 4
+# every entity's eye view (nb_eyes / nb_launch_eyes)
+NB_EYES_NONE = 0xFFFFFFFF
+NB_EYES_SEE_SELF = 1
+NB_EYES_MAX_WIDTH = 4096
 
 _STATUS_NAMES = {
     NB_ERR_INVALID: "NB_ERR_INVALID",
@@ -96,6 +100,8 @@ PROTOTYPES = {
     "nb_cameras": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_camera_constant": (c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p]),
     "nb_launch_cameras": (c_int, [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_eyes": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "nb_launch_eyes": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
     "nb_launch_random_step": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p]),
     "nb_update_instance_nbody": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbParams)]),
     "nb_update_instance_boids": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbBoidsParams)]),

@@ -20,6 +20,7 @@
 #include "../../include/nenbody.h"
 #include "../../include/nenbody_diag.h"
 #include "nb_kernels.h"
+#include "nb_eyes.h"
 
 #define NB_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -838,7 +839,10 @@ struct nb_ctx {
     float4 *vel_alt = nullptr;  // second velocity buffer: boids reads every old velocity, so velocities ping-pong too
     float *stage = nullptr;   // 3n floats: stride-3 staging for upload/download
     float4 *inst = nullptr;   // 4n float4, allocated on first use
-    float4 *cams = nullptr;   // 4n float4, allocated on first use (nb_cameras)
+    float4 *cams = nullptr;   // 4n float4, allocated on first use (nb_cameras, nb_eyes)
+    uint32_t *eye_ids = nullptr;  // nb_eyes' rows, allocated on first use and grown on demand: eye_ids_cap / eye_depth_cap entries
+    float *eye_depth = nullptr;
+    size_t eye_ids_cap = 0, eye_depth_cap = 0;
     float *xfer = nullptr;    // 22n floats [matrices 16n | positions 3n | velocities 3n]: one-copy round trip of the drop-in calls
     float *hxfer = nullptr;   // its pinned host twin
     float *hxfer_dev = nullptr;  // the device's address of hxfer (mapped host memory: kernels of the small-set drop-in read and write it directly)
@@ -919,6 +923,8 @@ NB_EXPORT void nb_destroy(nb_ctx *ctx)
     if (ctx->stage) (void)hipFree(ctx->stage);
     if (ctx->inst) (void)hipFree(ctx->inst);
     if (ctx->cams) (void)hipFree(ctx->cams);
+    if (ctx->eye_ids) (void)hipFree(ctx->eye_ids);
+    if (ctx->eye_depth) (void)hipFree(ctx->eye_depth);
     if (ctx->xfer) (void)hipFree(ctx->xfer);
     if (ctx->hxfer) (void)hipHostFree(ctx->hxfer);
     if (ctx->done_counter) (void)hipFree(ctx->done_counter);
@@ -1285,6 +1291,92 @@ NB_EXPORT int nb_cameras(nb_ctx *ctx, const float *up_xyz, const float *cp16, fl
     if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
     NB_HIP(ctx, nbk::launch_cameras(ctx->n, ctx->pos[ctx->cur], ctx->vel, up_xyz, cp16, ctx->cams, ctx->stream));
     NB_HIP(ctx, hipMemcpyAsync(out_16n, ctx->cams, (size_t)ctx->n * 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+// [a, a + an) and [b, b + bn) share a byte (a NULL or empty range shares none)
+static bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn)
+{
+    if (!a || !b || !an || !bn) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bn && y < x + an;
+}
+
+// The checks nb_eyes and nb_launch_eyes share, before anything touches the device: the width, the range, the flags, the outputs
+// (one at least; they must not overlap each other or the inputs `in0` / `in1` of in0_bytes / in1_bytes).
+static int eyes_check(const char *fn, uint32_t n, uint32_t first, uint32_t count, uint32_t width, uint32_t flags, const void *ids,
+                      const void *depth, const void *in0, size_t in0_bytes, const void *in1, size_t in1_bytes, std::string *err)
+{
+    if (width == 0 || width > NB_EYES_MAX_WIDTH) {
+        *err = std::string(fn) + ": width must be 1 .. NB_EYES_MAX_WIDTH (4096)";
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)first + count > n) {
+        *err = std::string(fn) + ": eyes [first, first + count) exceed the set";
+        return NB_ERR_INVALID;
+    }
+    if (flags & ~NB_EYES_SEE_SELF) {
+        *err = std::string(fn) + ": unknown flag bits";
+        return NB_ERR_INVALID;
+    }
+    if (!ids && !depth) {
+        *err = std::string(fn) + ": ids and depth are both NULL";
+        return NB_ERR_INVALID;
+    }
+    const size_t row_bytes = (size_t)count * width * 4u;
+    if ((ids && ids == depth) || ranges_overlap(ids, row_bytes, depth, row_bytes) || ranges_overlap(ids, row_bytes, in0, in0_bytes) ||
+        ranges_overlap(ids, row_bytes, in1, in1_bytes) || ranges_overlap(depth, row_bytes, in0, in0_bytes) ||
+        ranges_overlap(depth, row_bytes, in1, in1_bytes)) {
+        *err = std::string(fn) + ": the outputs must not alias each other or an input";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
+                      uint32_t flags, uint32_t *ids, float *depth)
+{
+    if (!ctx) {
+        g_tls_error = "nb_eyes: ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (!up_xyz || !cp16) {
+        ctx->err = "nb_eyes: null argument";
+        return NB_ERR_INVALID;
+    }
+    int rc = eyes_check("nb_eyes", ctx->n, first, count, width, flags, ids, depth, up_xyz, 3 * sizeof(float), cp16, 16 * sizeof(float),
+                        &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (!ctx->uploaded) {
+        ctx->err = "nb_eyes: no state uploaded";
+        return NB_ERR_STATE;
+    }
+    if (count == 0) return NB_OK;
+    const size_t cells = (size_t)count * width;
+    if (ids && cells > ctx->eye_ids_cap) {
+        if (ctx->eye_ids) (void)hipFree(ctx->eye_ids);
+        ctx->eye_ids = nullptr;
+        ctx->eye_ids_cap = 0;
+        NB_HIP(ctx, hipMalloc((void **)&ctx->eye_ids, cells * sizeof(uint32_t)));
+        ctx->eye_ids_cap = cells;
+    }
+    if (depth && cells > ctx->eye_depth_cap) {
+        if (ctx->eye_depth) (void)hipFree(ctx->eye_depth);
+        ctx->eye_depth = nullptr;
+        ctx->eye_depth_cap = 0;
+        NB_HIP(ctx, hipMalloc((void **)&ctx->eye_depth, cells * sizeof(float)));
+        ctx->eye_depth_cap = cells;
+    }
+    // the eye cameras of [first, first + count) as nb_cameras forms them, the model matrices of the whole set as nb_download does
+    if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
+    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags,
+                                 ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr, ctx->stream));
+    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
 }
@@ -1809,6 +1901,34 @@ NB_EXPORT int nb_launch_cameras(uint32_t count, const void *eyes, const void *di
     }
     NB_LAUNCH_TLS(nbk::launch_cameras(count, (const float4 *)eyes, (const float4 *)dirs, up_xyz, cp16, (float4 *)out_16n,
                                       (hipStream_t)stream));
+}
+
+NB_EXPORT int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
+                             uint32_t flags, void *ids, void *depth, void *stream)
+{
+    if (!cams_16 || !inst_16n) {
+        g_tls_error = "nb_launch_eyes: null argument";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16n) & 15u) {
+        g_tls_error = "nb_launch_eyes: cams_16 and inst_16n must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    int rc = eyes_check("nb_launch_eyes", n_total, first, count, width, flags, ids, depth, cams_16, (size_t)count * 16 * sizeof(float),
+                        inst_16n, (size_t)n_total * 16 * sizeof(float), &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = check_device(&g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = select_device_of(inst_16n, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    hipError_t e = nbk::launch_eyes(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags, (uint32_t *)ids,
+                                    (float *)depth, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
+        return NB_ERR_HIP;
+    }
+    return NB_OK;
 }
 
 NB_EXPORT int nb_launch_random_step(uint32_t first, uint32_t count, void *pos, void *vel, uint64_t seed, uint64_t step, void *stream)

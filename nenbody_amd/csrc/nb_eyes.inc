@@ -1,0 +1,205 @@
+// nb_eyes.inc -- every entity's eye view (DESIGN.md section 10): what the reference's depth attachment holds after its eye pass
+// (src/main.rs:585-647, 962-998: one 1 x W layer per entity, the camera on the entity looking along its velocity, every instance drawn
+// as the LineStrip 0-1-2-0 of its triangle, src/main.rs:130-138, 249, with depth test Less against a clear of 1.0, :256-260, 626),
+// and which instance wrote each pixel.
+// Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit: NOT in the two units whose device code kernel_code_sha()
+// hashes (nenbody_amd/_lib.py), so the stamp of profiles/hbm_traffic.json stays that of the benchmarked kernels.  Launcher: nb_eyes.h.
+//
+// The rule, one binary32 operation per step in the order written (-ffp-contract=off, IEEE '/'); tests/eyes_restatement.py states it
+// again in numpy and the GPU tests compare every bit:
+//   clip vertex  C (M a) for a = (-1,-1,0,1), (1,0,0,1), (-1,1,0,1); each row of each product ((m0 x + m1 y) + m2 z) + m3 w
+//   edges        (a0,a1), (a1,a2), (a2,a0), clipped (Liang-Barsky) to z >= 0, w - z >= 0, w + y >= 0, w - y >= 0; no x planes
+//   projection   xs = (x / w) * (W/2) + W/2, d = z / w; column c, centre xc = c + 0.5, covered iff min(xs) <= xc < max(xs)
+//   depth        t = (xc - xs0) / (xs1 - xs0), d = d0 + t (d1 - d0); a candidate iff d < 1, then !(d > 0) -> +0
+//   resolve      the minimum over bodies and edges of bits(d) << 32 | j: the nearest, ties to the lower index
+//
+// Shape: one workgroup of 256 lanes per eye (a grid-stride loop over the eyes); the eye's W keys in LDS (W <= 4096: 32 KB), resolved
+// with ds_min_u64 -- the minimum does not depend on the order the candidates arrive in, so the result is deterministic.  A lane takes
+// one body per pass: it clips the three edges, walks the first kEyeOwnCols columns of each span itself and hands the rest of a wide
+// span to its whole wave (a near body covers hundreds of columns: one lane per body would leave the wave waiting on its widest span).
+// Culls, none of which can change a bit: an edge whose ends are both outside one boundary is dropped before any divide (a body behind
+// the eye costs its clip z rows only); a column is skipped before its divide when a lower bound of every key the segment can write
+// there (klow, eye_edge) is not below the key in place; and the atomic only goes out when the key is below the key read just before.
+
+static constexpr int kEyeBlock = 256;
+static constexpr uint32_t kEyeOwnCols = 8;    // columns of a span its own lane walks; the rest goes to the whole wave
+static constexpr uint32_t kEyeMaxGrid = 1u << 20;
+
+struct EyeSeg {
+    float xs0, xs1, d0, d1;  // projected ends
+    float dx, dd;            // xs1 - xs0, d1 - d0
+    float xa, xb;            // min / max of xs0, xs1
+    uint32_t klow;           // bits of a lower bound of every depth this segment writes (the key's upper half)
+    uint32_t lo, hi;         // a superset of the covered columns, [lo, hi)
+};
+
+// One edge P0 -> P1 of clip-space vertices (x, y, z, w): clipped, projected, its column range.  false: dropped, or covers no column.
+__device__ __forceinline__ bool eye_edge(const float *P0, const float *P1, float h, uint32_t width, EyeSeg &s)
+{
+    float t_in = 0.0f, t_out = 1.0f;
+    const float b0v[4] = {P0[2], P0[3] - P0[2], P0[3] + P0[1], P0[3] - P0[1]};   // near, far, y = -w, y = +w
+    const float b1v[4] = {P1[2], P1[3] - P1[2], P1[3] + P1[1], P1[3] - P1[1]};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float b0 = b0v[k], b1 = b1v[k];
+        if (b0 < 0.0f && b1 < 0.0f) return false;
+        if (b0 < 0.0f && b1 >= 0.0f) {
+            const float r = b0 / (b0 - b1);
+            if (r > t_in) t_in = r;        // max(t_in, r); a NaN r changes nothing
+        } else if (b1 < 0.0f && b0 >= 0.0f) {
+            const float r = b0 / (b0 - b1);
+            if (r < t_out) t_out = r;      // min(t_out, r)
+        }
+    }
+    if (t_in > t_out) return false;
+    float Q0[4], Q1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float D = P1[r] - P0[r];
+        const float a = t_in * D, b = t_out * D;
+        Q0[r] = (t_in > 0.0f) ? P0[r] + a : P0[r];
+        Q1[r] = (t_out < 1.0f) ? P0[r] + b : P1[r];
+    }
+    if (!(Q0[3] > 0.0f && Q1[3] > 0.0f)) return false;
+    const float u0 = Q0[0] / Q0[3], u1 = Q1[0] / Q1[3];
+    const float p0 = u0 * h, p1 = u1 * h;
+    s.xs0 = p0 + h;
+    s.xs1 = p1 + h;
+    s.xa = (s.xs0 <= s.xs1) ? s.xs0 : s.xs1;
+    s.xb = (s.xs0 <= s.xs1) ? s.xs1 : s.xs0;
+    if (!(s.xa <= s.xb)) return false;                                          // a NaN end covers nothing
+    // c covered => xa <= c + 0.5 < xb => floor(xa) - 1 < c < ceil(xb): a superset, clamped in float first (the ends may be infinite)
+    const float lo = floorf(fmaxf(s.xa, -4.0f)) - 1.0f;
+    const float hi = ceilf(fminf(s.xb, (float)width + 4.0f)) + 1.0f;
+    s.lo = (uint32_t)fminf(fmaxf(lo, 0.0f), (float)width);
+    s.hi = (uint32_t)fminf(fmaxf(hi, 0.0f), (float)width);
+    if (s.lo >= s.hi) return false;
+    s.d0 = Q0[2] / Q0[3];
+    s.d1 = Q1[2] / Q1[3];
+    s.dx = s.xs1 - s.xs0;
+    s.dd = s.d1 - s.d0;
+    // A lower bound of d = d0 + t * dd over the covered columns.  There 0 <= t <= 1 or t is NaN (xc lies between the ends and
+    // rounding is monotone), so with dd >= 0 the product is >= 0 and d >= d0, and with dd < 0 the product is >= dd and
+    // d >= fl(d0 + dd).  A NaN bound becomes 0 (no cull); a NaN d is never a candidate anyway.
+    const float dlow = (s.d1 >= s.d0) ? s.d0 : s.d0 + s.dd;
+    s.klow = __float_as_uint(dlow > 0.0f ? dlow : 0.0f);
+    return true;
+}
+
+__device__ __forceinline__ uint64_t eye_key_load(uint64_t *k) { return __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// column c of segment s of body j
+__device__ __forceinline__ void eye_cover(uint64_t *keys, uint32_t c, const EyeSeg &s, uint32_t j)
+{
+    const float xc = (float)c + 0.5f;                                           // exact
+    if (!(s.xa <= xc && xc < s.xb)) return;
+    if ((((uint64_t)s.klow << 32) | j) >= eye_key_load(keys + c)) return;       // nothing this segment writes here can win
+    const float t = (xc - s.xs0) / s.dx;
+    const float q = t * s.dd;
+    float d = s.d0 + q;
+    if (!(d < 1.0f)) return;                                                    // Less against the clear value; NaN never passes
+    if (!(d > 0.0f)) d = 0.0f;
+    const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | j;
+    if (key < eye_key_load(keys + c)) __hip_atomic_fetch_min(keys + c, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ float eye_bcast(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
+__device__ __forceinline__ uint32_t eye_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
+
+__global__ __launch_bounds__(kEyeBlock) void eyes_kernel(uint32_t n_total, uint32_t first, uint32_t count, const float4 *__restrict__ cams,
+                                                        const float4 *__restrict__ inst, uint32_t width, uint32_t see_self,
+                                                        uint32_t *__restrict__ ids, float *__restrict__ depth)
+{
+    extern __shared__ uint64_t eye_keys[];   // width entries
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const float h = (float)width * 0.5f;     // exact
+    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
+    for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
+        for (uint32_t c = tid; c < width; c += kEyeBlock) eye_keys[c] = ~0ull;
+        __syncthreads();
+        float C[16];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 v = cams[(size_t)e * 4 + k];
+            C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w;
+        }
+        const uint32_t self = first + e;
+        for (uint32_t j0 = 0; j0 < n_total; j0 += kEyeBlock) {   // every lane of the workgroup runs every pass (the wave loops below)
+            const uint32_t j = j0 + tid;
+            float P[3][4] = {};
+            bool live = j < n_total && (see_self || j != self);
+            if (live) {
+                float M[16];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float4 v = inst[(size_t)j * 4 + k];
+                    M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
+                }
+                float w[3][4];
+#pragma unroll
+                for (int v = 0; v < 3; ++v)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
+                        w[v][r] = ((t0 + t1) + t2) + t3;
+                    }
+#pragma unroll
+                for (int v = 0; v < 3; ++v) {   // the near plane's row first: a body wholly behind the eye stops here
+                    const float t0 = C[2] * w[v][0], t1 = C[6] * w[v][1], t2 = C[10] * w[v][2], t3 = C[14] * w[v][3];
+                    P[v][2] = ((t0 + t1) + t2) + t3;
+                }
+                live = !(P[0][2] < 0.0f && P[1][2] < 0.0f && P[2][2] < 0.0f);
+                if (live) {
+#pragma unroll
+                    for (int v = 0; v < 3; ++v)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if (r == 2) continue;
+                            const float t0 = C[r] * w[v][0], t1 = C[4 + r] * w[v][1], t2 = C[8 + r] * w[v][2], t3 = C[12 + r] * w[v][3];
+                            P[v][r] = ((t0 + t1) + t2) + t3;
+                        }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                EyeSeg s{};
+                const bool has = live && eye_edge(P[k], P[k == 2 ? 0 : k + 1], h, width, s);
+                uint32_t rest = 0;   // first column left to the wave (rest < s.hi: some are)
+                if (has) {
+                    const uint32_t own = s.hi - s.lo < kEyeOwnCols ? s.hi : s.lo + kEyeOwnCols;
+                    for (uint32_t c = s.lo; c < own; ++c) eye_cover(eye_keys, c, s, j);
+                    rest = own;
+                }
+                uint64_t wide = __ballot(has && rest < s.hi);
+                while (wide) {
+                    const int src = __ffsll((unsigned long long)wide) - 1;
+                    wide &= wide - 1;
+                    EyeSeg b;
+                    b.xs0 = eye_bcast(s.xs0, src), b.xs1 = eye_bcast(s.xs1, src), b.d0 = eye_bcast(s.d0, src), b.d1 = eye_bcast(s.d1, src);
+                    b.dx = eye_bcast(s.dx, src), b.dd = eye_bcast(s.dd, src), b.xa = eye_bcast(s.xa, src), b.xb = eye_bcast(s.xb, src);
+                    b.klow = eye_bcast(s.klow, src), b.lo = eye_bcast(rest, src), b.hi = eye_bcast(s.hi, src);
+                    const uint32_t bj = eye_bcast(j, src);
+                    for (uint32_t c = b.lo + lane; c < b.hi; c += 64u) eye_cover(eye_keys, c, b, bj);
+                }
+            }
+        }
+        __syncthreads();
+        for (uint32_t c = tid; c < width; c += kEyeBlock) {   // coalesced rows of ids and depths
+            const uint64_t key = eye_keys[c];
+            const bool none = key == ~0ull;
+            const size_t o = (size_t)e * width + c;
+            if (ids) ids[o] = none ? 0xFFFFFFFFu : (uint32_t)key;
+            if (depth) depth[o] = none ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+        }
+        __syncthreads();   // the next eye re-initialises the keys
+    }
+}
+
+hipError_t launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const float *cams, const float *inst, uint32_t width,
+                       uint32_t flags, uint32_t *ids, float *depth, hipStream_t s)
+{
+    const uint32_t grid = count < kEyeMaxGrid ? count : kEyeMaxGrid;
+    hipLaunchKernelGGL(eyes_kernel, dim3(grid), dim3(kEyeBlock), (size_t)width * sizeof(uint64_t), s, n_total, first, count,
+                       (const float4 *)cams, (const float4 *)inst, width, flags & 1u, ids, depth);
+    return hipGetLastError();
+}

@@ -38,6 +38,7 @@
 //   nb_nbody_fast.inc    FAST kernels + fixed-order combine               (this unit)
 //   nb_aux.inc           model matrices, cameras, random walk, self-test  (this unit)
 //   nb_boids.inc         boids controller, one-lane and producer/consumer (SLP-off unit)
+//   nb_eyes.inc          every entity's eye view: depth + entity id per column (SLP-off unit; its own launcher, nb_eyes.h)
 //   nb_launch.inc        host-side launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +63,7 @@ static constexpr int kWaves = kBlock / 64;
 #include "nb_nbody_ring.inc"  // the same on a shard of a multi-GPU job: the blocks on a ring, each against the half that follows it
 #elif defined(NBK_NOSLP_TU)
 #include "nb_boids.inc"
+#include "nb_eyes.inc"        // every entity's eye view: outside the two units kernel_code_sha() stamps the evidence with
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

@@ -19,8 +19,8 @@ import numpy as np
 from . import _lib
 from ._lib import NB_MODE_FAST, NB_MODE_STRICT, NbBoidsParams, NbError, NbParams, check  # noqa: F401  (re-exported)
 
-__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "NB_MODE_STRICT", "NB_MODE_FAST",
-           "NbParams", "NbBoidsParams", "NbError"]
+__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "NB_MODE_STRICT",
+           "NB_MODE_FAST", "NbParams", "NbBoidsParams", "NbError"]
 
 
 def _as_f32(a, shape_tail, name):
@@ -37,6 +37,14 @@ def camera_constant(vertical_fov_deg: float, aspect_ratio: float, near: float = 
     cp = np.zeros((4, 4), np.float32)
     check(_lib.load().nb_camera_constant(vertical_fov_deg, aspect_ratio, near, far, cp.ctypes.data))
     return cp
+
+
+def eye_constant(width: int = 1024, horizontal_fov_deg: float = 90.0) -> np.ndarray:
+    """The constant of the reference's eye cameras for rows of ``width`` pixels, as it forms it: CameraArray::new takes the
+    horizontal field of view and an extent of width x 1 (src/main.rs:693-697) and passes perspective() the angle DIVIDED by the
+    aspect ratio (src/gfx.rs:379-383), so a row spans 2 atan(width tan(fov / (2 width))) -- 76.3 degrees at 90 and 1024, not 90."""
+    w = np.float32(width)
+    return camera_constant(float(np.float32(horizontal_fov_deg) / w), float(w / np.float32(1.0)), 1.0, 10000.0)
 
 
 def init_state(n: int, seed: int = 1234):
@@ -124,6 +132,27 @@ class Scene:
         out = np.zeros((self.n, 4, 4), np.float32)
         check(self._lib.nb_cameras(self._ctx, upv.ctypes.data, cpm.ctypes.data, out.ctypes.data), self._ctx)
         return out
+
+    def eyes(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, first: int = 0, count: Optional[int] = None,
+             see_self: bool = False):
+        """Every entity's eye view (nb_eyes) for bodies [first, first + count) of the current state: what the
+        reference's depth attachment holds after its eye pass, one row of ``width`` pixels per entity, and which entity wrote each
+        pixel.  ``cp`` is the eyes' camera constant, (4, 4) with [k] = column k; None: the reference's, :func:`eye_constant`.
+        Returns (ids uint32 (count, width) -- NB_EYES_NONE where nothing covers the column --, depth float32 (count, width))."""
+        if count is None:
+            count = self.n - first
+        if first < 0 or count < 0:
+            raise ValueError("first and count must be >= 0")
+        if cp is None:   # (an invalid width is the library's to refuse)
+            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MAX_WIDTH else np.zeros((4, 4), np.float32)
+        upv = np.ascontiguousarray(up, np.float32).reshape(3)
+        cpm = np.ascontiguousarray(cp, np.float32).reshape(16)
+        ids = np.empty((count, max(int(width), 0)), np.uint32)
+        depth = np.empty((count, max(int(width), 0)), np.float32)
+        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
+        check(self._lib.nb_eyes(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, ids.ctypes.data,
+                                depth.ctypes.data), self._ctx)
+        return ids, depth
 
     def device_state(self, with_instances: bool = True):
         """Device pointers (ints) of the current position records, velocity records and model matrices: the zero-copy
