@@ -148,8 +148,9 @@ int nb_camera_constant(float vertical_fov_deg, float aspect_ratio, float near_pl
  * layer per entity, the camera on the entity looking along its velocity (src/main.rs:939, 585-647, 962-998), every instance drawn
  * in index order as the LineStrip 0-1-2-0 of its triangle (:130-138, 249), Depth32Float cleared to 1.0, compare Less (:256-260,
  * 626) -- and which instance wrote each pixel.  Per column: the nearest body's id (ties: the lower index) and its depth, or
- * NB_EYES_NONE and 1.0f.  The eye's own body is skipped unless NB_EYES_SEE_SELF (the `n != i` of the controllers).  Colour, MSAA
- * and the texture are not reproduced.  Bit-exact: a fixed binary32 rule, clip = cp * view * (model * vertex). */
+ * NB_EYES_NONE and 1.0f.  The eye's own body is skipped unless NB_EYES_SEE_SELF (the `n != i` of the controllers).  The colour
+ * attachment is nb_eyes_colour's, below.  MSAA is not reproduced: one sample at the column centre.  Bit-exact: a fixed binary32
+ * rule, clip = cp * view * (model * vertex). */
 #define NB_EYES_NONE 0xFFFFFFFFu
 #define NB_EYES_SEE_SELF 1u
 #define NB_EYES_MAX_WIDTH 4096u
@@ -158,6 +159,36 @@ int nb_camera_constant(float vertical_fov_deg, float aspect_ratio, float near_pl
  * either may be NULL (not both).  count = 0 is a no-op.  Device rows are allocated on the context at first use. */
 int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width, uint32_t flags,
             uint32_t *ids, float *depth);
+
+/* The colour row of the same pass: what `resolved_eyes` and the viewport's imgui texture hold
+ * (src/main.rs:585-647, 962-998), one 1 x width Bgra8UnormSrgb layer per entity.  The fragment of a column is that of the FIRST
+ * edge (draw order 0-1, 1-2, 2-0; Less keeps the first of equal depths) of the winning body that covers the column with the winning
+ * depth; its texture coordinate is interpolated perspective-correctly along the clipped edge from the vertices' (0,0), (0,1), (1,1)
+ * (shaders/scene.vert:17, src/main.rs:131-135), one texel of the skin is fetched, the vignette c = tex * (1 - |uv - 0.5|^2) applied
+ * (shaders/scene.frag:15-16), alpha = 1; an empty column holds the clear colour (0.1, 0.2, 0.3, 1) (:613-618).
+ *   rgba    4 floats per column, linear: what the shader writes
+ *   bgra8   one uint32 per column whose bytes in memory are B, G, R, A: the texel the sRGB target stores (nb_srgb_encode below)
+ * NOT reproduced: the MSAA resolve (one sample at the column centre, as for the depth) and the sampler's linear minification
+ * (src/main.rs:362) -- which fragments count as minified depends on screen-space derivatives that a line primitive in a one-pixel-
+ * high target does not define portably; the texel is ClampToEdge with ONE nearest sample, ix = min(tw - 1, floor(u * tw)),
+ * iy = min(th - 1, floor(v * th)). */
+#define NB_EYES_MAX_SKIN 2048u
+/* The skin the context's colour rows sample: tw x th texels of linear RGBA floats, row 0 first as the image file stores it
+ * (1 <= tw, th <= NB_EYES_MAX_SKIN), copied to the device and kept by the context.  NULL, or never called: a 1 x 1 white skin,
+ * which gives the pure vignette (tw, th are ignored).  An 8-bit sRGB image (Rgba8UnormSrgb, src/main.rs:338) becomes linear
+ * through nb_srgb_decode_table. */
+int nb_eyes_skin(nb_ctx *ctx, const float *rgba_linear, uint32_t tw, uint32_t th);
+/* nb_eyes with the colour row: ids / depth as nb_eyes gives them, bit for bit; rgba: host, count*width*4 floats; bgra8: host,
+ * count*width words.  Any of the four may be NULL, but not both rgba and bgra8 (that call is nb_eyes).  count = 0 is a no-op. */
+int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width, uint32_t flags,
+                   uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8);
+/* The two sRGB tables behind bgra8 and an 8-bit skin; host arithmetic on committed constants, no device needed.
+ * decode = the sRGB EOTF: e / 12.92 for e <= 0.04045, else ((e + 0.055) / 1.055)^2.4.
+ *   nb_srgb_decode_table   out256[b] = binary32(decode(b / 255))
+ *   nb_srgb_encode         out[i] = the number of thresholds T[1..255] that are <= linear[i], T[b] = binary32(decode((b - 0.5) / 255)):
+ *                          the exact nearest byte; a NaN gives 0, anything >= T[255] gives 255 */
+int nb_srgb_decode_table(float *out256);
+int nb_srgb_encode(const float *linear, size_t n, uint8_t *out);
 
 /* Device -> host, after waiting for queued steps.  Any of the three may be NULL.
  * inst_16n, when given, receives the model matrices of the current state (src/main.rs:437-439),
@@ -332,6 +363,14 @@ int nb_launch_cameras(uint32_t count, const void *eyes, const void *dirs, const 
  * must not alias each other or an input.  count = 0 is a no-op. */
 int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
                    uint32_t flags, void *ids, void *depth, void *stream);
+
+/* nb_eyes_colour's rule, stateless, on caller-owned device memory: as nb_launch_eyes, plus skin = tw x th linear RGBA texels (row 0
+ * first, 16-byte aligned, 1 <= tw, th <= NB_EYES_MAX_SKIN), or NULL for the 1 x 1 white skin (tw, th ignored); rgba: count*width*4
+ * floats, 16-byte aligned; bgra8: count*width words.  Any of the four outputs may be NULL, but not both rgba and bgra8.  No two
+ * outputs may overlap, and none may overlap cams_16, inst_16n or skin.  count = 0 is a no-op. */
+int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
+                          uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids, void *depth, void *rgba, void *bgra8,
+                          void *stream);
 
 /* One random-walk step (main.rs:381-402) in place for `count` bodies whose global indices start at `first`. */
 int nb_launch_random_step(uint32_t first, uint32_t count, void *pos, void *vel, uint64_t seed, uint64_t step, void *stream);

@@ -91,6 +91,67 @@ public:
     void refresh() { check(nb_download(ctx_, positions[0].data(), velocities[0].data(), instances[0][0].data()), ctx_); }
     uint64_t steps_done() const { return nb_steps_done(ctx_); }
 
+    // Every entity's eye view (nb_eyes: the reference's eye pass, src/main.rs:585-647, 962-998) for bodies [first, first + count) of
+    // the current state, rows of `width` pixels: per column the nearest body's index (NB_EYES_NONE where none) and the depth
+    // attachment's value.  cp16: the eyes' camera constant, column-major (nb_camera_constant(90.0f / width, width, 1, 10000) is
+    // the reference's); up: its `normal`.
+    struct Eyes {
+        uint32_t width = 0;
+        std::vector<uint32_t> ids;
+        std::vector<float> depth;
+    };
+    Eyes eyes(const Mat4 &cp, uint32_t width = 1024, uint32_t first = 0, uint32_t count = UINT32_MAX, bool see_self = false,
+              const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (count == UINT32_MAX) count = first <= positions.size() ? (uint32_t)positions.size() - first : 0;
+        Eyes e;
+        e.width = width;
+        const size_t cells = (size_t)count * width;
+        e.ids.resize(cells ? cells : 1);      // (a pointer the library can check even where count = 0)
+        e.depth.resize(cells ? cells : 1);
+        check(nb_eyes(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids.data(), e.depth.data()),
+              ctx_);
+        e.ids.resize(cells);
+        e.depth.resize(cells);
+        return e;
+    }
+    // The skin the colour rows sample: tw x th linear RGBA texels, row 0 first; an empty vector: the 1 x 1 white skin.
+    void set_skin(const std::vector<std::array<float, 4>> &rgba_linear, uint32_t tw, uint32_t th)
+    {
+        if (!rgba_linear.empty() && rgba_linear.size() != (size_t)tw * th) throw std::invalid_argument("a skin needs tw * th texels");
+        check(nb_eyes_skin(ctx_, rgba_linear.empty() ? nullptr : rgba_linear[0].data(), tw, th), ctx_);
+    }
+    // The same pass with its colour row (nb_eyes_colour): rgba = what the fragment shader writes (texel under the vignette, or the
+    // clear colour), bgra8 = the texel of the reference's Bgra8UnormSrgb target, bytes B, G, R, A -- what a host uploads to its
+    // imgui texture instead of running the eye and viewport passes.
+    struct EyesColour {
+        uint32_t width = 0;
+        std::vector<uint32_t> ids;
+        std::vector<float> depth;
+        std::vector<std::array<float, 4>> rgba;
+        std::vector<uint32_t> bgra8;
+    };
+    EyesColour eyes_colour(const Mat4 &cp, uint32_t width = 1024, uint32_t first = 0, uint32_t count = UINT32_MAX, bool see_self = false,
+                           const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (count == UINT32_MAX) count = first <= positions.size() ? (uint32_t)positions.size() - first : 0;
+        EyesColour e;
+        e.width = width;
+        const size_t cells = (size_t)count * width;
+        e.ids.resize(cells ? cells : 1);
+        e.depth.resize(cells ? cells : 1);
+        e.rgba.resize(cells ? cells : 1);
+        e.bgra8.resize(cells ? cells : 1);
+        check(nb_eyes_colour(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids.data(),
+                             e.depth.data(), e.rgba[0].data(), e.bgra8.data()),
+              ctx_);
+        e.ids.resize(cells);
+        e.depth.resize(cells);
+        e.rgba.resize(cells);
+        e.bgra8.resize(cells);
+        return e;
+    }
+
 private:
     void create(const nb_params &params)
     {

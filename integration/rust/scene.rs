@@ -76,6 +76,57 @@ extern "C" {
         velocities: *mut f32, n_velocities: usize, seed: u64, step: u64,
     ) -> c_int;
     fn nb_update_random_seed(seed: u64);
+    // every entity's eye view (the reference's eye pass, src/main.rs:585-647, 962-998) and its colour row
+    fn nb_camera_constant(vertical_fov_deg: f32, aspect_ratio: f32, near_plane: f32, far_plane: f32, cp16: *mut f32) -> c_int;
+    fn nb_eyes(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids: *mut u32, depth: *mut f32) -> c_int;
+    fn nb_eyes_skin(ctx: *mut NbCtx, rgba_linear: *const f32, tw: u32, th: u32) -> c_int; // null = the 1 x 1 white skin
+    fn nb_eyes_colour(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids: *mut u32, depth: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
+    fn nb_srgb_decode_table(out256: *mut f32) -> c_int;
+    fn nb_srgb_encode(linear: *const f32, n: usize, out: *mut u8) -> c_int;
+}
+
+pub const NB_EYES_NONE: u32 = 0xFFFF_FFFF;
+pub const NB_EYES_SEE_SELF: u32 = 1;
+
+/// The eye cameras' constant as the reference forms it for rows of `width` pixels (src/main.rs:693-697, src/gfx.rs:379-383).
+pub fn eye_constant(width: u32) -> Result<[[f32; 4]; 4], SceneError> {
+    check_abi();
+    let mut cp = [[0.0f32; 4]; 4];
+    check(unsafe { nb_camera_constant(90.0 / width as f32, width as f32 / 1.0, 1.0, 10000.0, cp.as_mut_ptr() as *mut f32) }, std::ptr::null())?;
+    Ok(cp)
+}
+
+/// An 8-bit sRGB image (`Rgba8UnormSrgb`, src/main.rs:338) as the linear texels `Scene::set_skin` takes: colour through the
+/// library's decode table, alpha / 255.
+pub fn skin_from_srgb8(rgba8: &[[u8; 4]]) -> Result<Vec<[f32; 4]>, SceneError> {
+    check_abi();
+    let mut d = [0.0f32; 256];
+    check(unsafe { nb_srgb_decode_table(d.as_mut_ptr()) }, std::ptr::null())?;
+    Ok(rgba8.iter().map(|p| [d[p[0] as usize], d[p[1] as usize], d[p[2] as usize], p[3] as f32 / 255.0]).collect())
+}
+
+/// Linear values as the bytes an sRGB target stores (the exact nearest byte; a NaN gives 0).
+pub fn srgb_encode(linear: &[f32]) -> Result<Vec<u8>, SceneError> {
+    check_abi();
+    let mut out = vec![0u8; linear.len()];
+    check(unsafe { nb_srgb_encode(linear.as_ptr(), linear.len(), out.as_mut_ptr()) }, std::ptr::null())?;
+    Ok(out)
+}
+
+/// What `Scene::eyes` returns: `count` rows of `width` columns each.
+pub struct Eyes {
+    pub width: u32,
+    pub ids: Vec<u32>,   // the nearest instance per column, NB_EYES_NONE where none
+    pub depth: Vec<f32>, // the depth attachment's value, 1.0 where none
+}
+
+/// What `Scene::eyes_colour` returns: the same plus the colour attachment.
+pub struct EyesColour {
+    pub width: u32,
+    pub ids: Vec<u32>,
+    pub depth: Vec<f32>,
+    pub rgba: Vec<[f32; 4]>, // linear, what the fragment shader writes
+    pub bgra8: Vec<u32>,     // the texel of the Bgra8UnormSrgb target, bytes B, G, R, A: what the imgui texture takes
 }
 
 fn check_abi() {
@@ -186,6 +237,66 @@ impl Scene {
 
     pub fn sync(&mut self) -> Result<(), SceneError> {
         check(unsafe { nb_sync(self.ctx) }, self.ctx)
+    }
+
+    /// Every entity's eye view for bodies [first, first + count) of the current state (nb_eyes): replaces
+    /// `eye_cams.update` (src/main.rs:939) and the depth side of `build_command_buffer_parallel` (:962-977).
+    /// `cp` is the eyes' camera constant (`eye_constant(width)` is the reference's), `up` its `normal`.
+    pub fn eyes(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32, first: u32, count: u32, see_self: bool) -> Result<Eyes, SceneError> {
+        let cells = count as usize * width as usize;
+        let mut e = Eyes { width, ids: vec![0; cells.max(1)], depth: vec![0.0; cells.max(1)] };
+        let up = [up.x, up.y, up.z];
+        let flags = if see_self { NB_EYES_SEE_SELF } else { 0 };
+        check(
+            unsafe { nb_eyes(self.ctx, first, count, up.as_ptr(), cp.as_ptr() as *const f32, width, flags, e.ids.as_mut_ptr(), e.depth.as_mut_ptr()) },
+            self.ctx,
+        )?;
+        e.ids.truncate(cells);
+        e.depth.truncate(cells);
+        Ok(e)
+    }
+
+    /// The skin the colour rows sample: `tw` x `th` linear RGBA texels, row 0 first (`skin_from_srgb8` for the decoded
+    /// assets/skin.png); `None`: the 1 x 1 white skin.
+    pub fn set_skin(&mut self, skin: Option<(&[[f32; 4]], u32, u32)>) -> Result<(), SceneError> {
+        match skin {
+            None => check(unsafe { nb_eyes_skin(self.ctx, std::ptr::null(), 0, 0) }, self.ctx),
+            Some((texels, tw, th)) => {
+                if texels.len() != tw as usize * th as usize {
+                    return Err(SceneError(-1, "a skin needs tw * th texels".to_string())); // NB_ERR_INVALID
+                }
+                check(unsafe { nb_eyes_skin(self.ctx, texels.as_ptr() as *const f32, tw, th) }, self.ctx)
+            }
+        }
+    }
+
+    /// The same pass with its colour row (nb_eyes_colour): with it a host drops `build_command_buffer_parallel` and the
+    /// viewport pass (src/main.rs:962-998) and writes row `viewport_camera` of `bgra8` into its imgui texture.
+    pub fn eyes_colour(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32, first: u32, count: u32, see_self: bool) -> Result<EyesColour, SceneError> {
+        let cells = count as usize * width as usize;
+        let mut e = EyesColour {
+            width,
+            ids: vec![0; cells.max(1)],
+            depth: vec![0.0; cells.max(1)],
+            rgba: vec![[0.0; 4]; cells.max(1)],
+            bgra8: vec![0; cells.max(1)],
+        };
+        let up = [up.x, up.y, up.z];
+        let flags = if see_self { NB_EYES_SEE_SELF } else { 0 };
+        check(
+            unsafe {
+                nb_eyes_colour(
+                    self.ctx, first, count, up.as_ptr(), cp.as_ptr() as *const f32, width, flags,
+                    e.ids.as_mut_ptr(), e.depth.as_mut_ptr(), e.rgba.as_mut_ptr() as *mut f32, e.bgra8.as_mut_ptr(),
+                )
+            },
+            self.ctx,
+        )?;
+        e.ids.truncate(cells);
+        e.depth.truncate(cells);
+        e.rgba.truncate(cells);
+        e.bgra8.truncate(cells);
+        Ok(e)
     }
 }
 

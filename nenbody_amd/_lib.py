@@ -34,6 +34,7 @@ NB_RING_OWN, NB_RING_REST, NB_RING_SUMS, NB_RING_OWN_READY = 1, 2, 3, 4
 NB_EYES_NONE = 0xFFFFFFFF
 NB_EYES_SEE_SELF = 1
 NB_EYES_MAX_WIDTH = 4096
+NB_EYES_MAX_SKIN = 2048
 
 _STATUS_NAMES = {
     NB_ERR_INVALID: "NB_ERR_INVALID",
@@ -102,6 +103,12 @@ PROTOTYPES = {
     "nb_launch_cameras": (c_int, [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_eyes": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
     "nb_launch_eyes": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nb_eyes_skin": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32]),
+    "nb_eyes_colour": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_launch_eyes_colour": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_srgb_decode_table": (c_int, [c_void_p]),
+    "nb_srgb_encode": (c_int, [c_void_p, c_size_t, c_void_p]),
     "nb_launch_random_step": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p]),
     "nb_update_instance_nbody": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbParams)]),
     "nb_update_instance_boids": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbBoidsParams)]),

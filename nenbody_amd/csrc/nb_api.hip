@@ -21,6 +21,11 @@
 #include "../../include/nenbody_diag.h"
 #include "nb_kernels.h"
 #include "nb_eyes.h"
+#define NB_SRGB_TABLE static const
+#define NB_SRGB_WANT_DECODE
+#include "nb_srgb_tables.h"
+#undef NB_SRGB_WANT_DECODE
+#undef NB_SRGB_TABLE
 
 #define NB_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -843,6 +848,11 @@ struct nb_ctx {
     uint32_t *eye_ids = nullptr;  // nb_eyes' rows, allocated on first use and grown on demand: eye_ids_cap / eye_depth_cap entries
     float *eye_depth = nullptr;
     size_t eye_ids_cap = 0, eye_depth_cap = 0;
+    float *eye_rgba = nullptr;    // nb_eyes_colour's rows, likewise: eye_rgba_cap / eye_bgra_cap columns (4 floats / one word each)
+    uint32_t *eye_bgra = nullptr;
+    size_t eye_rgba_cap = 0, eye_bgra_cap = 0;
+    float *skin = nullptr;        // nb_eyes_skin's texels (skin_w x skin_h x 4 floats); null: the 1 x 1 white skin
+    uint32_t skin_w = 0, skin_h = 0;
     float *xfer = nullptr;    // 22n floats [matrices 16n | positions 3n | velocities 3n]: one-copy round trip of the drop-in calls
     float *hxfer = nullptr;   // its pinned host twin
     float *hxfer_dev = nullptr;  // the device's address of hxfer (mapped host memory: kernels of the small-set drop-in read and write it directly)
@@ -925,6 +935,9 @@ NB_EXPORT void nb_destroy(nb_ctx *ctx)
     if (ctx->cams) (void)hipFree(ctx->cams);
     if (ctx->eye_ids) (void)hipFree(ctx->eye_ids);
     if (ctx->eye_depth) (void)hipFree(ctx->eye_depth);
+    if (ctx->eye_rgba) (void)hipFree(ctx->eye_rgba);
+    if (ctx->eye_bgra) (void)hipFree(ctx->eye_bgra);
+    if (ctx->skin) (void)hipFree(ctx->skin);
     if (ctx->xfer) (void)hipFree(ctx->xfer);
     if (ctx->hxfer) (void)hipHostFree(ctx->hxfer);
     if (ctx->done_counter) (void)hipFree(ctx->done_counter);
@@ -1334,6 +1347,19 @@ static int eyes_check(const char *fn, uint32_t n, uint32_t first, uint32_t count
     return NB_OK;
 }
 
+// grow one of the context's eye rows to `cells` entries of `cell_bytes` each (nothing to do while it is large enough)
+template <typename T>
+static hipError_t grow_row(T **row, size_t *cap, size_t cells, size_t cell_bytes)
+{
+    if (cells <= *cap) return hipSuccess;
+    if (*row) (void)hipFree(*row);
+    *row = nullptr;
+    *cap = 0;
+    const hipError_t e = hipMalloc((void **)row, cells * cell_bytes);
+    if (e == hipSuccess) *cap = cells;
+    return e;
+}
+
 NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
                       uint32_t flags, uint32_t *ids, float *depth)
 {
@@ -1354,20 +1380,8 @@ NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *
     }
     if (count == 0) return NB_OK;
     const size_t cells = (size_t)count * width;
-    if (ids && cells > ctx->eye_ids_cap) {
-        if (ctx->eye_ids) (void)hipFree(ctx->eye_ids);
-        ctx->eye_ids = nullptr;
-        ctx->eye_ids_cap = 0;
-        NB_HIP(ctx, hipMalloc((void **)&ctx->eye_ids, cells * sizeof(uint32_t)));
-        ctx->eye_ids_cap = cells;
-    }
-    if (depth && cells > ctx->eye_depth_cap) {
-        if (ctx->eye_depth) (void)hipFree(ctx->eye_depth);
-        ctx->eye_depth = nullptr;
-        ctx->eye_depth_cap = 0;
-        NB_HIP(ctx, hipMalloc((void **)&ctx->eye_depth, cells * sizeof(float)));
-        ctx->eye_depth_cap = cells;
-    }
+    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, cells, sizeof(uint32_t)));
+    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, cells, sizeof(float)));
     // the eye cameras of [first, first + count) as nb_cameras forms them, the model matrices of the whole set as nb_download does
     if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
     NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
@@ -1377,6 +1391,143 @@ NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *
                                  ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr, ctx->stream));
     if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+// The colour row.  The checks the three entries share, before anything touches the device, as
+// eyes_check: the width, the range, the flags, the outputs (a colour output at least; no two of the four may overlap, and none may
+// overlap an input).
+struct ByteRange {
+    const void *p;
+    size_t bytes;
+};
+
+static int eyes_colour_check(const char *fn, uint32_t n, uint32_t first, uint32_t count, uint32_t width, uint32_t flags, const void *ids,
+                             const void *depth, const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
+{
+    if (width == 0 || width > NB_EYES_MAX_WIDTH) {
+        *err = std::string(fn) + ": width must be 1 .. NB_EYES_MAX_WIDTH (4096)";
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)first + count > n) {
+        *err = std::string(fn) + ": eyes [first, first + count) exceed the set";
+        return NB_ERR_INVALID;
+    }
+    if (flags & ~NB_EYES_SEE_SELF) {
+        *err = std::string(fn) + ": unknown flag bits";
+        return NB_ERR_INVALID;
+    }
+    if (!rgba && !bgra8) {
+        *err = std::string(fn) + ": rgba and bgra8 are both NULL (ids and depth alone: nb_eyes / nb_launch_eyes)";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)ids | (uintptr_t)depth | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
+        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t cells = (size_t)count * width;
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other or an input";
+                return NB_ERR_INVALID;
+            }
+        for (int b = 0; b < n_in; ++b)
+            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other or an input";
+                return NB_ERR_INVALID;
+            }
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_srgb_decode_table(float *out256)
+{
+    if (!out256) {
+        g_tls_error = "nb_srgb_decode_table: null argument";
+        return NB_ERR_INVALID;
+    }
+    memcpy(out256, kSrgbDecode, sizeof(kSrgbDecode));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_srgb_encode(const float *linear, size_t n, uint8_t *out)
+{
+    if (n && (!linear || !out)) {
+        g_tls_error = "nb_srgb_encode: null argument";
+        return NB_ERR_INVALID;
+    }
+    for (size_t i = 0; i < n; ++i) {   // the number of T[1..255] that are <= c: a NaN gives 0
+        const float c = linear[i];
+        uint32_t b = 0;
+        for (uint32_t step = 128; step; step >>= 1)
+            if (kSrgbEncodeT[b + step] <= c) b += step;
+        out[i] = (uint8_t)b;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_eyes_skin(nb_ctx *ctx, const float *rgba_linear, uint32_t tw, uint32_t th)
+{
+    if (!ctx) {
+        g_tls_error = "nb_eyes_skin: ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (rgba_linear && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
+        ctx->err = "nb_eyes_skin: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
+        return NB_ERR_INVALID;
+    }
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (every eye call waits for its kernel: nothing reads the old skin any more)
+    if (ctx->skin) (void)hipFree(ctx->skin);
+    ctx->skin = nullptr;
+    ctx->skin_w = ctx->skin_h = 0;
+    if (!rgba_linear) return NB_OK;                   // back to the 1 x 1 white skin
+    const size_t bytes = (size_t)tw * th * 4 * sizeof(float);
+    NB_HIP(ctx, hipMalloc((void **)&ctx->skin, bytes));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->skin, rgba_linear, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->skin_w = tw, ctx->skin_h = th;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
+                             uint32_t flags, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8)
+{
+    if (!ctx) {
+        g_tls_error = "nb_eyes_colour: ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (!up_xyz || !cp16) {
+        ctx->err = "nb_eyes_colour: null argument";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
+    int rc = eyes_colour_check("nb_eyes_colour", ctx->n, first, count, width, flags, ids, depth, rgba, bgra8, in, 2, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (!ctx->uploaded) {
+        ctx->err = "nb_eyes_colour: no state uploaded";
+        return NB_ERR_STATE;
+    }
+    if (count == 0) return NB_OK;
+    const size_t cells = (size_t)count * width;
+    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, cells, sizeof(uint32_t)));
+    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, cells, sizeof(float)));
+    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
+    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
+    // cameras and model matrices as nb_eyes forms them
+    if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
+    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    NB_HIP(ctx, nbk::launch_eyes_colour(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
+                                        ctx->skin_w, ctx->skin_h, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
+                                        rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
 }
@@ -1924,6 +2075,41 @@ NB_EXPORT int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, c
     if (rc != NB_OK) return rc;
     hipError_t e = nbk::launch_eyes(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags, (uint32_t *)ids,
                                     (float *)depth, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
+        return NB_ERR_HIP;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n,
+                                    uint32_t width, uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids, void *depth,
+                                    void *rgba, void *bgra8, void *stream)
+{
+    if (!cams_16 || !inst_16n) {
+        g_tls_error = "nb_launch_eyes_colour: null argument";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
+        g_tls_error = "nb_launch_eyes_colour: cams_16, inst_16n, skin and rgba must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
+        g_tls_error = "nb_launch_eyes_colour: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[3] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
+                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}};
+    int rc = eyes_colour_check("nb_launch_eyes_colour", n_total, first, count, width, flags, ids, depth, rgba, bgra8, in, 3, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = check_device(&g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = select_device_of(inst_16n, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    hipError_t e = nbk::launch_eyes_colour(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags,
+                                           (const float *)skin, tw, th, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8,
+                                           (hipStream_t)stream);
     if (e != hipSuccess) {
         g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
         return NB_ERR_HIP;

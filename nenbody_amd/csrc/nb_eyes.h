@@ -11,4 +11,11 @@ namespace nbk {
 hipError_t launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const float *cams, const float *inst, uint32_t width,
                        uint32_t flags, uint32_t *ids, float *depth, hipStream_t s);
 
+// The same with the colour row (rule steps 6-11): skin = tw x th linear RGBA texels, row 0 first, 16-byte aligned, or NULL for the
+// 1 x 1 white skin; rgba: count x width x 4 floats, 16-byte aligned; bgra8: count x width words whose bytes are B, G, R, A.  Any of
+// the four outputs may be NULL.  The caller has checked the arguments (as above; 1 <= tw, th <= NB_EYES_MAX_SKIN where skin is given).
+hipError_t launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, const float *cams, const float *inst, uint32_t width,
+                              uint32_t flags, const float *skin, uint32_t tw, uint32_t th, uint32_t *ids, float *depth, float *rgba,
+                              uint32_t *bgra8, hipStream_t s);
+
 }  // namespace nbk

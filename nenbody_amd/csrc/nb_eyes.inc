@@ -12,6 +12,12 @@
 //   projection   xs = (x / w) * (W/2) + W/2, d = z / w; column c, centre xc = c + 0.5, covered iff min(xs) <= xc < max(xs)
 //   depth        t = (xc - xs0) / (xs1 - xs0), d = d0 + t (d1 - d0); a candidate iff d < 1, then !(d > 0) -> +0
 //   resolve      the minimum over bodies and edges of bits(d) << 32 | j: the nearest, ties to the lower index
+// and, for the colour row (nb_eyes_colour; tests/eyes_colour_restatement.py), per resolved column:
+//   edge         the first of the winner's edges 0, 1, 2 that covers the column, is a candidate and gives the key's depth bits
+//   parameter    s0 = max(t_in, 0), s1 = min(t_out, 1), i = 1 / w of the clipped ends; s = (s0 i0 + t (s1 i1 - s0 i0)) / (i0 + t (i1 - i0))
+//   coordinate   (u, v) = (0, s), (s, 1), (1 - s, 1 - s) for edge 0, 1, 2; texel (min(tw - 1, floor(u tw)), min(th - 1, floor(v th)))
+//   colour       texel * (1 - ((u - 0.5)^2 + (v - 0.5)^2)), alpha 1; no winner: the clear colour (0.1, 0.2, 0.3, 1)
+//   bgra8        per channel the number of thresholds T[1..255] <= c (nb_srgb_tables.h): the exact sRGB byte
 //
 // Shape: one workgroup of 256 lanes per eye (a grid-stride loop over the eyes); the eye's W keys in LDS (W <= 4096: 32 KB), resolved
 // with ds_min_u64 -- the minimum does not depend on the order the candidates arrive in, so the result is deterministic.  A lane takes
@@ -33,8 +39,13 @@ struct EyeSeg {
     uint32_t lo, hi;         // a superset of the covered columns, [lo, hi)
 };
 
+// what the colour row needs of a clipped edge beyond EyeSeg (rule step 7): the clip parameters and the ends' w
+struct EyeTex {
+    float t_in, t_out, w0, w1;
+};
+
 // One edge P0 -> P1 of clip-space vertices (x, y, z, w): clipped, projected, its column range.  false: dropped, or covers no column.
-__device__ __forceinline__ bool eye_edge(const float *P0, const float *P1, float h, uint32_t width, EyeSeg &s)
+__device__ __forceinline__ bool eye_edge(const float *P0, const float *P1, float h, uint32_t width, EyeSeg &s, EyeTex *tx = nullptr)
 {
     float t_in = 0.0f, t_out = 1.0f;
     const float b0v[4] = {P0[2], P0[3] - P0[2], P0[3] + P0[1], P0[3] - P0[1]};   // near, far, y = -w, y = +w
@@ -61,6 +72,7 @@ __device__ __forceinline__ bool eye_edge(const float *P0, const float *P1, float
         Q1[r] = (t_out < 1.0f) ? P0[r] + b : P1[r];
     }
     if (!(Q0[3] > 0.0f && Q1[3] > 0.0f)) return false;
+    if (tx) tx->t_in = t_in, tx->t_out = t_out, tx->w0 = Q0[3], tx->w1 = Q1[3];
     const float u0 = Q0[0] / Q0[3], u1 = Q1[0] / Q1[3];
     const float p0 = u0 * h, p1 = u1 * h;
     s.xs0 = p0 + h;
@@ -106,11 +118,109 @@ __device__ __forceinline__ void eye_cover(uint64_t *keys, uint32_t c, const EyeS
 __device__ __forceinline__ float eye_bcast(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
 __device__ __forceinline__ uint32_t eye_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
 
+// The colour of column c of one eye (rule steps 6-11), its key resolved: the winner's three edges again with eye_edge's own arithmetic,
+// the first that covers c, is a candidate and gives the key's depth bits, then the texture coordinate, one texel, the vignette.
+__device__ __forceinline__ float4 eye_shade(uint64_t key, uint32_t c, const float *C, const float4 *__restrict__ inst, float h,
+                                            uint32_t width, const float4 *__restrict__ skin, uint32_t tw, uint32_t th)
+{
+    const float4 clear = make_float4(0.1f, 0.2f, 0.3f, 1.0f);
+    if (key == ~0ull) return clear;
+    const uint32_t j = (uint32_t)key, dbits = (uint32_t)(key >> 32);
+    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
+    float M[16], P[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float4 v = inst[(size_t)j * 4 + k];
+        M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        float w[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
+            w[r] = ((t0 + t1) + t2) + t3;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float t0 = C[r] * w[0], t1 = C[4 + r] * w[1], t2 = C[8 + r] * w[2], t3 = C[12 + r] * w[3];
+            P[v][r] = ((t0 + t1) + t2) + t3;
+        }
+    }
+    const float xc = (float)c + 0.5f;
+    int edge = -1;
+    float s = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        EyeSeg g{};
+        EyeTex x{};
+        if (edge >= 0 || !eye_edge(P[k], P[k == 2 ? 0 : k + 1], h, width, g, &x)) continue;
+        if (!(g.xa <= xc && xc < g.xb)) continue;
+        const float t = (xc - g.xs0) / g.dx;
+        const float q = t * g.dd;
+        float d = g.d0 + q;
+        if (!(d < 1.0f)) continue;
+        if (!(d > 0.0f)) d = 0.0f;
+        if (__float_as_uint(d) != dbits) continue;
+        edge = k;
+        const float s0 = x.t_in > 0.0f ? x.t_in : 0.0f, s1 = x.t_out < 1.0f ? x.t_out : 1.0f;   // step 7
+        const float i0 = 1.0f / x.w0, i1 = 1.0f / x.w1;
+        const float a0 = s0 * i0, a1 = s1 * i1;
+        const float da = a1 - a0, di = i1 - i0;
+        const float pa = t * da, pi = t * di;
+        const float num = a0 + pa, den = i0 + pi;
+        s = num / den;
+        if (!(s > 0.0f)) s = 0.0f;
+        if (s > 1.0f) s = 1.0f;
+    }
+    if (edge < 0) return clear;   // (the key came from one of the three: not reached)
+    const float r1 = 1.0f - s;
+    const float u = edge == 0 ? 0.0f : edge == 1 ? s : r1;       // step 8: the vertices carry (0,0), (0,1), (1,1)
+    const float v = edge == 0 ? s : edge == 1 ? 1.0f : r1;
+    float4 tex = make_float4(1.0f, 1.0f, 1.0f, 1.0f);            // no skin: 1 x 1 white
+    if (skin) {                                                  // step 9: ClampToEdge, one nearest sample
+        const float fu = u * (float)tw, fv = v * (float)th;
+        const uint32_t fx = (uint32_t)floorf(fu), fy = (uint32_t)floorf(fv);   // 0 <= u, v <= 1: in range of the conversion
+        const uint32_t ix = fx < tw - 1u ? fx : tw - 1u, iy = fy < th - 1u ? fy : th - 1u;
+        tex = skin[(size_t)iy * tw + ix];
+    }
+    const float du = u - 0.5f, dv = v - 0.5f;                    // step 10
+    const float uu = du * du, vv = dv * dv;
+    const float m2 = uu + vv;
+    const float f = 1.0f - m2;
+    return make_float4(tex.x * f, tex.y * f, tex.z * f, 1.0f);
+}
+
+// the sRGB byte of a linear value: the number of thresholds T[1..255] that are <= c (T strictly increasing; a NaN gives 0)
+__device__ __forceinline__ uint32_t eye_srgb_byte(const float *T, float c)
+{
+    uint32_t b = 0;
+#pragma unroll
+    for (uint32_t step = 128; step; step >>= 1)
+        if (T[b + step] <= c) b += step;     // b + step <= 255
+    return b;
+}
+
+#define NB_SRGB_TABLE static __device__ const
+#include "nb_srgb_tables.h"
+#undef NB_SRGB_TABLE
+
+// kColour = false: ids / depth alone (nb_eyes, nb_launch_eyes).  kColour = true: the shading pass too, while the eye's keys are still
+// in LDS -- a lane per column -- with T behind the keys in LDS (width * 8 + 1024 bytes); rgba is a float4 row, bgra8 a uint32 row.
+template <bool kColour>
 __global__ __launch_bounds__(kEyeBlock) void eyes_kernel(uint32_t n_total, uint32_t first, uint32_t count, const float4 *__restrict__ cams,
                                                         const float4 *__restrict__ inst, uint32_t width, uint32_t see_self,
-                                                        uint32_t *__restrict__ ids, float *__restrict__ depth)
+                                                        uint32_t *__restrict__ ids, float *__restrict__ depth,
+                                                        const float4 *__restrict__ skin, uint32_t tw, uint32_t th,
+                                                        float4 *__restrict__ rgba, uint32_t *__restrict__ bgra8)
 {
     extern __shared__ uint64_t eye_keys[];   // width entries
+    float *enc = nullptr;                    // kColour: T behind the keys, 256 entries
+    if constexpr (kColour) {
+        static_assert(kEyeBlock == 256, "one lane copies one entry of T");
+        enc = reinterpret_cast<float *>(eye_keys + width);
+        enc[threadIdx.x] = kSrgbEncodeT[threadIdx.x];   // (the first barrier below orders it)
+    }
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const float h = (float)width * 0.5f;     // exact
     const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
@@ -190,6 +300,12 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_kernel(uint32_t n_total, uint3
             const size_t o = (size_t)e * width + c;
             if (ids) ids[o] = none ? 0xFFFFFFFFu : (uint32_t)key;
             if (depth) depth[o] = none ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+            if constexpr (kColour) {
+                const float4 px = eye_shade(key, c, C, inst, h, width, skin, tw, th);
+                if (rgba) rgba[o] = px;
+                if (bgra8)   // bytes in memory B, G, R, A
+                    bgra8[o] = eye_srgb_byte(enc, px.z) | eye_srgb_byte(enc, px.y) << 8 | eye_srgb_byte(enc, px.x) << 16 | 0xFF000000u;
+            }
         }
         __syncthreads();   // the next eye re-initialises the keys
     }
@@ -199,7 +315,19 @@ hipError_t launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const f
                        uint32_t flags, uint32_t *ids, float *depth, hipStream_t s)
 {
     const uint32_t grid = count < kEyeMaxGrid ? count : kEyeMaxGrid;
-    hipLaunchKernelGGL(eyes_kernel, dim3(grid), dim3(kEyeBlock), (size_t)width * sizeof(uint64_t), s, n_total, first, count,
-                       (const float4 *)cams, (const float4 *)inst, width, flags & 1u, ids, depth);
+    hipLaunchKernelGGL(eyes_kernel<false>, dim3(grid), dim3(kEyeBlock), (size_t)width * sizeof(uint64_t), s, n_total, first, count,
+                       (const float4 *)cams, (const float4 *)inst, width, flags & 1u, ids, depth, (const float4 *)nullptr, 0u, 0u,
+                       (float4 *)nullptr, (uint32_t *)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, const float *cams, const float *inst, uint32_t width,
+                              uint32_t flags, const float *skin, uint32_t tw, uint32_t th, uint32_t *ids, float *depth, float *rgba,
+                              uint32_t *bgra8, hipStream_t s)
+{
+    const uint32_t grid = count < kEyeMaxGrid ? count : kEyeMaxGrid;
+    hipLaunchKernelGGL(eyes_kernel<true>, dim3(grid), dim3(kEyeBlock), (size_t)width * sizeof(uint64_t) + 256 * sizeof(float), s, n_total,
+                       first, count, (const float4 *)cams, (const float4 *)inst, width, flags & 1u, ids, depth, (const float4 *)skin, tw,
+                       th, (float4 *)rgba, bgra8);
     return hipGetLastError();
 }

@@ -19,7 +19,8 @@ import numpy as np
 from . import _lib
 from ._lib import NB_MODE_FAST, NB_MODE_STRICT, NbBoidsParams, NbError, NbParams, check  # noqa: F401  (re-exported)
 
-__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "NB_MODE_STRICT",
+__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "srgb_decode", "srgb_encode",
+           "NB_MODE_STRICT",
            "NB_MODE_FAST", "NbParams", "NbBoidsParams", "NbError"]
 
 
@@ -45,6 +46,23 @@ def eye_constant(width: int = 1024, horizontal_fov_deg: float = 90.0) -> np.ndar
     aspect ratio (src/gfx.rs:379-383), so a row spans 2 atan(width tan(fov / (2 width))) -- 76.3 degrees at 90 and 1024, not 90."""
     w = np.float32(width)
     return camera_constant(float(np.float32(horizontal_fov_deg) / w), float(w / np.float32(1.0)), 1.0, 10000.0)
+
+
+def srgb_decode(srgb8) -> np.ndarray:
+    """8-bit sRGB values as the linear binary32 a Rgba8UnormSrgb texture hands the shader: the library's table
+    D[b] = binary32(decode(b / 255)) (nb_srgb_decode_table).  Same shape as ``srgb8`` (uint8)."""
+    table = np.empty(256, np.float32)
+    check(_lib.load().nb_srgb_decode_table(table.ctypes.data))
+    return table[np.asarray(srgb8, np.uint8)]
+
+
+def srgb_encode(linear) -> np.ndarray:
+    """Linear values as the bytes an sRGB target stores (nb_srgb_encode): the exact nearest byte, table-driven; a NaN gives 0.
+    Same shape as ``linear``, uint8."""
+    lin = np.ascontiguousarray(linear, np.float32)
+    out = np.empty(lin.shape, np.uint8)
+    check(_lib.load().nb_srgb_encode(lin.ctypes.data, lin.size, out.ctypes.data))
+    return out
 
 
 def init_state(n: int, seed: int = 1234):
@@ -153,6 +171,59 @@ class Scene:
         check(self._lib.nb_eyes(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, ids.ctypes.data,
                                 depth.ctypes.data), self._ctx)
         return ids, depth
+
+    def set_skin(self, rgba=None) -> None:
+        """The skin the colour rows sample (nb_eyes_skin): an array (th, tw, 4), row 0 first as the image file stores it -- floats
+        are linear RGBA, uint8 is an sRGB image (Rgba8UnormSrgb: colour through :func:`srgb_decode`, alpha / 255).  None: the 1 x 1
+        white skin, which gives the pure vignette."""
+        if rgba is None:
+            check(self._lib.nb_eyes_skin(self._ctx, None, 0, 0), self._ctx)
+            return
+        a = np.asarray(rgba)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError(f"a skin must have shape (th, tw, 4), got {a.shape}")
+        if a.dtype == np.uint8:
+            lin = np.empty(a.shape, np.float32)
+            lin[..., :3] = srgb_decode(a[..., :3])
+            lin[..., 3] = a[..., 3].astype(np.float32) / np.float32(255)
+        else:
+            lin = np.ascontiguousarray(a, np.float32)
+        check(self._lib.nb_eyes_skin(self._ctx, lin.ctypes.data, a.shape[1], a.shape[0]), self._ctx)
+
+    def eyes_colour(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, first: int = 0, count: Optional[int] = None,
+                    see_self: bool = False):
+        """:meth:`eyes` with the colour row of the same pass (nb_eyes_colour): per column the
+        winning fragment's texel of the skin (:meth:`set_skin`) under the vignette, or the clear colour.
+        Returns (ids, depth, rgba float32 (count, width, 4) linear, bgra8 uint32 (count, width) whose bytes are B, G, R, A: the
+        texel of the reference's Bgra8UnormSrgb target)."""
+        if count is None:
+            count = self.n - first
+        if first < 0 or count < 0:
+            raise ValueError("first and count must be >= 0")
+        if cp is None:   # (an invalid width is the library's to refuse)
+            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MAX_WIDTH else np.zeros((4, 4), np.float32)
+        upv = np.ascontiguousarray(up, np.float32).reshape(3)
+        cpm = np.ascontiguousarray(cp, np.float32).reshape(16)
+        w = max(int(width), 0)
+        ids = np.empty((count, w), np.uint32)
+        depth = np.empty((count, w), np.float32)
+        rgba = np.empty((count, w, 4), np.float32)
+        bgra8 = np.empty((count, w), np.uint32)
+        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
+        check(self._lib.nb_eyes_colour(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, ids.ctypes.data,
+                                       depth.ctypes.data, rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
+        return ids, depth, rgba, bgra8
+
+    def viewport(self, camera: int, scale: float = 0.1, extent=(1024, 768), width: int = 1024, up=(0.0, 0.0, 1.0), cp=None,
+                 see_self: bool = False) -> np.ndarray:
+        """The image the reference's UI shows (src/main.rs:86-96, 981-998): entity ``camera``'s row, a 1-D line of pixels scaled
+        to extent * scale.  Returns uint32 (max(1, int(extent[1] * scale)), max(1, int(extent[0] * scale))), bytes B, G, R, A:
+        every line is the eye's bgra8 row, image column x showing row column floor((x + 0.5) * width / columns)."""
+        cols = max(1, int(extent[0] * scale))
+        rows = max(1, int(extent[1] * scale))
+        row = self.eyes_colour(width, up, cp, camera, 1, see_self)[3][0]
+        pick = ((2 * np.arange(cols, dtype=np.int64) + 1) * width) // (2 * cols)
+        return np.repeat(row[pick][None, :], rows, 0)
 
     def device_state(self, with_instances: bool = True):
         """Device pointers (ints) of the current position records, velocity records and model matrices: the zero-copy
