@@ -190,6 +190,25 @@ int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_
 int nb_srgb_decode_table(float *out256);
 int nb_srgb_encode(const float *linear, size_t n, uint8_t *out);
 
+/* The scene camera's frame: what the reference's display pass leaves in its width x height target
+ * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
+ * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which
+ * instance wrote each pixel.  The eye rule carries over (clip, projection, depth, key, texture coordinate, vignette, sRGB byte) with a
+ * second screen axis, ys = H/2 - (y / w) * H/2, row 0 the top: an edge is walked along its major axis (x iff |dx| >= |dy|), one
+ * pixel per column (or row) whose centre lies in the half-open interval between the projected ends.  There is no "self" to skip, so
+ * flags must be 0.  An empty pixel reads NB_EYES_NONE and 1.0f and the clear colour.  One sample per pixel: no MSAA resolve, no
+ * linear minification, as for the eyes.  Bit-exact, and the same bits from run to run. */
+#define NB_FRAME_MAX_DIM 4096u
+/* One camera from a host-supplied eye and direction, out16 = cp16 * look_at_dir(eye, dir, up), through the kernel nb_cameras runs
+ * (its count 1): the reference's scene camera is eye (p.x, p.y, 990) above the body it follows, dir (0, 0, -1), up (1, 0, 0),
+ * cp16 = nb_camera_constant(90.0f / a, a, 1, 10000) with a = (float)width / (float)height (src/main.rs:753-762, 940-942). */
+int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_xyz, const float *up_xyz, const float *cp16, float *out16);
+/* The frame of the context's current state through cam16 (host, 16 floats, column-major), with the context's skin.  ids / depth /
+ * bgra8: host, height*width each, row 0 first; rgba: host, height*width*4 floats.  Any may be NULL, one at least.  The device rows
+ * and the key plane are the context's, allocated at first use and grown on demand. */
+int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids, float *depth, float *rgba,
+             uint32_t *bgra8);
+
 /* Device -> host, after waiting for queued steps.  Any of the three may be NULL.
  * inst_16n, when given, receives the model matrices of the current state (src/main.rs:437-439),
  * produced on demand by a separate kernel: they never feed back into the dynamics. */
@@ -371,6 +390,16 @@ int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const void 
 int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
                           uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids, void *depth, void *rgba, void *bgra8,
                           void *stream);
+
+/* nb_frame's rule, stateless, on caller-owned device memory: cam_16 = one camera, inst_16n = n_total model matrices, skin as
+ * nb_launch_eyes_colour's (16-byte aligned, all three); scratch = nb_frame_scratch_bytes(width, height) bytes, 8-byte aligned,
+ * rewritten by every call; ids / depth / bgra8: height*width words each, rgba: height*width*4 floats, 16-byte aligned.  Any output
+ * may be NULL, one at least.  No output may overlap another output, an input or the scratch.  n_total = 0 (inst_16n may then be
+ * NULL) gives a frame of clear pixels.  Three kernels on `stream`. */
+size_t nb_frame_scratch_bytes(uint32_t width, uint32_t height);   /* width * height * 8; 0 for an invalid extent */
+int nb_launch_frame(uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height, uint32_t flags,
+                    const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids, void *depth, void *rgba, void *bgra8,
+                    void *stream);
 
 /* One random-walk step (main.rs:381-402) in place for `count` bodies whose global indices start at `first`. */
 int nb_launch_random_step(uint32_t first, uint32_t count, void *pos, void *vel, uint64_t seed, uint64_t step, void *stream);

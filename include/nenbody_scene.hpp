@@ -152,6 +152,39 @@ public:
         return e;
     }
 
+    // One camera from a host-supplied eye and direction (nb_camera_at): cp * look_at_dir(eye, dir, up).  The reference's scene
+    // camera (src/main.rs:753-762, 940-942) is camera_at({p.x, p.y, 990}, {0, 0, -1}, {1, 0, 0}, cp) above the body p it follows,
+    // with cp = nb_camera_constant(90.0f / a, a, 1, 10000), a = (float)width / (float)height.
+    Mat4 camera_at(const Vec3 &eye, const Vec3 &dir, const Vec3 &up, const Mat4 &cp)
+    {
+        Mat4 out{};
+        check(nb_camera_at(ctx_, eye.data(), dir.data(), up.data(), cp[0].data(), out[0].data()), ctx_);
+        return out;
+    }
+    // The scene camera's frame (nb_frame: the reference's display pass, src/main.rs:948-960) of the current state through `camera`,
+    // height rows of width pixels, row 0 the top: per pixel the instance drawn there (NB_EYES_NONE where none), the depth
+    // attachment's value, the linear colour and the Bgra8UnormSrgb texel -- what a headless host presents instead of running
+    // render(&display, ...).  The skin is set_skin's.
+    struct Frame {
+        uint32_t width = 0, height = 0;
+        std::vector<uint32_t> ids;
+        std::vector<float> depth;
+        std::vector<std::array<float, 4>> rgba;
+        std::vector<uint32_t> bgra8;
+    };
+    Frame frame(const Mat4 &camera, uint32_t width = 1920, uint32_t height = 1080)
+    {
+        Frame f;
+        f.width = width, f.height = height;
+        const size_t cells = (size_t)width * height;
+        f.ids.resize(cells ? cells : 1);      // (a pointer the library can check even where the extent is invalid)
+        f.depth.resize(cells ? cells : 1);
+        f.rgba.resize(cells ? cells : 1);
+        f.bgra8.resize(cells ? cells : 1);
+        check(nb_frame(ctx_, camera[0].data(), width, height, 0u, f.ids.data(), f.depth.data(), f.rgba[0].data(), f.bgra8.data()), ctx_);
+        return f;
+    }
+
 private:
     void create(const nb_params &params)
     {

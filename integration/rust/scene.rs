@@ -83,6 +83,37 @@ extern "C" {
     fn nb_eyes_colour(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids: *mut u32, depth: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
     fn nb_srgb_decode_table(out256: *mut f32) -> c_int;
     fn nb_srgb_encode(linear: *const f32, n: usize, out: *mut u8) -> c_int;
+    // the scene camera's frame (the reference's display pass, src/main.rs:948-960)
+    fn nb_camera_at(ctx: *mut NbCtx, eye_xyz: *const f32, dir_xyz: *const f32, up_xyz: *const f32, cp16: *const f32, out16: *mut f32) -> c_int;
+    fn nb_frame(ctx: *mut NbCtx, cam16: *const f32, width: u32, height: u32, flags: u32, ids: *mut u32, depth: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
+    fn nb_frame_scratch_bytes(width: u32, height: u32) -> usize;
+}
+
+pub const NB_FRAME_MAX_DIM: u32 = 4096;
+
+/// The scene camera's constant as the reference forms it for a `width` x `height` target (src/main.rs:753-762,
+/// src/gfx.rs:379-383: the angle divided by the aspect ratio).
+pub fn frame_constant(width: u32, height: u32) -> Result<[[f32; 4]; 4], SceneError> {
+    check_abi();
+    let a = width as f32 / height as f32;
+    let mut cp = [[0.0f32; 4]; 4];
+    check(unsafe { nb_camera_constant(90.0 / a, a, 1.0, 10000.0, cp.as_mut_ptr() as *mut f32) }, std::ptr::null())?;
+    Ok(cp)
+}
+
+/// Bytes of the key plane `nb_launch_frame` needs for an extent (0 for an invalid one); `Scene::frame` keeps its own.
+pub fn frame_scratch_bytes(width: u32, height: u32) -> usize {
+    unsafe { nb_frame_scratch_bytes(width, height) }
+}
+
+/// What `Scene::frame` returns: `height` rows of `width` pixels, row 0 the top.
+pub struct Frame {
+    pub width: u32,
+    pub height: u32,
+    pub ids: Vec<u32>,       // the instance drawn at the pixel, NB_EYES_NONE where none
+    pub depth: Vec<f32>,     // the depth attachment's value, 1.0 where none
+    pub rgba: Vec<[f32; 4]>, // linear, what the fragment shader writes
+    pub bgra8: Vec<u32>,     // the texel of the Bgra8UnormSrgb target, bytes B, G, R, A
 }
 
 pub const NB_EYES_NONE: u32 = 0xFFFF_FFFF;
@@ -297,6 +328,42 @@ impl Scene {
         e.rgba.truncate(cells);
         e.bgra8.truncate(cells);
         Ok(e)
+    }
+
+    /// One camera from a host-supplied eye and direction (nb_camera_at).  The reference's scene camera (src/main.rs:753-762,
+    /// 940-942): `camera_at(Point3::new(p.x, p.y, 990.0), -Vector3::unit_z(), Vector3::unit_x(), &frame_constant(w, h)?)`.
+    pub fn camera_at(&mut self, eye: Point3<f32>, dir: Vector3<f32>, up: Vector3<f32>, cp: &[[f32; 4]; 4]) -> Result<[[f32; 4]; 4], SceneError> {
+        let (eye, dir, up) = ([eye.x, eye.y, eye.z], [dir.x, dir.y, dir.z], [up.x, up.y, up.z]);
+        let mut out = [[0.0f32; 4]; 4];
+        check(
+            unsafe { nb_camera_at(self.ctx, eye.as_ptr(), dir.as_ptr(), up.as_ptr(), cp.as_ptr() as *const f32, out.as_mut_ptr() as *mut f32) },
+            self.ctx,
+        )?;
+        Ok(out)
+    }
+
+    /// The scene camera's frame of the current state (nb_frame): with it a headless host drops `render(&display, ...)`
+    /// (src/main.rs:948-960) and presents, saves or streams `bgra8`.  The skin is `set_skin`'s.
+    pub fn frame(&mut self, camera: &[[f32; 4]; 4], width: u32, height: u32) -> Result<Frame, SceneError> {
+        let cells = width as usize * height as usize;
+        let mut f = Frame {
+            width,
+            height,
+            ids: vec![0; cells.max(1)],
+            depth: vec![0.0; cells.max(1)],
+            rgba: vec![[0.0; 4]; cells.max(1)],
+            bgra8: vec![0; cells.max(1)],
+        };
+        check(
+            unsafe {
+                nb_frame(
+                    self.ctx, camera.as_ptr() as *const f32, width, height, 0,
+                    f.ids.as_mut_ptr(), f.depth.as_mut_ptr(), f.rgba.as_mut_ptr() as *mut f32, f.bgra8.as_mut_ptr(),
+                )
+            },
+            self.ctx,
+        )?;
+        Ok(f)
     }
 }
 

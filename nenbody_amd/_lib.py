@@ -35,6 +35,8 @@ NB_EYES_NONE = 0xFFFFFFFF
 NB_EYES_SEE_SELF = 1
 NB_EYES_MAX_WIDTH = 4096
 NB_EYES_MAX_SKIN = 2048
+# the scene camera's frame (nb_frame / nb_launch_frame)
+NB_FRAME_MAX_DIM = 4096
 
 _STATUS_NAMES = {
     NB_ERR_INVALID: "NB_ERR_INVALID",
@@ -109,6 +111,11 @@ PROTOTYPES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_srgb_decode_table": (c_int, [c_void_p]),
     "nb_srgb_encode": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "nb_camera_at": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_frame": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_frame_scratch_bytes": (c_size_t, [c_uint32, c_uint32]),
+    "nb_launch_frame": (c_int, [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_launch_random_step": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p]),
     "nb_update_instance_nbody": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbParams)]),
     "nb_update_instance_boids": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbBoidsParams)]),

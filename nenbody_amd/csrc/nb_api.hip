@@ -21,6 +21,7 @@
 #include "../../include/nenbody_diag.h"
 #include "nb_kernels.h"
 #include "nb_eyes.h"
+#include "nb_frame.h"
 #define NB_SRGB_TABLE static const
 #define NB_SRGB_WANT_DECODE
 #include "nb_srgb_tables.h"
@@ -853,6 +854,9 @@ struct nb_ctx {
     size_t eye_rgba_cap = 0, eye_bgra_cap = 0;
     float *skin = nullptr;        // nb_eyes_skin's texels (skin_w x skin_h x 4 floats); null: the 1 x 1 white skin
     uint32_t skin_w = 0, skin_h = 0;
+    uint64_t *frame_keys = nullptr;  // nb_frame's key plane, grown on demand: frame_keys_cap pixels (its rows are the eye rows above)
+    size_t frame_keys_cap = 0;
+    float4 *frame_cam = nullptr;     // 6 float4: nb_frame's camera, then nb_camera_at's eye and direction records
     float *xfer = nullptr;    // 22n floats [matrices 16n | positions 3n | velocities 3n]: one-copy round trip of the drop-in calls
     float *hxfer = nullptr;   // its pinned host twin
     float *hxfer_dev = nullptr;  // the device's address of hxfer (mapped host memory: kernels of the small-set drop-in read and write it directly)
@@ -938,6 +942,8 @@ NB_EXPORT void nb_destroy(nb_ctx *ctx)
     if (ctx->eye_rgba) (void)hipFree(ctx->eye_rgba);
     if (ctx->eye_bgra) (void)hipFree(ctx->eye_bgra);
     if (ctx->skin) (void)hipFree(ctx->skin);
+    if (ctx->frame_keys) (void)hipFree(ctx->frame_keys);
+    if (ctx->frame_cam) (void)hipFree(ctx->frame_cam);
     if (ctx->xfer) (void)hipFree(ctx->xfer);
     if (ctx->hxfer) (void)hipHostFree(ctx->hxfer);
     if (ctx->done_counter) (void)hipFree(ctx->done_counter);
@@ -1532,6 +1538,113 @@ NB_EXPORT int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const 
     return NB_OK;
 }
 
+// The scene camera's frame.  The checks nb_frame and nb_launch_frame share, before anything touches the
+// device, as eyes_colour_check: the extent, the flags, the outputs (one at least, 4-byte aligned; no two may overlap, and none may
+// overlap an input or the scratch, which is among `in`).
+static int frame_check(const char *fn, uint32_t width, uint32_t height, uint32_t flags, const void *ids, const void *depth,
+                       const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
+{
+    if (width == 0 || width > NB_FRAME_MAX_DIM || height == 0 || height > NB_FRAME_MAX_DIM) {
+        *err = std::string(fn) + ": width and height must be 1 .. NB_FRAME_MAX_DIM (4096)";
+        return NB_ERR_INVALID;
+    }
+    if (flags) {
+        *err = std::string(fn) + ": flags must be 0";
+        return NB_ERR_INVALID;
+    }
+    if (!ids && !depth && !rgba && !bgra8) {
+        *err = std::string(fn) + ": ids, depth, rgba and bgra8 are all NULL";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)ids | (uintptr_t)depth | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
+        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t cells = (size_t)width * height;
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
+                return NB_ERR_INVALID;
+            }
+        for (int b = 0; b < n_in; ++b)
+            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
+                return NB_ERR_INVALID;
+            }
+    }
+    return NB_OK;
+}
+
+NB_EXPORT size_t nb_frame_scratch_bytes(uint32_t width, uint32_t height)
+{
+    if (width == 0 || width > NB_FRAME_MAX_DIM || height == 0 || height > NB_FRAME_MAX_DIM) return 0;
+    return (size_t)width * height * sizeof(uint64_t);
+}
+
+NB_EXPORT int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_xyz, const float *up_xyz, const float *cp16, float *out16)
+{
+    if (!ctx) {
+        g_tls_error = "nb_camera_at: ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (!eye_xyz || !dir_xyz || !up_xyz || !cp16 || !out16) {
+        ctx->err = "nb_camera_at: null argument";
+        return NB_ERR_INVALID;
+    }
+    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
+    // the eye and the direction as the 16-byte records the camera kernel reads, behind the camera's own four
+    const float rec[8] = {eye_xyz[0], eye_xyz[1], eye_xyz[2], 0.0f, dir_xyz[0], dir_xyz[1], dir_xyz[2], 0.0f};
+    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam + 4, rec, sizeof(rec), hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (rec is on the stack)
+    NB_HIP(ctx, nbk::launch_cameras(1, ctx->frame_cam + 4, ctx->frame_cam + 5, up_xyz, cp16, ctx->frame_cam, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(out16, ctx->frame_cam, 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids, float *depth,
+                       float *rgba, uint32_t *bgra8)
+{
+    if (!ctx) {
+        g_tls_error = "nb_frame: ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (!cam16) {
+        ctx->err = "nb_frame: null argument";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
+    int rc = frame_check("nb_frame", width, height, flags, ids, depth, rgba, bgra8, in, 1, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (!ctx->uploaded) {
+        ctx->err = "nb_frame: no state uploaded";
+        return NB_ERR_STATE;
+    }
+    // the rows are the eye rows (one set of output rows per context), the key plane is the frame's own
+    const size_t cells = (size_t)width * height;
+    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, cells, sizeof(uint32_t)));
+    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, cells, sizeof(float)));
+    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
+    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
+    NB_HIP(ctx, grow_row(&ctx->frame_keys, &ctx->frame_keys_cap, cells, sizeof(uint64_t)));
+    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    // the model matrices of the whole set as nb_eyes forms them
+    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    NB_HIP(ctx, nbk::launch_frame(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
+                                  ctx->skin_h, ctx->frame_keys, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
+                                  rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
 NB_EXPORT int nb_sync(nb_ctx *ctx)
 {
     if (!ctx) {
@@ -2112,6 +2225,44 @@ NB_EXPORT int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t c
                                            (hipStream_t)stream);
     if (e != hipSuccess) {
         g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
+        return NB_ERR_HIP;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_launch_frame(uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height, uint32_t flags,
+                              const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids, void *depth, void *rgba, void *bgra8,
+                              void *stream)
+{
+    if (!cam_16 || !scratch || (n_total && !inst_16n)) {
+        g_tls_error = "nb_launch_frame: null argument";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)cam_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
+        g_tls_error = "nb_launch_frame: cam_16, inst_16n, skin and rgba must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if ((uintptr_t)scratch & 7u) {
+        g_tls_error = "nb_launch_frame: scratch must be 8-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
+        g_tls_error = "nb_launch_frame: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[4] = {{cam_16, 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
+                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}, {scratch, nb_frame_scratch_bytes(width, height)}};
+    int rc = frame_check("nb_launch_frame", width, height, flags, ids, depth, rgba, bgra8, in, 4, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = check_device(&g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = select_device_of(scratch, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    hipError_t e = nbk::launch_frame(n_total, (const float *)cam_16, (const float *)inst_16n, width, height, (const float *)skin, tw, th,
+                                     (uint64_t *)scratch, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8,
+                                     (hipStream_t)stream);
+    if (e != hipSuccess) {
+        g_tls_error = std::string("nb: frame kernel launch failed: ") + hipGetErrorString(e);
         return NB_ERR_HIP;
     }
     return NB_OK;

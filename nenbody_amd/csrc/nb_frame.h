@@ -1,0 +1,16 @@
+// nb_frame.h -- launcher of the frame kernels (nb_frame.inc, compiled in the SLP-off unit of nb_kernels.hip), for the C ABI (nb_api.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace nbk {
+
+// The scene camera's frame of n_total bodies: cam = one camera, inst = n_total model matrices, 16 floats each,
+// column-major, both 16-byte aligned (inst may be NULL where n_total = 0); skin = tw x th linear RGBA texels, row 0 first, 16-byte
+// aligned, or NULL for the 1 x 1 white skin; keys = width * height 64-bit words of scratch, rewritten by every call; ids / depth /
+// bgra8: height x width words each, rgba: height x width x 4 floats, 16-byte aligned, row 0 the top; any of the four may be NULL.
+// Three kernels on stream s: clear, edges, resolve.  The caller has checked the arguments (1 <= width, height <= NB_FRAME_MAX_DIM).
+hipError_t launch_frame(uint32_t n_total, const float *cam, const float *inst, uint32_t width, uint32_t height, const float *skin,
+                        uint32_t tw, uint32_t th, uint64_t *keys, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8, hipStream_t s);
+
+}  // namespace nbk

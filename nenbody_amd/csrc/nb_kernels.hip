@@ -39,6 +39,7 @@
 //   nb_aux.inc           model matrices, cameras, random walk, self-test  (this unit)
 //   nb_boids.inc         boids controller, one-lane and producer/consumer (SLP-off unit)
 //   nb_eyes.inc          every entity's eye view: depth + entity id per column (SLP-off unit; its own launcher, nb_eyes.h)
+//   nb_frame.inc         the scene camera's frame: ids, depth and colour per pixel (SLP-off unit; its own launcher, nb_frame.h)
 //   nb_launch.inc        host-side launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,6 +65,7 @@ static constexpr int kWaves = kBlock / 64;
 #elif defined(NBK_NOSLP_TU)
 #include "nb_boids.inc"
 #include "nb_eyes.inc"        // every entity's eye view: outside the two units kernel_code_sha() stamps the evidence with
+#include "nb_frame.inc"       // the scene camera's frame: likewise; uses nb_eyes.inc's broadcast and sRGB helpers
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib
 from ._lib import NB_MODE_FAST, NB_MODE_STRICT, NbBoidsParams, NbError, NbParams, check  # noqa: F401  (re-exported)
 
-__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "srgb_decode", "srgb_encode",
+__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "frame_constant", "srgb_decode", "srgb_encode",
            "NB_MODE_STRICT",
            "NB_MODE_FAST", "NbParams", "NbBoidsParams", "NbError"]
 
@@ -46,6 +46,14 @@ def eye_constant(width: int = 1024, horizontal_fov_deg: float = 90.0) -> np.ndar
     aspect ratio (src/gfx.rs:379-383), so a row spans 2 atan(width tan(fov / (2 width))) -- 76.3 degrees at 90 and 1024, not 90."""
     w = np.float32(width)
     return camera_constant(float(np.float32(horizontal_fov_deg) / w), float(w / np.float32(1.0)), 1.0, 10000.0)
+
+
+def frame_constant(extent=(1920, 1080), horizontal_fov_deg: float = 90.0) -> np.ndarray:
+    """The constant of the reference's scene camera for a target of ``extent`` = (width, height) pixels, as it forms it
+    (src/main.rs:753-762): the aspect ratio a = (float)width / (float)height, and perspective() given the angle DIVIDED by it
+    (src/gfx.rs:379-383; kept, as for the eyes): camera_constant(fov / a, a, 1, 10000)."""
+    a = np.float32(extent[0]) / np.float32(extent[1])
+    return camera_constant(float(np.float32(horizontal_fov_deg) / a), float(a), 1.0, 10000.0)
 
 
 def srgb_decode(srgb8) -> np.ndarray:
@@ -224,6 +232,45 @@ class Scene:
         row = self.eyes_colour(width, up, cp, camera, 1, see_self)[3][0]
         pick = ((2 * np.arange(cols, dtype=np.int64) + 1) * width) // (2 * cols)
         return np.repeat(row[pick][None, :], rows, 0)
+
+    def camera_at(self, eye, direction, up, cp) -> np.ndarray:
+        """One camera from an eye and a direction given by the host (nb_camera_at): cp * look_at_dir(eye, direction, up), formed by
+        the kernel behind :meth:`cameras`.  Returns (4, 4), [k] = column k."""
+        ev = np.ascontiguousarray(eye, np.float32).reshape(3)
+        dv = np.ascontiguousarray(direction, np.float32).reshape(3)
+        upv = np.ascontiguousarray(up, np.float32).reshape(3)
+        cpm = np.ascontiguousarray(cp, np.float32).reshape(16)
+        out = np.zeros((4, 4), np.float32)
+        check(self._lib.nb_camera_at(self._ctx, ev.ctypes.data, dv.ctypes.data, upv.ctypes.data, cpm.ctypes.data, out.ctypes.data),
+              self._ctx)
+        return out
+
+    def scene_camera(self, extent=(1920, 1080), height: float = 990.0, follow: int = 0, cp=None) -> np.ndarray:
+        """The reference's scene camera for the current state (src/main.rs:753-762, 940-942): the eye ``height`` above body
+        ``follow``, looking down -z with +x up; ``cp`` None: :func:`frame_constant` of ``extent``.  Returns (4, 4)."""
+        p = self.positions()[follow]
+        if cp is None:
+            cp = frame_constant(extent)
+        return self.camera_at((p[0], p[1], height), (0.0, 0.0, -1.0), (1.0, 0.0, 0.0), cp)
+
+    def frame(self, camera=None, extent=(1920, 1080)):
+        """The scene camera's frame (nb_frame): what the reference's display pass leaves in its target of
+        ``extent`` = (width, height) pixels, and which entity wrote each pixel.  ``camera``: (4, 4) with [k] = column k; None: the
+        reference's, :meth:`scene_camera` of ``extent``.  The skin is :meth:`set_skin`'s.
+        Returns (ids uint32 (H, W) -- NB_EYES_NONE where nothing is drawn --, depth float32 (H, W), rgba float32 (H, W, 4) linear,
+        bgra8 uint32 (H, W) whose bytes are B, G, R, A); row 0 is the top."""
+        w, h = int(extent[0]), int(extent[1])
+        if camera is None:   # (an invalid extent is the library's to refuse)
+            camera = self.scene_camera((w, h)) if w > 0 and h > 0 else np.zeros((4, 4), np.float32)
+        cam = np.ascontiguousarray(camera, np.float32).reshape(16)
+        shape = (max(h, 0), max(w, 0))
+        ids = np.empty(shape, np.uint32)
+        depth = np.empty(shape, np.float32)
+        rgba = np.empty(shape + (4,), np.float32)
+        bgra8 = np.empty(shape, np.uint32)
+        check(self._lib.nb_frame(self._ctx, cam.ctypes.data, max(w, 0), max(h, 0), 0, ids.ctypes.data, depth.ctypes.data,
+                                 rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
+        return ids, depth, rgba, bgra8
 
     def device_state(self, with_instances: bool = True):
         """Device pointers (ints) of the current position records, velocity records and model matrices: the zero-copy
