@@ -149,8 +149,8 @@ int nb_camera_constant(float vertical_fov_deg, float aspect_ratio, float near_pl
  * in index order as the LineStrip 0-1-2-0 of its triangle (:130-138, 249), Depth32Float cleared to 1.0, compare Less (:256-260,
  * 626) -- and which instance wrote each pixel.  Per column: the nearest body's id (ties: the lower index) and its depth, or
  * NB_EYES_NONE and 1.0f.  The eye's own body is skipped unless NB_EYES_SEE_SELF (the `n != i` of the controllers).  The colour
- * attachment is nb_eyes_colour's, below.  MSAA is not reproduced: one sample at the column centre.  Bit-exact: a fixed binary32
- * rule, clip = cp * view * (model * vertex). */
+ * attachment is nb_eyes_colour's, below.  MSAA is not reproduced here: one sample at the column centre (the 8-sample rows are
+ * nb_eyes_msaa's, further below).  Bit-exact: a fixed binary32 rule, clip = cp * view * (model * vertex). */
 #define NB_EYES_NONE 0xFFFFFFFFu
 #define NB_EYES_SEE_SELF 1u
 #define NB_EYES_MAX_WIDTH 4096u
@@ -168,8 +168,8 @@ int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, co
  * (shaders/scene.frag:15-16), alpha = 1; an empty column holds the clear colour (0.1, 0.2, 0.3, 1) (:613-618).
  *   rgba    4 floats per column, linear: what the shader writes
  *   bgra8   one uint32 per column whose bytes in memory are B, G, R, A: the texel the sRGB target stores (nb_srgb_encode below)
- * NOT reproduced: the MSAA resolve (one sample at the column centre, as for the depth) and the sampler's linear minification
- * (src/main.rs:362) -- which fragments count as minified depends on screen-space derivatives that a line primitive in a one-pixel-
+ * NOT reproduced: the MSAA resolve (one sample at the column centre, as for the depth; nb_eyes_msaa below resolves 8) and the
+ * sampler's linear minification (src/main.rs:362) -- which fragments count as minified depends on screen-space derivatives that a line primitive in a one-pixel-
  * high target does not define portably; the texel is ClampToEdge with ONE nearest sample, ix = min(tw - 1, floor(u * tw)),
  * iy = min(th - 1, floor(v * th)). */
 #define NB_EYES_MAX_SKIN 2048u
@@ -190,14 +190,31 @@ int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_
 int nb_srgb_decode_table(float *out256);
 int nb_srgb_encode(const float *linear, size_t n, uint8_t *out);
 
+/* The eye rows through 8 samples per column, resolved: the reference renders every target
+ * with msaa_samples = 8 and resolves it (src/main.rs:652, 263, 547, 611), so a span end covers a fraction of its column and a
+ * column where two bodies meet holds a mix of both.  Sample k of column c lies at x = c + o[k], o = (9, 7, 13, 5, 3, 1, 11, 15) / 16
+ * (the x coordinates of Vulkan's standard 8-sample pattern; nb_eyes_sample_offsets); coverage, depth, the winning body and its edge
+ * are nb_eyes' and nb_eyes_colour's rule per sample; there is one fragment per column, body and edge, shaded at the column centre
+ * c + 0.5 whether or not the centre is covered (no sample-rate shading); the column is the mean of its eight samples' colours, the
+ * clear colour where a sample is empty, summed as a tree: (((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7))) * 0.125f.
+ *   ids8, depth8   count*width*8 words each, sample k of column c of eye e at (e*width + c)*8 + k; empty: NB_EYES_NONE and 1.0f
+ *   rgba, bgra8    the resolved rows, shaped as nb_eyes_colour's
+ * Any output may be NULL, one at least.  The skin is the context's (nb_eyes_skin).  1 <= width <= NB_EYES_MSAA_MAX_WIDTH: an eye's
+ * samples are resolved in the 160 KB of LDS of one compute unit.  count = 0 is a no-op.  Bit-exact, the same bits from run to run. */
+#define NB_EYES_SAMPLES 8u
+#define NB_EYES_MSAA_MAX_WIDTH 2048u
+int nb_eyes_sample_offsets(float *out8);   /* host arithmetic, no device */
+int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width, uint32_t flags,
+                 uint32_t *ids8, float *depth8, float *rgba, uint32_t *bgra8);
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which
  * instance wrote each pixel.  The eye rule carries over (clip, projection, depth, key, texture coordinate, vignette, sRGB byte) with a
  * second screen axis, ys = H/2 - (y / w) * H/2, row 0 the top: an edge is walked along its major axis (x iff |dx| >= |dy|), one
  * pixel per column (or row) whose centre lies in the half-open interval between the projected ends.  There is no "self" to skip, so
- * flags must be 0.  An empty pixel reads NB_EYES_NONE and 1.0f and the clear colour.  One sample per pixel: no MSAA resolve, no
- * linear minification, as for the eyes.  Bit-exact, and the same bits from run to run. */
+ * flags must be 0.  An empty pixel reads NB_EYES_NONE and 1.0f and the clear colour.  One sample per pixel: no MSAA resolve (the
+ * eyes have one, nb_eyes_msaa; the frame does not), no linear minification.  Bit-exact, and the same bits from run to run. */
 #define NB_FRAME_MAX_DIM 4096u
 /* One camera from a host-supplied eye and direction, out16 = cp16 * look_at_dir(eye, dir, up), through the kernel nb_cameras runs
  * (its count 1): the reference's scene camera is eye (p.x, p.y, 990) above the body it follows, dir (0, 0, -1), up (1, 0, 0),
@@ -390,6 +407,14 @@ int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const void 
 int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
                           uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids, void *depth, void *rgba, void *bgra8,
                           void *stream);
+
+/* nb_eyes_msaa's rule, stateless, on caller-owned device memory: inputs as nb_launch_eyes_colour's (cams_16, inst_16n and skin 16-byte
+ * aligned); ids8 (uint32) / depth8 (float): count*width*8 words each; rgba: count*width*4 floats, 16-byte aligned; bgra8: count*width
+ * words.  Any output may be NULL, one at least.  No two outputs may overlap, and none may overlap cams_16, inst_16n or skin.
+ * 1 <= width <= NB_EYES_MSAA_MAX_WIDTH.  count = 0 is a no-op.  One kernel on `stream`. */
+int nb_launch_eyes_msaa(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
+                        uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids8, void *depth8, void *rgba, void *bgra8,
+                        void *stream);
 
 /* nb_frame's rule, stateless, on caller-owned device memory: cam_16 = one camera, inst_16n = n_total model matrices, skin as
  * nb_launch_eyes_colour's (16-byte aligned, all three); scratch = nb_frame_scratch_bytes(width, height) bytes, 8-byte aligned,

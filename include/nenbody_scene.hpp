@@ -152,6 +152,37 @@ public:
         return e;
     }
 
+    // The eye rows through 8 samples per column, resolved as the reference's targets are (nb_eyes_msaa; msaa_samples = 8 and
+    // resolve_target, src/main.rs:652, 547, 611): ids8 / depth8 hold the eight samples of every column, sample k of column c of row
+    // e at (e * width + c) * 8 + k; rgba / bgra8 are the resolved rows, shaped as eyes_colour's.  width <= NB_EYES_MSAA_MAX_WIDTH.
+    struct EyesMsaa {
+        uint32_t width = 0;
+        std::vector<std::array<uint32_t, NB_EYES_SAMPLES>> ids8;
+        std::vector<std::array<float, NB_EYES_SAMPLES>> depth8;
+        std::vector<std::array<float, 4>> rgba;
+        std::vector<uint32_t> bgra8;
+    };
+    EyesMsaa eyes_msaa(const Mat4 &cp, uint32_t width = 1024, uint32_t first = 0, uint32_t count = UINT32_MAX, bool see_self = false,
+                       const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (count == UINT32_MAX) count = first <= positions.size() ? (uint32_t)positions.size() - first : 0;
+        EyesMsaa e;
+        e.width = width;
+        const size_t cells = (size_t)count * width;
+        e.ids8.resize(cells ? cells : 1);
+        e.depth8.resize(cells ? cells : 1);
+        e.rgba.resize(cells ? cells : 1);
+        e.bgra8.resize(cells ? cells : 1);
+        check(nb_eyes_msaa(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids8[0].data(),
+                           e.depth8[0].data(), e.rgba[0].data(), e.bgra8.data()),
+              ctx_);
+        e.ids8.resize(cells);
+        e.depth8.resize(cells);
+        e.rgba.resize(cells);
+        e.bgra8.resize(cells);
+        return e;
+    }
+
     // One camera from a host-supplied eye and direction (nb_camera_at): cp * look_at_dir(eye, dir, up).  The reference's scene
     // camera (src/main.rs:753-762, 940-942) is camera_at({p.x, p.y, 990}, {0, 0, -1}, {1, 0, 0}, cp) above the body p it follows,
     // with cp = nb_camera_constant(90.0f / a, a, 1, 10000), a = (float)width / (float)height.

@@ -81,6 +81,8 @@ extern "C" {
     fn nb_eyes(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids: *mut u32, depth: *mut f32) -> c_int;
     fn nb_eyes_skin(ctx: *mut NbCtx, rgba_linear: *const f32, tw: u32, th: u32) -> c_int; // null = the 1 x 1 white skin
     fn nb_eyes_colour(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids: *mut u32, depth: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
+    fn nb_eyes_sample_offsets(out8: *mut f32) -> c_int;
+    fn nb_eyes_msaa(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids8: *mut u32, depth8: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
     fn nb_srgb_decode_table(out256: *mut f32) -> c_int;
     fn nb_srgb_encode(linear: *const f32, n: usize, out: *mut u8) -> c_int;
     // the scene camera's frame (the reference's display pass, src/main.rs:948-960)
@@ -158,6 +160,27 @@ pub struct EyesColour {
     pub depth: Vec<f32>,
     pub rgba: Vec<[f32; 4]>, // linear, what the fragment shader writes
     pub bgra8: Vec<u32>,     // the texel of the Bgra8UnormSrgb target, bytes B, G, R, A: what the imgui texture takes
+}
+
+pub const NB_EYES_SAMPLES: usize = 8;
+pub const NB_EYES_MSAA_MAX_WIDTH: u32 = 2048;
+
+/// Where the eight samples of a column lie: sample k of column c is at c + o[k] (the x coordinates of Vulkan's standard
+/// 8-sample pattern, the reference's `msaa_samples = 8`, src/main.rs:652).
+pub fn eye_sample_offsets() -> Result<[f32; NB_EYES_SAMPLES], SceneError> {
+    check_abi();
+    let mut o = [0.0f32; NB_EYES_SAMPLES];
+    check(unsafe { nb_eyes_sample_offsets(o.as_mut_ptr()) }, std::ptr::null())?;
+    Ok(o)
+}
+
+/// What `Scene::eyes_msaa` returns: per column its eight samples and the resolved colour.
+pub struct EyesMsaa {
+    pub width: u32,
+    pub ids8: Vec<[u32; NB_EYES_SAMPLES]>,   // the nearest instance per sample, NB_EYES_NONE where none
+    pub depth8: Vec<[f32; NB_EYES_SAMPLES]>, // the depth per sample, 1.0 where none
+    pub rgba: Vec<[f32; 4]>,                 // linear: the mean of the samples' fragments and the clear colour
+    pub bgra8: Vec<u32>,                     // the texel of the resolved Bgra8UnormSrgb target, bytes B, G, R, A
 }
 
 fn check_abi() {
@@ -325,6 +348,35 @@ impl Scene {
         )?;
         e.ids.truncate(cells);
         e.depth.truncate(cells);
+        e.rgba.truncate(cells);
+        e.bgra8.truncate(cells);
+        Ok(e)
+    }
+
+    /// The eye rows through 8 samples per column, resolved as the reference's targets are (nb_eyes_msaa; `resolve_target`,
+    /// src/main.rs:547, 611): a span end covers a fraction of its column.  `width` is at most NB_EYES_MSAA_MAX_WIDTH.
+    pub fn eyes_msaa(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32, first: u32, count: u32, see_self: bool) -> Result<EyesMsaa, SceneError> {
+        let cells = count as usize * width as usize;
+        let mut e = EyesMsaa {
+            width,
+            ids8: vec![[0; NB_EYES_SAMPLES]; cells.max(1)],
+            depth8: vec![[0.0; NB_EYES_SAMPLES]; cells.max(1)],
+            rgba: vec![[0.0; 4]; cells.max(1)],
+            bgra8: vec![0; cells.max(1)],
+        };
+        let up = [up.x, up.y, up.z];
+        let flags = if see_self { NB_EYES_SEE_SELF } else { 0 };
+        check(
+            unsafe {
+                nb_eyes_msaa(
+                    self.ctx, first, count, up.as_ptr(), cp.as_ptr() as *const f32, width, flags,
+                    e.ids8.as_mut_ptr() as *mut u32, e.depth8.as_mut_ptr() as *mut f32, e.rgba.as_mut_ptr() as *mut f32, e.bgra8.as_mut_ptr(),
+                )
+            },
+            self.ctx,
+        )?;
+        e.ids8.truncate(cells);
+        e.depth8.truncate(cells);
         e.rgba.truncate(cells);
         e.bgra8.truncate(cells);
         Ok(e)

@@ -35,6 +35,9 @@ NB_EYES_NONE = 0xFFFFFFFF
 NB_EYES_SEE_SELF = 1
 NB_EYES_MAX_WIDTH = 4096
 NB_EYES_MAX_SKIN = 2048
+# the eye rows through 8 samples per column (nb_eyes_msaa / nb_launch_eyes_msaa)
+NB_EYES_SAMPLES = 8
+NB_EYES_MSAA_MAX_WIDTH = 2048
 # the scene camera's frame (nb_frame / nb_launch_frame)
 NB_FRAME_MAX_DIM = 4096
 
@@ -109,6 +112,10 @@ PROTOTYPES = {
     "nb_eyes_colour": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_launch_eyes_colour": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_eyes_sample_offsets": (c_int, [c_void_p]),
+    "nb_eyes_msaa": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_launch_eyes_msaa": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_srgb_decode_table": (c_int, [c_void_p]),
     "nb_srgb_encode": (c_int, [c_void_p, c_size_t, c_void_p]),
     "nb_camera_at": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1538,6 +1538,101 @@ NB_EXPORT int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const 
     return NB_OK;
 }
 
+// The eye rows through 8 samples per column.  The checks nb_eyes_msaa and nb_launch_eyes_msaa
+// share, before anything touches the device, as eyes_colour_check: the width, the range, the flags, the outputs (one at least, 4-byte
+// aligned; no two may overlap, and none may overlap an input).
+static int eyes_msaa_check(const char *fn, uint32_t n, uint32_t first, uint32_t count, uint32_t width, uint32_t flags, const void *ids8,
+                           const void *depth8, const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
+{
+    if (width == 0 || width > NB_EYES_MSAA_MAX_WIDTH) {
+        *err = std::string(fn) + ": width must be 1 .. NB_EYES_MSAA_MAX_WIDTH (2048)";
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)first + count > n) {
+        *err = std::string(fn) + ": eyes [first, first + count) exceed the set";
+        return NB_ERR_INVALID;
+    }
+    if (flags & ~NB_EYES_SEE_SELF) {
+        *err = std::string(fn) + ": unknown flag bits";
+        return NB_ERR_INVALID;
+    }
+    if (!ids8 && !depth8 && !rgba && !bgra8) {
+        *err = std::string(fn) + ": ids8, depth8, rgba and bgra8 are all NULL";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)ids8 | (uintptr_t)depth8 | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
+        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t cells = (size_t)count * width;
+    const ByteRange out[4] = {{ids8, cells * NB_EYES_SAMPLES * 4u}, {depth8, cells * NB_EYES_SAMPLES * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other or an input";
+                return NB_ERR_INVALID;
+            }
+        for (int b = 0; b < n_in; ++b)
+            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other or an input";
+                return NB_ERR_INVALID;
+            }
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_eyes_sample_offsets(float *out8)
+{
+    if (!out8) {
+        g_tls_error = "nb_eyes_sample_offsets: null argument";
+        return NB_ERR_INVALID;
+    }
+    static const float sixteenths[NB_EYES_SAMPLES] = {9.0f, 7.0f, 13.0f, 5.0f, 3.0f, 1.0f, 11.0f, 15.0f};
+    for (uint32_t k = 0; k < NB_EYES_SAMPLES; ++k) out8[k] = sixteenths[k] / 16.0f;   // exact
+    return NB_OK;
+}
+
+NB_EXPORT int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
+                           uint32_t flags, uint32_t *ids8, float *depth8, float *rgba, uint32_t *bgra8)
+{
+    if (!ctx) {
+        g_tls_error = "nb_eyes_msaa: ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (!up_xyz || !cp16) {
+        ctx->err = "nb_eyes_msaa: null argument";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
+    int rc = eyes_msaa_check("nb_eyes_msaa", ctx->n, first, count, width, flags, ids8, depth8, rgba, bgra8, in, 2, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (!ctx->uploaded) {
+        ctx->err = "nb_eyes_msaa: no state uploaded";
+        return NB_ERR_STATE;
+    }
+    if (count == 0) return NB_OK;
+    // the rows are the eye rows (one set of output rows per context), eight words a column for the samples
+    const size_t cells = (size_t)count * width, words = cells * NB_EYES_SAMPLES;
+    if (ids8) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, words, sizeof(uint32_t)));
+    if (depth8) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, words, sizeof(float)));
+    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
+    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
+    // cameras and model matrices as nb_eyes forms them
+    if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
+    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    NB_HIP(ctx, nbk::launch_eyes_msaa(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
+                                      ctx->skin_w, ctx->skin_h, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
+                                      rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+    if (ids8) NB_HIP(ctx, hipMemcpyAsync(ids8, ctx->eye_ids, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth8) NB_HIP(ctx, hipMemcpyAsync(depth8, ctx->eye_depth, words * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
 // The scene camera's frame.  The checks nb_frame and nb_launch_frame share, before anything touches the
 // device, as eyes_colour_check: the extent, the flags, the outputs (one at least, 4-byte aligned; no two may overlap, and none may
 // overlap an input or the scratch, which is among `in`).
@@ -2223,6 +2318,41 @@ NB_EXPORT int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t c
     hipError_t e = nbk::launch_eyes_colour(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags,
                                            (const float *)skin, tw, th, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8,
                                            (hipStream_t)stream);
+    if (e != hipSuccess) {
+        g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
+        return NB_ERR_HIP;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_launch_eyes_msaa(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n,
+                                  uint32_t width, uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids8, void *depth8,
+                                  void *rgba, void *bgra8, void *stream)
+{
+    if (!cams_16 || !inst_16n) {
+        g_tls_error = "nb_launch_eyes_msaa: null argument";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
+        g_tls_error = "nb_launch_eyes_msaa: cams_16, inst_16n, skin and rgba must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
+        g_tls_error = "nb_launch_eyes_msaa: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[3] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
+                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}};
+    int rc = eyes_msaa_check("nb_launch_eyes_msaa", n_total, first, count, width, flags, ids8, depth8, rgba, bgra8, in, 3, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = check_device(&g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = select_device_of(inst_16n, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    hipError_t e = nbk::launch_eyes_msaa(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags,
+                                         (const float *)skin, tw, th, (uint32_t *)ids8, (float *)depth8, (float *)rgba, (uint32_t *)bgra8,
+                                         (hipStream_t)stream);
     if (e != hipSuccess) {
         g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
         return NB_ERR_HIP;

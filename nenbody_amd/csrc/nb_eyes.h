@@ -18,4 +18,11 @@ hipError_t launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, 
                               uint32_t flags, const float *skin, uint32_t tw, uint32_t th, uint32_t *ids, float *depth, float *rgba,
                               uint32_t *bgra8, hipStream_t s);
 
+// The same through 8 samples per column (rule steps M1-M5, nb_eyes_msaa.inc): ids8 / depth8 hold count x width x 8 words, sample k
+// of column c of eye e at (e * width + c) * 8 + k; rgba / bgra8 are the resolved rows, shaped as above.  Any of the four outputs may
+// be NULL.  The caller has checked the arguments (1 <= width <= NB_EYES_MSAA_MAX_WIDTH: the eye's keys take 64 bytes of LDS a column).
+hipError_t launch_eyes_msaa(uint32_t n_total, uint32_t first, uint32_t count, const float *cams, const float *inst, uint32_t width,
+                            uint32_t flags, const float *skin, uint32_t tw, uint32_t th, uint32_t *ids8, float *depth8, float *rgba,
+                            uint32_t *bgra8, hipStream_t s);
+
 }  // namespace nbk

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib
 from ._lib import NB_MODE_FAST, NB_MODE_STRICT, NbBoidsParams, NbError, NbParams, check  # noqa: F401  (re-exported)
 
-__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "frame_constant", "srgb_decode", "srgb_encode",
+__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "eye_sample_offsets", "frame_constant", "srgb_decode", "srgb_encode",
            "NB_MODE_STRICT",
            "NB_MODE_FAST", "NbParams", "NbBoidsParams", "NbError"]
 
@@ -54,6 +54,14 @@ def frame_constant(extent=(1920, 1080), horizontal_fov_deg: float = 90.0) -> np.
     (src/gfx.rs:379-383; kept, as for the eyes): camera_constant(fov / a, a, 1, 10000)."""
     a = np.float32(extent[0]) / np.float32(extent[1])
     return camera_constant(float(np.float32(horizontal_fov_deg) / a), float(a), 1.0, 10000.0)
+
+
+def eye_sample_offsets() -> np.ndarray:
+    """Where the eight samples of a column lie, as fractions of the column (nb_eyes_sample_offsets): sample k of column c is at
+    c + o[k], o = (9, 7, 13, 5, 3, 1, 11, 15) / 16, the x coordinates of Vulkan's standard 8-sample pattern."""
+    out = np.empty(_lib.NB_EYES_SAMPLES, np.float32)
+    check(_lib.load().nb_eyes_sample_offsets(out.ctypes.data))
+    return out
 
 
 def srgb_decode(srgb8) -> np.ndarray:
@@ -222,14 +230,41 @@ class Scene:
                                        depth.ctypes.data, rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
         return ids, depth, rgba, bgra8
 
+    def eyes_msaa(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, first: int = 0, count: Optional[int] = None,
+                  see_self: bool = False):
+        """The eye rows through 8 samples per column, resolved as the reference's targets are (nb_eyes_msaa, DESIGN.md section 10
+        steps M1-M5): sample k of column c lies at c + :func:`eye_sample_offsets` [k]; a column's colour is the mean of its samples'
+        fragments (one fragment per column, body and edge, shaded at the column centre) and of the clear colour where a sample is
+        empty.  ``width`` is at most NB_EYES_MSAA_MAX_WIDTH.
+        Returns (ids8 uint32 (count, width, 8), depth8 float32 (count, width, 8), rgba float32 (count, width, 4) linear, bgra8
+        uint32 (count, width) whose bytes are B, G, R, A)."""
+        if count is None:
+            count = self.n - first
+        if first < 0 or count < 0:
+            raise ValueError("first and count must be >= 0")
+        if cp is None:   # (an invalid width is the library's to refuse)
+            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MSAA_MAX_WIDTH else np.zeros((4, 4), np.float32)
+        upv = np.ascontiguousarray(up, np.float32).reshape(3)
+        cpm = np.ascontiguousarray(cp, np.float32).reshape(16)
+        w = max(int(width), 0)
+        ids8 = np.empty((count, w, _lib.NB_EYES_SAMPLES), np.uint32)
+        depth8 = np.empty((count, w, _lib.NB_EYES_SAMPLES), np.float32)
+        rgba = np.empty((count, w, 4), np.float32)
+        bgra8 = np.empty((count, w), np.uint32)
+        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
+        check(self._lib.nb_eyes_msaa(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, ids8.ctypes.data,
+                                     depth8.ctypes.data, rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
+        return ids8, depth8, rgba, bgra8
+
     def viewport(self, camera: int, scale: float = 0.1, extent=(1024, 768), width: int = 1024, up=(0.0, 0.0, 1.0), cp=None,
-                 see_self: bool = False) -> np.ndarray:
+                 see_self: bool = False, msaa: bool = False) -> np.ndarray:
         """The image the reference's UI shows (src/main.rs:86-96, 981-998): entity ``camera``'s row, a 1-D line of pixels scaled
         to extent * scale.  Returns uint32 (max(1, int(extent[1] * scale)), max(1, int(extent[0] * scale))), bytes B, G, R, A:
-        every line is the eye's bgra8 row, image column x showing row column floor((x + 0.5) * width / columns)."""
+        every line is the eye's bgra8 row, image column x showing row column floor((x + 0.5) * width / columns).  ``msaa``: the
+        row resolved from 8 samples per column (:meth:`eyes_msaa`), as the reference's is, not the one-sample row."""
         cols = max(1, int(extent[0] * scale))
         rows = max(1, int(extent[1] * scale))
-        row = self.eyes_colour(width, up, cp, camera, 1, see_self)[3][0]
+        row = (self.eyes_msaa if msaa else self.eyes_colour)(width, up, cp, camera, 1, see_self)[3][0]
         pick = ((2 * np.arange(cols, dtype=np.int64) + 1) * width) // (2 * cols)
         return np.repeat(row[pick][None, :], rows, 0)
 

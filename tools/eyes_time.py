@@ -4,8 +4,10 @@ rep (in an order that rotates from rep to rep) so that they share the device's s
 
   eyes      nb_launch_eyes (ids + depth)
   colour    nb_launch_eyes_colour (ids + depth + rgba + bgra8, the reference's 20 x 20 skin, tests/golden/skin_rgba8.npy)
+  msaa      nb_launch_eyes_msaa (ids8 + depth8 + rgba + bgra8: 8 samples per column, resolved; the same skin)
   other     nb_launch_eyes of a second build of the library (--other PATH: the parent commit's, say), timed TWICE per rep
             (other, other'): the difference between those two is the spread a build shows against itself
+  othercol  nb_launch_eyes_colour of that second build: what msaa is measured against
 
 then Scene.eyes and Scene.eyes_colour with their downloads at N = 100 and 2 048 (wall).
 
@@ -51,6 +53,8 @@ def launch_ms(n, reps, other):
     depth = torch.empty((n, W), dtype=torch.float32, device=dev)
     rgba = torch.empty((n, W, 4), dtype=torch.float32, device=dev)
     bgra8 = torch.empty((n, W), dtype=torch.int32, device=dev)
+    ids8 = torch.empty((n, W, 8), dtype=torch.int32, device=dev)
+    depth8 = torch.empty((n, W, 8), dtype=torch.float32, device=dev)
     skin = reference_skin()
     st = torch.from_numpy(skin).to(dev)
     th, tw = skin.shape[:2]
@@ -64,14 +68,24 @@ def launch_ms(n, reps, other):
         _lib.check(lib.nb_launch_eyes_colour(n, 0, n, ct.data_ptr(), it.data_ptr(), W, 0, st.data_ptr(), tw, th,
                                              ids.data_ptr(), depth.data_ptr(), rgba.data_ptr(), bgra8.data_ptr(), s.cuda_stream))
 
+    def msaa():
+        _lib.check(lib.nb_launch_eyes_msaa(n, 0, n, ct.data_ptr(), it.data_ptr(), W, 0, st.data_ptr(), tw, th,
+                                           ids8.data_ptr(), depth8.data_ptr(), rgba.data_ptr(), bgra8.data_ptr(), s.cuda_stream))
+
+    def other_colour():
+        rc = other.nb_launch_eyes_colour(n, 0, n, ct.data_ptr(), it.data_ptr(), W, 0, st.data_ptr(), tw, th,
+                                         ids.data_ptr(), depth.data_ptr(), rgba.data_ptr(), bgra8.data_ptr(), s.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"--other: nb_launch_eyes_colour returned {rc}")
+
     def other_eyes():
         rc = other.nb_launch_eyes(n, 0, n, ct.data_ptr(), it.data_ptr(), W, 0, ids.data_ptr(), depth.data_ptr(), s.cuda_stream)
         if rc != 0:
             raise RuntimeError(f"--other: nb_launch_eyes returned {rc}")
 
-    calls = [("eyes", eyes), ("colour", colour)]
+    calls = [("eyes", eyes), ("colour", colour), ("msaa", msaa)]
     if other is not None:
-        calls = [("other", other_eyes), ("eyes", eyes), (AGAIN, other_eyes), ("colour", colour)]
+        calls = [("other", other_eyes), ("eyes", eyes), (AGAIN, other_eyes), ("colour", colour), ("othercol", other_colour), ("msaa", msaa)]
     for _, call in calls:
         call()
     torch.cuda.synchronize()
@@ -86,7 +100,7 @@ def launch_ms(n, reps, other):
             b.synchronize()
             times[name].append(a.elapsed_time(b))
     filled = float((ids != -1).float().mean())
-    del ids, depth, rgba, bgra8
+    del ids, depth, rgba, bgra8, ids8, depth8
     torch.cuda.empty_cache()
     return times, filled
 
@@ -108,11 +122,14 @@ def scene_ms(n, reps):
 
 
 def bind_other(path):
-    """nb_launch_eyes of another build of the library, bound by hand (its other symbols may differ from this binding's)"""
+    """nb_launch_eyes and nb_launch_eyes_colour of another build of the library, bound by hand (its other symbols may differ from
+    this binding's)"""
     lib = ctypes.CDLL(path)
     c_u32, c_p = ctypes.c_uint32, ctypes.c_void_p
     lib.nb_launch_eyes.restype = ctypes.c_int
     lib.nb_launch_eyes.argtypes = [c_u32, c_u32, c_u32, c_p, c_p, c_u32, c_u32, c_p, c_p, c_p]
+    lib.nb_launch_eyes_colour.restype = ctypes.c_int
+    lib.nb_launch_eyes_colour.argtypes = [c_u32, c_u32, c_u32, c_p, c_p, c_u32, c_u32, c_p, c_u32, c_u32, c_p, c_p, c_p, c_p, c_p]
     return lib
 
 
@@ -126,16 +143,18 @@ def main():
         del args[i:i + 2]
     sizes = [int(a) for a in args] or [100, 2048, 16384, 131072]
     print(f"every eye, W = {W}: device ms per call, median / min / max of the reps, the entries alternating; "
-          f"eyes writes 8 bytes per column, colour 28")
+          f"eyes writes 8 bytes per column, colour 28, msaa 84")
     for n in sizes:
         reps = 20 if n <= 16384 else 3
         t, filled = launch_ms(n, reps, other)
         med = {k: statistics.median(v) for k, v in t.items()}
         print(f"  N = {n:6d} ({reps} reps; filled {filled * 100:.1f} %; eyes writes {n * W * 8 / 2**20:.1f} MiB, colour {n * W * 28 / 2**20:.1f} MiB)")
         for name, v in t.items():
-            print(f"    {name:7s} {med[name]:9.4f} / {min(v):9.4f} / {max(v):9.4f} ms", flush=True)
+            print(f"    {name:8s} {med[name]:9.4f} / {min(v):9.4f} / {max(v):9.4f} ms", flush=True)
         print(f"    colour / eyes = {med['colour'] / med['eyes']:.3f} (median), {min(t['colour']) / min(t['eyes']):.3f} (min); "
               f"{3.0 * n * n / min(t['eyes']) / 1e6:7.2f} G eye-edges/s")
+        base = "othercol" if other is not None else "colour"
+        print(f"    msaa / {base} = {med['msaa'] / med[base]:.3f} (median), {min(t['msaa']) / min(t[base]):.3f} (min)")
         if other is not None:
             both = t["other"] + t[AGAIN]
             print(f"    eyes - other = {med['eyes'] - statistics.median(both):+.4f} ms (medians; other: both series together); the spread "
