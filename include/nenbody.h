@@ -213,8 +213,9 @@ int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xy
  * instance wrote each pixel.  The eye rule carries over (clip, projection, depth, key, texture coordinate, vignette, sRGB byte) with a
  * second screen axis, ys = H/2 - (y / w) * H/2, row 0 the top: an edge is walked along its major axis (x iff |dx| >= |dy|), one
  * pixel per column (or row) whose centre lies in the half-open interval between the projected ends.  There is no "self" to skip, so
- * flags must be 0.  An empty pixel reads NB_EYES_NONE and 1.0f and the clear colour.  One sample per pixel: no MSAA resolve (the
- * eyes have one, nb_eyes_msaa; the frame does not), no linear minification.  Bit-exact, and the same bits from run to run. */
+ * flags must be 0.  An empty pixel reads NB_EYES_NONE and 1.0f and the clear colour.  One sample per pixel, at its centre: no MSAA resolve
+ * HERE (the frame resolved from 8 samples per pixel, as the reference's is, is nb_frame_msaa's, below, as the eyes' rows are
+ * nb_eyes_msaa's), no linear minification.  Bit-exact, and the same bits from run to run. */
 #define NB_FRAME_MAX_DIM 4096u
 /* One camera from a host-supplied eye and direction, out16 = cp16 * look_at_dir(eye, dir, up), through the kernel nb_cameras runs
  * (its count 1): the reference's scene camera is eye (p.x, p.y, 990) above the body it follows, dir (0, 0, -1), up (1, 0, 0),
@@ -225,6 +226,26 @@ int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_xyz, const 
  * and the key plane are the context's, allocated at first use and grown on demand. */
 int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids, float *depth, float *rgba,
              uint32_t *bgra8);
+
+/* The frame through 8 samples per pixel, resolved: the reference builds its display target
+ * with msaa_samples = 8 and resolves it into the swapchain image (src/main.rs:652, 685-690, 545-548), so a width-1 line that
+ * crosses a pixel off-centre still shows there, and a pixel where two bodies meet holds a mix of both.  Sample k of pixel (c, r)
+ * lies at (c + ox[k], r + oy[k]), ox = (9, 7, 13, 5, 3, 1, 11, 15) / 16 (nb_eyes_sample_offsets'), oy = (5, 11, 9, 3, 13, 7, 15, 1) / 16:
+ * Vulkan's standard 8-sample pattern (nb_frame_sample_offsets).  nb_frame's clip, projection and major axis are unchanged; along
+ * its major axis an edge tries sample k of step m iff m + oa[k] lies between the projected ends, and the sample belongs to the
+ * pixel whose minor index is floor(o + 0.5 - ob[k]), o the line's minor coordinate there: the line is one pixel wide.  Depth, the
+ * winning body and its edge are nb_frame's rule per sample; there is one fragment per pixel, body and edge, shaded at the pixel
+ * centre whether or not the centre is covered; the pixel is the mean of its eight samples' colours, the clear colour where a
+ * sample is empty, summed as a tree: (((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7))) * 0.125f.
+ *   ids8, depth8   height*width*8 words each, sample k of pixel (c, r) at (r*width + c)*8 + k; empty: NB_EYES_NONE and 1.0f
+ *   rgba, bgra8    the resolved frame, shaped as nb_frame's
+ * Any output may be NULL, one at least.  flags must be 0.  1 <= width, height <= NB_FRAME_MSAA_MAX_DIM: at most 256 MiB of keys and
+ * 128 MiB per sample output.  The device rows and the key plane are the context's, grown on demand as nb_frame's.  Bit-exact, and
+ * the same bits from run to run. */
+#define NB_FRAME_MSAA_MAX_DIM 2048u
+int nb_frame_sample_offsets(float *out16);   /* ox[0..7] then oy[0..7]; host arithmetic, no device */
+int nb_frame_msaa(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids8, float *depth8,
+                  float *rgba, uint32_t *bgra8);
 
 /* Device -> host, after waiting for queued steps.  Any of the three may be NULL.
  * inst_16n, when given, receives the model matrices of the current state (src/main.rs:437-439),
@@ -425,6 +446,16 @@ size_t nb_frame_scratch_bytes(uint32_t width, uint32_t height);   /* width * hei
 int nb_launch_frame(uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height, uint32_t flags,
                     const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids, void *depth, void *rgba, void *bgra8,
                     void *stream);
+
+/* nb_frame_msaa's rule, stateless, on caller-owned device memory: inputs as nb_launch_frame's; scratch =
+ * nb_frame_msaa_scratch_bytes(width, height) bytes, 8-byte aligned, rewritten by every call; ids8 (uint32) / depth8 (float):
+ * height*width*8 words each; rgba: height*width*4 floats, 16-byte aligned; bgra8: height*width words.  Any output may be NULL, one
+ * at least.  No output may overlap another output, an input or the scratch.  n_total = 0 (inst_16n may then be NULL) gives a clear
+ * frame with every sample empty.  Three kernels on `stream`. */
+size_t nb_frame_msaa_scratch_bytes(uint32_t width, uint32_t height);   /* width * height * 64; 0 for an invalid extent */
+int nb_launch_frame_msaa(uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height, uint32_t flags,
+                         const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids8, void *depth8, void *rgba, void *bgra8,
+                         void *stream);
 
 /* One random-walk step (main.rs:381-402) in place for `count` bodies whose global indices start at `first`. */
 int nb_launch_random_step(uint32_t first, uint32_t count, void *pos, void *vel, uint64_t seed, uint64_t step, void *stream);

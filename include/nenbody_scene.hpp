@@ -216,6 +216,31 @@ public:
         return f;
     }
 
+    // The same frame through 8 samples per pixel, resolved as the reference's display target is (nb_frame_msaa; msaa_samples = 8,
+    // src/main.rs:652, 685-690, 545-548): ids8 / depth8 hold the eight samples of every pixel, sample k of pixel (c, r) at
+    // (r * width + c) * 8 + k; rgba / bgra8 are the resolved frame, shaped as frame's.  width, height <= NB_FRAME_MSAA_MAX_DIM.
+    struct FrameMsaa {
+        uint32_t width = 0, height = 0;
+        std::vector<std::array<uint32_t, NB_EYES_SAMPLES>> ids8;
+        std::vector<std::array<float, NB_EYES_SAMPLES>> depth8;
+        std::vector<std::array<float, 4>> rgba;
+        std::vector<uint32_t> bgra8;
+    };
+    FrameMsaa frame_msaa(const Mat4 &camera, uint32_t width = 1920, uint32_t height = 1080)
+    {
+        FrameMsaa f;
+        f.width = width, f.height = height;
+        const bool valid = width >= 1 && width <= NB_FRAME_MSAA_MAX_DIM && height >= 1 && height <= NB_FRAME_MSAA_MAX_DIM;
+        const size_t cells = valid ? (size_t)width * height : 0;   // (an extent the library refuses: nothing to allocate)
+        f.ids8.resize(cells ? cells : 1);     // (a pointer the library can check even where the extent is invalid)
+        f.depth8.resize(cells ? cells : 1);
+        f.rgba.resize(cells ? cells : 1);
+        f.bgra8.resize(cells ? cells : 1);
+        check(nb_frame_msaa(ctx_, camera[0].data(), width, height, 0u, f.ids8[0].data(), f.depth8[0].data(), f.rgba[0].data(), f.bgra8.data()),
+              ctx_);
+        return f;
+    }
+
 private:
     void create(const nb_params &params)
     {

@@ -89,9 +89,14 @@ extern "C" {
     fn nb_camera_at(ctx: *mut NbCtx, eye_xyz: *const f32, dir_xyz: *const f32, up_xyz: *const f32, cp16: *const f32, out16: *mut f32) -> c_int;
     fn nb_frame(ctx: *mut NbCtx, cam16: *const f32, width: u32, height: u32, flags: u32, ids: *mut u32, depth: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
     fn nb_frame_scratch_bytes(width: u32, height: u32) -> usize;
+    // the same through 8 samples per pixel, resolved (msaa_samples = 8, src/main.rs:652, 685-690, 545-548)
+    fn nb_frame_sample_offsets(out16: *mut f32) -> c_int;
+    fn nb_frame_msaa(ctx: *mut NbCtx, cam16: *const f32, width: u32, height: u32, flags: u32, ids8: *mut u32, depth8: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
+    fn nb_frame_msaa_scratch_bytes(width: u32, height: u32) -> usize;
 }
 
 pub const NB_FRAME_MAX_DIM: u32 = 4096;
+pub const NB_FRAME_MSAA_MAX_DIM: u32 = 2048;
 
 /// The scene camera's constant as the reference forms it for a `width` x `height` target (src/main.rs:753-762,
 /// src/gfx.rs:379-383: the angle divided by the aspect ratio).
@@ -116,6 +121,30 @@ pub struct Frame {
     pub depth: Vec<f32>,     // the depth attachment's value, 1.0 where none
     pub rgba: Vec<[f32; 4]>, // linear, what the fragment shader writes
     pub bgra8: Vec<u32>,     // the texel of the Bgra8UnormSrgb target, bytes B, G, R, A
+}
+
+/// Bytes of the key plane `nb_launch_frame_msaa` needs for an extent (0 for an invalid one); `Scene::frame_msaa` keeps its own.
+pub fn frame_msaa_scratch_bytes(width: u32, height: u32) -> usize {
+    unsafe { nb_frame_msaa_scratch_bytes(width, height) }
+}
+
+/// Where the eight samples of a pixel lie: sample k of pixel (c, r) is at (c + o[0][k], r + o[1][k]) -- Vulkan's standard
+/// 8-sample pattern, the reference's `msaa_samples = 8`, src/main.rs:652; o[0] is `eye_sample_offsets`.
+pub fn frame_sample_offsets() -> Result<[[f32; NB_EYES_SAMPLES]; 2], SceneError> {
+    check_abi();
+    let mut o = [[0.0f32; NB_EYES_SAMPLES]; 2];
+    check(unsafe { nb_frame_sample_offsets(o.as_mut_ptr() as *mut f32) }, std::ptr::null())?;
+    Ok(o)
+}
+
+/// What `Scene::frame_msaa` returns: per pixel its eight samples and the resolved colour; row 0 the top.
+pub struct FrameMsaa {
+    pub width: u32,
+    pub height: u32,
+    pub ids8: Vec<[u32; NB_EYES_SAMPLES]>,   // the instance drawn at each sample, NB_EYES_NONE where none
+    pub depth8: Vec<[f32; NB_EYES_SAMPLES]>, // the depth per sample, 1.0 where none
+    pub rgba: Vec<[f32; 4]>,                 // linear: the mean of the samples' fragments and the clear colour
+    pub bgra8: Vec<u32>,                     // the texel of the resolved Bgra8UnormSrgb target, bytes B, G, R, A
 }
 
 pub const NB_EYES_NONE: u32 = 0xFFFF_FFFF;
@@ -411,6 +440,31 @@ impl Scene {
                 nb_frame(
                     self.ctx, camera.as_ptr() as *const f32, width, height, 0,
                     f.ids.as_mut_ptr(), f.depth.as_mut_ptr(), f.rgba.as_mut_ptr() as *mut f32, f.bgra8.as_mut_ptr(),
+                )
+            },
+            self.ctx,
+        )?;
+        Ok(f)
+    }
+
+    /// The same frame through 8 samples per pixel, resolved as the reference's display target is (nb_frame_msaa): a line that
+    /// crosses a pixel off-centre still shows there.  `width` and `height` are at most NB_FRAME_MSAA_MAX_DIM.
+    pub fn frame_msaa(&mut self, camera: &[[f32; 4]; 4], width: u32, height: u32) -> Result<FrameMsaa, SceneError> {
+        let valid = (1..=NB_FRAME_MSAA_MAX_DIM).contains(&width) && (1..=NB_FRAME_MSAA_MAX_DIM).contains(&height);
+        let cells = if valid { width as usize * height as usize } else { 0 }; // (an extent the library refuses: nothing to allocate)
+        let mut f = FrameMsaa {
+            width,
+            height,
+            ids8: vec![[0; NB_EYES_SAMPLES]; cells.max(1)],
+            depth8: vec![[0.0; NB_EYES_SAMPLES]; cells.max(1)],
+            rgba: vec![[0.0; 4]; cells.max(1)],
+            bgra8: vec![0; cells.max(1)],
+        };
+        check(
+            unsafe {
+                nb_frame_msaa(
+                    self.ctx, camera.as_ptr() as *const f32, width, height, 0,
+                    f.ids8.as_mut_ptr() as *mut u32, f.depth8.as_mut_ptr() as *mut f32, f.rgba.as_mut_ptr() as *mut f32, f.bgra8.as_mut_ptr(),
                 )
             },
             self.ctx,

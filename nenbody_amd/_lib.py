@@ -40,6 +40,8 @@ NB_EYES_SAMPLES = 8
 NB_EYES_MSAA_MAX_WIDTH = 2048
 # the scene camera's frame (nb_frame / nb_launch_frame)
 NB_FRAME_MAX_DIM = 4096
+# the frame through 8 samples per pixel (nb_frame_msaa / nb_launch_frame_msaa)
+NB_FRAME_MSAA_MAX_DIM = 2048
 
 _STATUS_NAMES = {
     NB_ERR_INVALID: "NB_ERR_INVALID",
@@ -123,6 +125,11 @@ PROTOTYPES = {
     "nb_frame_scratch_bytes": (c_size_t, [c_uint32, c_uint32]),
     "nb_launch_frame": (c_int, [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_frame_sample_offsets": (c_int, [c_void_p]),
+    "nb_frame_msaa": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_frame_msaa_scratch_bytes": (c_size_t, [c_uint32, c_uint32]),
+    "nb_launch_frame_msaa": (c_int, [c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_launch_random_step": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p]),
     "nb_update_instance_nbody": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbParams)]),
     "nb_update_instance_boids": (c_int, [c_void_p, c_size_t] * 5 + [POINTER(NbBoidsParams)]),

@@ -854,7 +854,7 @@ struct nb_ctx {
     size_t eye_rgba_cap = 0, eye_bgra_cap = 0;
     float *skin = nullptr;        // nb_eyes_skin's texels (skin_w x skin_h x 4 floats); null: the 1 x 1 white skin
     uint32_t skin_w = 0, skin_h = 0;
-    uint64_t *frame_keys = nullptr;  // nb_frame's key plane, grown on demand: frame_keys_cap pixels (its rows are the eye rows above)
+    uint64_t *frame_keys = nullptr;  // nb_frame's and nb_frame_msaa's key plane, grown on demand: frame_keys_cap keys (their rows are the eye rows above)
     size_t frame_keys_cap = 0;
     float4 *frame_cam = nullptr;     // 6 float4: nb_frame's camera, then nb_camera_at's eye and direction records
     float *xfer = nullptr;    // 22n floats [matrices 16n | positions 3n | velocities 3n]: one-copy round trip of the drop-in calls
@@ -1740,6 +1740,104 @@ NB_EXPORT int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t
     return NB_OK;
 }
 
+// The frame through 8 samples per pixel.  The checks nb_frame_msaa and nb_launch_frame_msaa share, before
+// anything touches the device, as frame_check: the extent, the flags, the outputs (one at least, 4-byte aligned; no two may
+// overlap, and none may overlap an input or the scratch, which is among `in`).
+static int frame_msaa_check(const char *fn, uint32_t width, uint32_t height, uint32_t flags, const void *ids8, const void *depth8,
+                            const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
+{
+    if (width == 0 || width > NB_FRAME_MSAA_MAX_DIM || height == 0 || height > NB_FRAME_MSAA_MAX_DIM) {
+        *err = std::string(fn) + ": width and height must be 1 .. NB_FRAME_MSAA_MAX_DIM (2048)";
+        return NB_ERR_INVALID;
+    }
+    if (flags) {
+        *err = std::string(fn) + ": flags must be 0";
+        return NB_ERR_INVALID;
+    }
+    if (!ids8 && !depth8 && !rgba && !bgra8) {
+        *err = std::string(fn) + ": ids8, depth8, rgba and bgra8 are all NULL";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)ids8 | (uintptr_t)depth8 | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
+        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t cells = (size_t)width * height;
+    const ByteRange out[4] = {{ids8, cells * NB_EYES_SAMPLES * 4u}, {depth8, cells * NB_EYES_SAMPLES * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
+                return NB_ERR_INVALID;
+            }
+        for (int b = 0; b < n_in; ++b)
+            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
+                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
+                return NB_ERR_INVALID;
+            }
+    }
+    return NB_OK;
+}
+
+NB_EXPORT size_t nb_frame_msaa_scratch_bytes(uint32_t width, uint32_t height)
+{
+    if (width == 0 || width > NB_FRAME_MSAA_MAX_DIM || height == 0 || height > NB_FRAME_MSAA_MAX_DIM) return 0;
+    return (size_t)width * height * NB_EYES_SAMPLES * sizeof(uint64_t);
+}
+
+NB_EXPORT int nb_frame_sample_offsets(float *out16)
+{
+    if (!out16) {
+        g_tls_error = "nb_frame_sample_offsets: null argument";
+        return NB_ERR_INVALID;
+    }
+    static const float sixteenths[2 * NB_EYES_SAMPLES] = {9.0f, 7.0f, 13.0f, 5.0f, 3.0f, 1.0f, 11.0f, 15.0f,
+                                                          5.0f, 11.0f, 9.0f, 3.0f, 13.0f, 7.0f, 15.0f, 1.0f};
+    for (uint32_t k = 0; k < 2 * NB_EYES_SAMPLES; ++k) out16[k] = sixteenths[k] / 16.0f;   // exact
+    return NB_OK;
+}
+
+NB_EXPORT int nb_frame_msaa(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids8, float *depth8,
+                            float *rgba, uint32_t *bgra8)
+{
+    if (!ctx) {
+        g_tls_error = "nb_frame_msaa: ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (!cam16) {
+        ctx->err = "nb_frame_msaa: null argument";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
+    int rc = frame_msaa_check("nb_frame_msaa", width, height, flags, ids8, depth8, rgba, bgra8, in, 1, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (!ctx->uploaded) {
+        ctx->err = "nb_frame_msaa: no state uploaded";
+        return NB_ERR_STATE;
+    }
+    // the rows are the eye rows and the key plane nb_frame's (one set per context), eight words a pixel for the samples
+    const size_t cells = (size_t)width * height, words = cells * NB_EYES_SAMPLES;
+    if (ids8) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, words, sizeof(uint32_t)));
+    if (depth8) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, words, sizeof(float)));
+    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
+    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
+    NB_HIP(ctx, grow_row(&ctx->frame_keys, &ctx->frame_keys_cap, words, sizeof(uint64_t)));
+    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    // the model matrices of the whole set as nb_eyes forms them
+    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    NB_HIP(ctx, nbk::launch_frame_msaa(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
+                                       ctx->skin_h, ctx->frame_keys, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
+                                       rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+    if (ids8) NB_HIP(ctx, hipMemcpyAsync(ids8, ctx->eye_ids, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth8) NB_HIP(ctx, hipMemcpyAsync(depth8, ctx->eye_depth, words * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
 NB_EXPORT int nb_sync(nb_ctx *ctx)
 {
     if (!ctx) {
@@ -2391,6 +2489,44 @@ NB_EXPORT int nb_launch_frame(uint32_t n_total, const void *cam_16, const void *
     hipError_t e = nbk::launch_frame(n_total, (const float *)cam_16, (const float *)inst_16n, width, height, (const float *)skin, tw, th,
                                      (uint64_t *)scratch, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8,
                                      (hipStream_t)stream);
+    if (e != hipSuccess) {
+        g_tls_error = std::string("nb: frame kernel launch failed: ") + hipGetErrorString(e);
+        return NB_ERR_HIP;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_launch_frame_msaa(uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height, uint32_t flags,
+                                   const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids8, void *depth8, void *rgba,
+                                   void *bgra8, void *stream)
+{
+    if (!cam_16 || !scratch || (n_total && !inst_16n)) {
+        g_tls_error = "nb_launch_frame_msaa: null argument";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)cam_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
+        g_tls_error = "nb_launch_frame_msaa: cam_16, inst_16n, skin and rgba must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if ((uintptr_t)scratch & 7u) {
+        g_tls_error = "nb_launch_frame_msaa: scratch must be 8-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
+        g_tls_error = "nb_launch_frame_msaa: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[4] = {{cam_16, 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
+                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}, {scratch, nb_frame_msaa_scratch_bytes(width, height)}};
+    int rc = frame_msaa_check("nb_launch_frame_msaa", width, height, flags, ids8, depth8, rgba, bgra8, in, 4, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = check_device(&g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = select_device_of(scratch, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    hipError_t e = nbk::launch_frame_msaa(n_total, (const float *)cam_16, (const float *)inst_16n, width, height, (const float *)skin, tw, th,
+                                          (uint64_t *)scratch, (uint32_t *)ids8, (float *)depth8, (float *)rgba, (uint32_t *)bgra8,
+                                          (hipStream_t)stream);
     if (e != hipSuccess) {
         g_tls_error = std::string("nb: frame kernel launch failed: ") + hipGetErrorString(e);
         return NB_ERR_HIP;

@@ -13,4 +13,12 @@ namespace nbk {
 hipError_t launch_frame(uint32_t n_total, const float *cam, const float *inst, uint32_t width, uint32_t height, const float *skin,
                         uint32_t tw, uint32_t th, uint64_t *keys, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8, hipStream_t s);
 
+// The same frame through 8 samples per pixel, resolved: inputs as launch_frame's; keys = width * height * 8
+// 64-bit words of scratch, rewritten by every call; ids8 / depth8: height x width x 8 words each, sample k of pixel (c, r) at
+// (r * width + c) * 8 + k; rgba / bgra8 as launch_frame's; any of the four may be NULL.  Three kernels on stream s: clear, edges,
+// resolve.  The caller has checked the arguments (1 <= width, height <= NB_FRAME_MSAA_MAX_DIM).
+hipError_t launch_frame_msaa(uint32_t n_total, const float *cam, const float *inst, uint32_t width, uint32_t height, const float *skin,
+                             uint32_t tw, uint32_t th, uint64_t *keys, uint32_t *ids8, float *depth8, float *rgba, uint32_t *bgra8,
+                             hipStream_t s);
+
 }  // namespace nbk

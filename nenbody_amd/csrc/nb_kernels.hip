@@ -41,6 +41,7 @@
 //   nb_eyes.inc          every entity's eye view: depth + entity id per column (SLP-off unit; its own launcher, nb_eyes.h)
 //   nb_frame.inc         the scene camera's frame: ids, depth and colour per pixel (SLP-off unit; its own launcher, nb_frame.h)
 //   nb_eyes_msaa.inc     the eye view through 8 samples per column, resolved (SLP-off unit; launcher in nb_eyes.h)
+//   nb_frame_msaa.inc    the scene camera's frame through 8 samples per pixel, resolved (SLP-off unit; launcher in nb_frame.h)
 //   nb_launch.inc        host-side launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,6 +69,7 @@ static constexpr int kWaves = kBlock / 64;
 #include "nb_eyes.inc"        // every entity's eye view: outside the two units kernel_code_sha() stamps the evidence with
 #include "nb_frame.inc"       // the scene camera's frame: likewise; uses nb_eyes.inc's broadcast and sRGB helpers
 #include "nb_eyes_msaa.inc"   // the eye view through 8 samples per column: likewise; uses nb_eyes.inc's edge, broadcast and sRGB helpers
+#include "nb_frame_msaa.inc"  // the frame through 8 samples per pixel: likewise; uses nb_frame.inc's edge and clear, nb_eyes_msaa.inc's fragment
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib
 from ._lib import NB_MODE_FAST, NB_MODE_STRICT, NbBoidsParams, NbError, NbParams, check  # noqa: F401  (re-exported)
 
-__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "eye_sample_offsets", "frame_constant", "srgb_decode", "srgb_encode",
+__all__ = ["Scene", "update_instance_nbody", "update_instance_boids", "update_release", "init_state", "eye_constant", "eye_sample_offsets", "frame_constant", "frame_sample_offsets", "srgb_decode", "srgb_encode",
            "NB_MODE_STRICT",
            "NB_MODE_FAST", "NbParams", "NbBoidsParams", "NbError"]
 
@@ -61,6 +61,15 @@ def eye_sample_offsets() -> np.ndarray:
     c + o[k], o = (9, 7, 13, 5, 3, 1, 11, 15) / 16, the x coordinates of Vulkan's standard 8-sample pattern."""
     out = np.empty(_lib.NB_EYES_SAMPLES, np.float32)
     check(_lib.load().nb_eyes_sample_offsets(out.ctypes.data))
+    return out
+
+
+def frame_sample_offsets() -> np.ndarray:
+    """Where the eight samples of a pixel lie, as fractions of the pixel (nb_frame_sample_offsets): sample k of pixel (c, r) is at
+    (c + o[0, k], r + o[1, k]), o[0] = :func:`eye_sample_offsets`, o[1] = (5, 11, 9, 3, 13, 7, 15, 1) / 16 -- Vulkan's standard
+    8-sample pattern.  Returns (2, 8)."""
+    out = np.empty((2, _lib.NB_EYES_SAMPLES), np.float32)
+    check(_lib.load().nb_frame_sample_offsets(out.ctypes.data))
     return out
 
 
@@ -306,6 +315,30 @@ class Scene:
         check(self._lib.nb_frame(self._ctx, cam.ctypes.data, max(w, 0), max(h, 0), 0, ids.ctypes.data, depth.ctypes.data,
                                  rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
         return ids, depth, rgba, bgra8
+
+    def frame_msaa(self, camera=None, extent=None):
+        """The scene camera's frame through 8 samples per pixel, resolved as the reference's target is (nb_frame_msaa, DESIGN.md
+        section 11.1 steps FM1-FM5): sample k of pixel (c, r) lies at (c, r) + :func:`frame_sample_offsets` [:, k]; a pixel's colour
+        is the mean of its samples' fragments (one fragment per pixel, body and edge, shaded at the pixel centre) and of the clear
+        colour where a sample is empty.  ``camera`` and ``extent`` as :meth:`frame`'s (None: the reference's camera, 1920 x 1080);
+        each side of ``extent`` is at most NB_FRAME_MSAA_MAX_DIM.
+        Returns (ids8 uint32 (H, W, 8), depth8 float32 (H, W, 8), rgba float32 (H, W, 4) linear, bgra8 uint32 (H, W) whose bytes
+        are B, G, R, A); row 0 is the top."""
+        if extent is None:
+            extent = (1920, 1080)
+        w, h = int(extent[0]), int(extent[1])
+        if camera is None:   # (an invalid extent is the library's to refuse)
+            camera = self.scene_camera((w, h)) if w > 0 and h > 0 else np.zeros((4, 4), np.float32)
+        cam = np.ascontiguousarray(camera, np.float32).reshape(16)
+        ok = 0 < w <= _lib.NB_FRAME_MSAA_MAX_DIM and 0 < h <= _lib.NB_FRAME_MSAA_MAX_DIM
+        shape = (h, w) if ok else (0, 0)   # (nothing is allocated for an extent the library refuses)
+        ids8 = np.empty(shape + (_lib.NB_EYES_SAMPLES,), np.uint32)
+        depth8 = np.empty(shape + (_lib.NB_EYES_SAMPLES,), np.float32)
+        rgba = np.empty(shape + (4,), np.float32)
+        bgra8 = np.empty(shape, np.uint32)
+        check(self._lib.nb_frame_msaa(self._ctx, cam.ctypes.data, max(w, 0), max(h, 0), 0, ids8.ctypes.data, depth8.ctypes.data,
+                                      rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
+        return ids8, depth8, rgba, bgra8
 
     def device_state(self, with_instances: bool = True):
         """Device pointers (ints) of the current position records, velocity records and model matrices: the zero-copy
