@@ -1322,13 +1322,26 @@ static bool ranges_overlap(const void *a, size_t an, const void *b, size_t bn)
     return x < y + bn && y < x + an;
 }
 
-// The checks nb_eyes and nb_launch_eyes share, before anything touches the device: the width, the range, the flags, the outputs
-// (one at least; they must not overlap each other or the inputs `in0` / `in1` of in0_bytes / in1_bytes).
-static int eyes_check(const char *fn, uint32_t n, uint32_t first, uint32_t count, uint32_t width, uint32_t flags, const void *ids,
-                      const void *depth, const void *in0, size_t in0_bytes, const void *in1, size_t in1_bytes, std::string *err)
+// What the eye and frame entries check before anything touches the device, the nb_launch_* variants included: first their own
+// extent, range and flags (eyes_range_check / frame_extent_check), then their outputs (outputs_check).
+struct ByteRange {
+    const void *p;
+    size_t bytes;
+};
+
+static const char kNoIdsDepth[] = ": ids and depth are both NULL";
+static const char kNoColour[] = ": rgba and bgra8 are both NULL (ids and depth alone: nb_eyes / nb_launch_eyes)";
+static const char kNoOutputs[] = ": ids, depth, rgba and bgra8 are all NULL";
+static const char kNoOutputs8[] = ": ids8, depth8, rgba and bgra8 are all NULL";
+static const char kEyesAlias[] = ": the outputs must not alias each other or an input";
+static const char kFrameAlias[] = ": the outputs must not alias each other, an input or the scratch";
+
+// the width (msaa: the 8-sample rows' limit), the range of eyes, the flags
+static int eyes_range_check(const char *fn, uint32_t n, uint32_t first, uint32_t count, uint32_t width, bool msaa, uint32_t flags,
+                            std::string *err)
 {
-    if (width == 0 || width > NB_EYES_MAX_WIDTH) {
-        *err = std::string(fn) + ": width must be 1 .. NB_EYES_MAX_WIDTH (4096)";
+    if (width == 0 || width > (msaa ? NB_EYES_MSAA_MAX_WIDTH : NB_EYES_MAX_WIDTH)) {
+        *err = std::string(fn) + (msaa ? ": width must be 1 .. NB_EYES_MSAA_MAX_WIDTH (2048)" : ": width must be 1 .. NB_EYES_MAX_WIDTH (4096)");
         return NB_ERR_INVALID;
     }
     if ((uint64_t)first + count > n) {
@@ -1339,16 +1352,53 @@ static int eyes_check(const char *fn, uint32_t n, uint32_t first, uint32_t count
         *err = std::string(fn) + ": unknown flag bits";
         return NB_ERR_INVALID;
     }
-    if (!ids && !depth) {
-        *err = std::string(fn) + ": ids and depth are both NULL";
+    return NB_OK;
+}
+
+// the extent (msaa: the 8-sample frame's limit), the flags
+static int frame_extent_check(const char *fn, uint32_t width, uint32_t height, bool msaa, uint32_t flags, std::string *err)
+{
+    const uint32_t max_dim = msaa ? NB_FRAME_MSAA_MAX_DIM : NB_FRAME_MAX_DIM;
+    if (width == 0 || width > max_dim || height == 0 || height > max_dim) {
+        *err = std::string(fn) + (msaa ? ": width and height must be 1 .. NB_FRAME_MSAA_MAX_DIM (2048)"
+                                       : ": width and height must be 1 .. NB_FRAME_MAX_DIM (4096)");
         return NB_ERR_INVALID;
     }
-    const size_t row_bytes = (size_t)count * width * 4u;
-    if ((ids && ids == depth) || ranges_overlap(ids, row_bytes, depth, row_bytes) || ranges_overlap(ids, row_bytes, in0, in0_bytes) ||
-        ranges_overlap(ids, row_bytes, in1, in1_bytes) || ranges_overlap(depth, row_bytes, in0, in0_bytes) ||
-        ranges_overlap(depth, row_bytes, in1, in1_bytes)) {
-        *err = std::string(fn) + ": the outputs must not alias each other or an input";
+    if (flags) {
+        *err = std::string(fn) + ": flags must be 0";
         return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// The outputs ids, depth, rgba, bgra8 (NULL: not wanted): one of those in `need` (bit a: out[a]) at least, or none_msg; 4-byte
+// aligned where aligned4 asks for it; no two may overlap, and none may overlap one of the inputs `in` (a frame's scratch among them).
+static int outputs_check(const char *fn, const ByteRange (&out)[4], uint32_t need, const char *none_msg, bool aligned4, const ByteRange *in,
+                         int n_in, const char *alias_msg, std::string *err)
+{
+    uintptr_t bits = 0;
+    bool any = false;
+    for (int a = 0; a < 4; ++a) {
+        bits |= (uintptr_t)out[a].p;
+        any = any || ((need >> a & 1u) && out[a].p);
+    }
+    if (!any) {
+        *err = std::string(fn) + none_msg;
+        return NB_ERR_INVALID;
+    }
+    if (aligned4 && (bits & 3u)) {
+        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    for (int a = 0; a < 4; ++a) {
+        bool alias = false;
+        for (int b = a + 1; b < 4; ++b)
+            alias = alias || (out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes);
+        for (int b = 0; b < n_in; ++b) alias = alias || ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes);
+        if (alias) {
+            *err = std::string(fn) + alias_msg;
+            return NB_ERR_INVALID;
+        }
     }
     return NB_OK;
 }
@@ -1366,6 +1416,44 @@ static hipError_t grow_row(T **row, size_t *cap, size_t cells, size_t cell_bytes
     return e;
 }
 
+// The context's entries then read: check, stage, launch, download.  The three helpers below are their staging and their download,
+// every operation on the context's stream in the order given.
+
+// the context's output rows for the outputs wanted (a NULL host pointer: not wanted): `words` entries of ids and depth, `cells` of
+// rgba and bgra8
+static int grow_rows(nb_ctx *ctx, const void *ids, const void *depth, const void *rgba, const void *bgra8, size_t words, size_t cells)
+{
+    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, words, sizeof(uint32_t)));
+    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, words, sizeof(float)));
+    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
+    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
+    return NB_OK;
+}
+
+// up_xyz given: the eye cameras of [first, first + count) as nb_cameras forms them; then the model matrices of the whole set as
+// nb_download does (both allocated on first use, both formed afresh from the state in place)
+static int stage_matrices(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16)
+{
+    if (up_xyz) {
+        if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
+        NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
+    }
+    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    return NB_OK;
+}
+
+// the rows to the host, for the outputs wanted, and the wait for them
+static int download_rows(nb_ctx *ctx, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8, size_t words, size_t cells)
+{
+    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, words * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
 NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
                       uint32_t flags, uint32_t *ids, float *depth)
 {
@@ -1377,76 +1465,23 @@ NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *
         ctx->err = "nb_eyes: null argument";
         return NB_ERR_INVALID;
     }
-    int rc = eyes_check("nb_eyes", ctx->n, first, count, width, flags, ids, depth, up_xyz, 3 * sizeof(float), cp16, 16 * sizeof(float),
-                        &ctx->err);
+    const size_t cells = (size_t)count * width;
+    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {nullptr, 0}, {nullptr, 0}};
+    int rc = eyes_range_check("nb_eyes", ctx->n, first, count, width, false, flags, &ctx->err);
+    if (rc == NB_OK) rc = outputs_check("nb_eyes", out, 0x3u, kNoIdsDepth, false, in, 2, kEyesAlias, &ctx->err);
     if (rc != NB_OK) return rc;
     if (!ctx->uploaded) {
         ctx->err = "nb_eyes: no state uploaded";
         return NB_ERR_STATE;
     }
     if (count == 0) return NB_OK;
-    const size_t cells = (size_t)count * width;
-    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, cells, sizeof(uint32_t)));
-    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, cells, sizeof(float)));
-    // the eye cameras of [first, first + count) as nb_cameras forms them, the model matrices of the whole set as nb_download does
-    if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
-    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    rc = grow_rows(ctx, ids, depth, nullptr, nullptr, cells, cells);
+    if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
+    if (rc != NB_OK) return rc;
     NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags,
                                  ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr, ctx->stream));
-    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NB_OK;
-}
-
-// The colour row.  The checks the three entries share, before anything touches the device, as
-// eyes_check: the width, the range, the flags, the outputs (a colour output at least; no two of the four may overlap, and none may
-// overlap an input).
-struct ByteRange {
-    const void *p;
-    size_t bytes;
-};
-
-static int eyes_colour_check(const char *fn, uint32_t n, uint32_t first, uint32_t count, uint32_t width, uint32_t flags, const void *ids,
-                             const void *depth, const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
-{
-    if (width == 0 || width > NB_EYES_MAX_WIDTH) {
-        *err = std::string(fn) + ": width must be 1 .. NB_EYES_MAX_WIDTH (4096)";
-        return NB_ERR_INVALID;
-    }
-    if ((uint64_t)first + count > n) {
-        *err = std::string(fn) + ": eyes [first, first + count) exceed the set";
-        return NB_ERR_INVALID;
-    }
-    if (flags & ~NB_EYES_SEE_SELF) {
-        *err = std::string(fn) + ": unknown flag bits";
-        return NB_ERR_INVALID;
-    }
-    if (!rgba && !bgra8) {
-        *err = std::string(fn) + ": rgba and bgra8 are both NULL (ids and depth alone: nb_eyes / nb_launch_eyes)";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)ids | (uintptr_t)depth | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
-        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)count * width;
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = a + 1; b < 4; ++b)
-            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other or an input";
-                return NB_ERR_INVALID;
-            }
-        for (int b = 0; b < n_in; ++b)
-            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other or an input";
-                return NB_ERR_INVALID;
-            }
-    }
-    return NB_OK;
+    return download_rows(ctx, ids, depth, nullptr, nullptr, cells, cells);
 }
 
 NB_EXPORT int nb_srgb_decode_table(float *out256)
@@ -1498,6 +1533,7 @@ NB_EXPORT int nb_eyes_skin(nb_ctx *ctx, const float *rgba_linear, uint32_t tw, u
     return NB_OK;
 }
 
+// The colour row: a colour output at least.
 NB_EXPORT int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
                              uint32_t flags, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8)
 {
@@ -1509,76 +1545,24 @@ NB_EXPORT int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const 
         ctx->err = "nb_eyes_colour: null argument";
         return NB_ERR_INVALID;
     }
+    const size_t cells = (size_t)count * width;
     const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
-    int rc = eyes_colour_check("nb_eyes_colour", ctx->n, first, count, width, flags, ids, depth, rgba, bgra8, in, 2, &ctx->err);
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = eyes_range_check("nb_eyes_colour", ctx->n, first, count, width, false, flags, &ctx->err);
+    if (rc == NB_OK) rc = outputs_check("nb_eyes_colour", out, 0xCu, kNoColour, true, in, 2, kEyesAlias, &ctx->err);
     if (rc != NB_OK) return rc;
     if (!ctx->uploaded) {
         ctx->err = "nb_eyes_colour: no state uploaded";
         return NB_ERR_STATE;
     }
     if (count == 0) return NB_OK;
-    const size_t cells = (size_t)count * width;
-    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, cells, sizeof(uint32_t)));
-    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, cells, sizeof(float)));
-    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
-    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
-    // cameras and model matrices as nb_eyes forms them
-    if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
-    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    rc = grow_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
+    if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
+    if (rc != NB_OK) return rc;
     NB_HIP(ctx, nbk::launch_eyes_colour(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
                                         ctx->skin_w, ctx->skin_h, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
                                         rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NB_OK;
-}
-
-// The eye rows through 8 samples per column.  The checks nb_eyes_msaa and nb_launch_eyes_msaa
-// share, before anything touches the device, as eyes_colour_check: the width, the range, the flags, the outputs (one at least, 4-byte
-// aligned; no two may overlap, and none may overlap an input).
-static int eyes_msaa_check(const char *fn, uint32_t n, uint32_t first, uint32_t count, uint32_t width, uint32_t flags, const void *ids8,
-                           const void *depth8, const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
-{
-    if (width == 0 || width > NB_EYES_MSAA_MAX_WIDTH) {
-        *err = std::string(fn) + ": width must be 1 .. NB_EYES_MSAA_MAX_WIDTH (2048)";
-        return NB_ERR_INVALID;
-    }
-    if ((uint64_t)first + count > n) {
-        *err = std::string(fn) + ": eyes [first, first + count) exceed the set";
-        return NB_ERR_INVALID;
-    }
-    if (flags & ~NB_EYES_SEE_SELF) {
-        *err = std::string(fn) + ": unknown flag bits";
-        return NB_ERR_INVALID;
-    }
-    if (!ids8 && !depth8 && !rgba && !bgra8) {
-        *err = std::string(fn) + ": ids8, depth8, rgba and bgra8 are all NULL";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)ids8 | (uintptr_t)depth8 | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
-        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)count * width;
-    const ByteRange out[4] = {{ids8, cells * NB_EYES_SAMPLES * 4u}, {depth8, cells * NB_EYES_SAMPLES * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = a + 1; b < 4; ++b)
-            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other or an input";
-                return NB_ERR_INVALID;
-            }
-        for (int b = 0; b < n_in; ++b)
-            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other or an input";
-                return NB_ERR_INVALID;
-            }
-    }
-    return NB_OK;
+    return download_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
 }
 
 NB_EXPORT int nb_eyes_sample_offsets(float *out8)
@@ -1587,11 +1571,13 @@ NB_EXPORT int nb_eyes_sample_offsets(float *out8)
         g_tls_error = "nb_eyes_sample_offsets: null argument";
         return NB_ERR_INVALID;
     }
-    static const float sixteenths[NB_EYES_SAMPLES] = {9.0f, 7.0f, 13.0f, 5.0f, 3.0f, 1.0f, 11.0f, 15.0f};
-    for (uint32_t k = 0; k < NB_EYES_SAMPLES; ++k) out8[k] = sixteenths[k] / 16.0f;   // exact
+    static_assert(NB_EYES_SAMPLES == 8, "nb_eyes.h lists eight");
+    for (uint32_t k = 0; k < NB_EYES_SAMPLES; ++k) out8[k] = (float)nbk::kEyeSampleX16[k] / 16.0f;   // exact
     return NB_OK;
 }
 
+// The eye rows through 8 samples per column: the rows are the eye rows (one set of output rows
+// per context), eight words a column for the samples.
 NB_EXPORT int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
                            uint32_t flags, uint32_t *ids8, float *depth8, float *rgba, uint32_t *bgra8)
 {
@@ -1603,73 +1589,24 @@ NB_EXPORT int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const fl
         ctx->err = "nb_eyes_msaa: null argument";
         return NB_ERR_INVALID;
     }
+    const size_t cells = (size_t)count * width, words = cells * NB_EYES_SAMPLES;
     const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
-    int rc = eyes_msaa_check("nb_eyes_msaa", ctx->n, first, count, width, flags, ids8, depth8, rgba, bgra8, in, 2, &ctx->err);
+    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = eyes_range_check("nb_eyes_msaa", ctx->n, first, count, width, true, flags, &ctx->err);
+    if (rc == NB_OK) rc = outputs_check("nb_eyes_msaa", out, 0xFu, kNoOutputs8, true, in, 2, kEyesAlias, &ctx->err);
     if (rc != NB_OK) return rc;
     if (!ctx->uploaded) {
         ctx->err = "nb_eyes_msaa: no state uploaded";
         return NB_ERR_STATE;
     }
     if (count == 0) return NB_OK;
-    // the rows are the eye rows (one set of output rows per context), eight words a column for the samples
-    const size_t cells = (size_t)count * width, words = cells * NB_EYES_SAMPLES;
-    if (ids8) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, words, sizeof(uint32_t)));
-    if (depth8) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, words, sizeof(float)));
-    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
-    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
-    // cameras and model matrices as nb_eyes forms them
-    if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
-    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    rc = grow_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
+    if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
+    if (rc != NB_OK) return rc;
     NB_HIP(ctx, nbk::launch_eyes_msaa(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
                                       ctx->skin_w, ctx->skin_h, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
                                       rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    if (ids8) NB_HIP(ctx, hipMemcpyAsync(ids8, ctx->eye_ids, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (depth8) NB_HIP(ctx, hipMemcpyAsync(depth8, ctx->eye_depth, words * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NB_OK;
-}
-
-// The scene camera's frame.  The checks nb_frame and nb_launch_frame share, before anything touches the
-// device, as eyes_colour_check: the extent, the flags, the outputs (one at least, 4-byte aligned; no two may overlap, and none may
-// overlap an input or the scratch, which is among `in`).
-static int frame_check(const char *fn, uint32_t width, uint32_t height, uint32_t flags, const void *ids, const void *depth,
-                       const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
-{
-    if (width == 0 || width > NB_FRAME_MAX_DIM || height == 0 || height > NB_FRAME_MAX_DIM) {
-        *err = std::string(fn) + ": width and height must be 1 .. NB_FRAME_MAX_DIM (4096)";
-        return NB_ERR_INVALID;
-    }
-    if (flags) {
-        *err = std::string(fn) + ": flags must be 0";
-        return NB_ERR_INVALID;
-    }
-    if (!ids && !depth && !rgba && !bgra8) {
-        *err = std::string(fn) + ": ids, depth, rgba and bgra8 are all NULL";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)ids | (uintptr_t)depth | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
-        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)width * height;
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = a + 1; b < 4; ++b)
-            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
-                return NB_ERR_INVALID;
-            }
-        for (int b = 0; b < n_in; ++b)
-            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
-                return NB_ERR_INVALID;
-            }
-    }
-    return NB_OK;
+    return download_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
 }
 
 NB_EXPORT size_t nb_frame_scratch_bytes(uint32_t width, uint32_t height)
@@ -1699,6 +1636,16 @@ NB_EXPORT int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_x
     return NB_OK;
 }
 
+// the frame's own staging: the key plane (one per context, grown on demand) and the camera
+static int stage_frame(nb_ctx *ctx, const float *cam16, size_t keys)
+{
+    NB_HIP(ctx, grow_row(&ctx->frame_keys, &ctx->frame_keys_cap, keys, sizeof(uint64_t)));
+    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return NB_OK;
+}
+
+// The scene camera's frame: the rows are the eye rows, the key plane is the frame's own.
 NB_EXPORT int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids, float *depth,
                        float *rgba, uint32_t *bgra8)
 {
@@ -1710,73 +1657,24 @@ NB_EXPORT int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t
         ctx->err = "nb_frame: null argument";
         return NB_ERR_INVALID;
     }
+    const size_t cells = (size_t)width * height;
     const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
-    int rc = frame_check("nb_frame", width, height, flags, ids, depth, rgba, bgra8, in, 1, &ctx->err);
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = frame_extent_check("nb_frame", width, height, false, flags, &ctx->err);
+    if (rc == NB_OK) rc = outputs_check("nb_frame", out, 0xFu, kNoOutputs, true, in, 1, kFrameAlias, &ctx->err);
     if (rc != NB_OK) return rc;
     if (!ctx->uploaded) {
         ctx->err = "nb_frame: no state uploaded";
         return NB_ERR_STATE;
     }
-    // the rows are the eye rows (one set of output rows per context), the key plane is the frame's own
-    const size_t cells = (size_t)width * height;
-    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, cells, sizeof(uint32_t)));
-    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, cells, sizeof(float)));
-    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
-    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
-    NB_HIP(ctx, grow_row(&ctx->frame_keys, &ctx->frame_keys_cap, cells, sizeof(uint64_t)));
-    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
-    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    // the model matrices of the whole set as nb_eyes forms them
-    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    rc = grow_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
+    if (rc == NB_OK) rc = stage_frame(ctx, cam16, cells);
+    if (rc == NB_OK) rc = stage_matrices(ctx, 0, 0, nullptr, nullptr);
+    if (rc != NB_OK) return rc;
     NB_HIP(ctx, nbk::launch_frame(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
                                   ctx->skin_h, ctx->frame_keys, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
                                   rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, cells * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NB_OK;
-}
-
-// The frame through 8 samples per pixel.  The checks nb_frame_msaa and nb_launch_frame_msaa share, before
-// anything touches the device, as frame_check: the extent, the flags, the outputs (one at least, 4-byte aligned; no two may
-// overlap, and none may overlap an input or the scratch, which is among `in`).
-static int frame_msaa_check(const char *fn, uint32_t width, uint32_t height, uint32_t flags, const void *ids8, const void *depth8,
-                            const void *rgba, const void *bgra8, const ByteRange *in, int n_in, std::string *err)
-{
-    if (width == 0 || width > NB_FRAME_MSAA_MAX_DIM || height == 0 || height > NB_FRAME_MSAA_MAX_DIM) {
-        *err = std::string(fn) + ": width and height must be 1 .. NB_FRAME_MSAA_MAX_DIM (2048)";
-        return NB_ERR_INVALID;
-    }
-    if (flags) {
-        *err = std::string(fn) + ": flags must be 0";
-        return NB_ERR_INVALID;
-    }
-    if (!ids8 && !depth8 && !rgba && !bgra8) {
-        *err = std::string(fn) + ": ids8, depth8, rgba and bgra8 are all NULL";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)ids8 | (uintptr_t)depth8 | (uintptr_t)rgba | (uintptr_t)bgra8) & 3u) {
-        *err = std::string(fn) + ": the outputs must be 4-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)width * height;
-    const ByteRange out[4] = {{ids8, cells * NB_EYES_SAMPLES * 4u}, {depth8, cells * NB_EYES_SAMPLES * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    for (int a = 0; a < 4; ++a) {
-        for (int b = a + 1; b < 4; ++b)
-            if ((out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
-                return NB_ERR_INVALID;
-            }
-        for (int b = 0; b < n_in; ++b)
-            if (ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
-                *err = std::string(fn) + ": the outputs must not alias each other, an input or the scratch";
-                return NB_ERR_INVALID;
-            }
-    }
-    return NB_OK;
+    return download_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
 }
 
 NB_EXPORT size_t nb_frame_msaa_scratch_bytes(uint32_t width, uint32_t height)
@@ -1791,12 +1689,15 @@ NB_EXPORT int nb_frame_sample_offsets(float *out16)
         g_tls_error = "nb_frame_sample_offsets: null argument";
         return NB_ERR_INVALID;
     }
-    static const float sixteenths[2 * NB_EYES_SAMPLES] = {9.0f, 7.0f, 13.0f, 5.0f, 3.0f, 1.0f, 11.0f, 15.0f,
-                                                          5.0f, 11.0f, 9.0f, 3.0f, 13.0f, 7.0f, 15.0f, 1.0f};
-    for (uint32_t k = 0; k < 2 * NB_EYES_SAMPLES; ++k) out16[k] = sixteenths[k] / 16.0f;   // exact
+    for (uint32_t k = 0; k < NB_EYES_SAMPLES; ++k) {   // exact
+        out16[k] = (float)nbk::kEyeSampleX16[k] / 16.0f;
+        out16[NB_EYES_SAMPLES + k] = (float)nbk::kFrameSampleY16[k] / 16.0f;
+    }
     return NB_OK;
 }
 
+// The frame through 8 samples per pixel: the rows and the key plane are nb_frame's, eight words a pixel for
+// the samples.
 NB_EXPORT int nb_frame_msaa(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids8, float *depth8,
                             float *rgba, uint32_t *bgra8)
 {
@@ -1808,34 +1709,24 @@ NB_EXPORT int nb_frame_msaa(nb_ctx *ctx, const float *cam16, uint32_t width, uin
         ctx->err = "nb_frame_msaa: null argument";
         return NB_ERR_INVALID;
     }
+    const size_t cells = (size_t)width * height, words = cells * NB_EYES_SAMPLES;
     const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
-    int rc = frame_msaa_check("nb_frame_msaa", width, height, flags, ids8, depth8, rgba, bgra8, in, 1, &ctx->err);
+    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = frame_extent_check("nb_frame_msaa", width, height, true, flags, &ctx->err);
+    if (rc == NB_OK) rc = outputs_check("nb_frame_msaa", out, 0xFu, kNoOutputs8, true, in, 1, kFrameAlias, &ctx->err);
     if (rc != NB_OK) return rc;
     if (!ctx->uploaded) {
         ctx->err = "nb_frame_msaa: no state uploaded";
         return NB_ERR_STATE;
     }
-    // the rows are the eye rows and the key plane nb_frame's (one set per context), eight words a pixel for the samples
-    const size_t cells = (size_t)width * height, words = cells * NB_EYES_SAMPLES;
-    if (ids8) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, words, sizeof(uint32_t)));
-    if (depth8) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, words, sizeof(float)));
-    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
-    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
-    NB_HIP(ctx, grow_row(&ctx->frame_keys, &ctx->frame_keys_cap, words, sizeof(uint64_t)));
-    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
-    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    // the model matrices of the whole set as nb_eyes forms them
-    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    rc = grow_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
+    if (rc == NB_OK) rc = stage_frame(ctx, cam16, words);
+    if (rc == NB_OK) rc = stage_matrices(ctx, 0, 0, nullptr, nullptr);
+    if (rc != NB_OK) return rc;
     NB_HIP(ctx, nbk::launch_frame_msaa(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
                                        ctx->skin_h, ctx->frame_keys, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
                                        rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    if (ids8) NB_HIP(ctx, hipMemcpyAsync(ids8, ctx->eye_ids, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (depth8) NB_HIP(ctx, hipMemcpyAsync(depth8, ctx->eye_depth, words * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NB_OK;
+    return download_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
 }
 
 NB_EXPORT int nb_sync(nb_ctx *ctx)
@@ -2371,8 +2262,11 @@ NB_EXPORT int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, c
         g_tls_error = "nb_launch_eyes: cams_16 and inst_16n must be 16-byte aligned";
         return NB_ERR_INVALID;
     }
-    int rc = eyes_check("nb_launch_eyes", n_total, first, count, width, flags, ids, depth, cams_16, (size_t)count * 16 * sizeof(float),
-                        inst_16n, (size_t)n_total * 16 * sizeof(float), &g_tls_error);
+    const size_t cells = (size_t)count * width;
+    const ByteRange in[2] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)}};
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {nullptr, 0}, {nullptr, 0}};
+    int rc = eyes_range_check("nb_launch_eyes", n_total, first, count, width, false, flags, &g_tls_error);
+    if (rc == NB_OK) rc = outputs_check("nb_launch_eyes", out, 0x3u, kNoIdsDepth, false, in, 2, kEyesAlias, &g_tls_error);
     if (rc != NB_OK) return rc;
     if (count == 0) return NB_OK;
     rc = check_device(&g_tls_error);
@@ -2406,7 +2300,10 @@ NB_EXPORT int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t c
     }
     const ByteRange in[3] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
                              {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}};
-    int rc = eyes_colour_check("nb_launch_eyes_colour", n_total, first, count, width, flags, ids, depth, rgba, bgra8, in, 3, &g_tls_error);
+    const size_t cells = (size_t)count * width;
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = eyes_range_check("nb_launch_eyes_colour", n_total, first, count, width, false, flags, &g_tls_error);
+    if (rc == NB_OK) rc = outputs_check("nb_launch_eyes_colour", out, 0xCu, kNoColour, true, in, 3, kEyesAlias, &g_tls_error);
     if (rc != NB_OK) return rc;
     if (count == 0) return NB_OK;
     rc = check_device(&g_tls_error);
@@ -2441,7 +2338,10 @@ NB_EXPORT int nb_launch_eyes_msaa(uint32_t n_total, uint32_t first, uint32_t cou
     }
     const ByteRange in[3] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
                              {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}};
-    int rc = eyes_msaa_check("nb_launch_eyes_msaa", n_total, first, count, width, flags, ids8, depth8, rgba, bgra8, in, 3, &g_tls_error);
+    const size_t cells = (size_t)count * width, words = cells * NB_EYES_SAMPLES;
+    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = eyes_range_check("nb_launch_eyes_msaa", n_total, first, count, width, true, flags, &g_tls_error);
+    if (rc == NB_OK) rc = outputs_check("nb_launch_eyes_msaa", out, 0xFu, kNoOutputs8, true, in, 3, kEyesAlias, &g_tls_error);
     if (rc != NB_OK) return rc;
     if (count == 0) return NB_OK;
     rc = check_device(&g_tls_error);
@@ -2480,7 +2380,10 @@ NB_EXPORT int nb_launch_frame(uint32_t n_total, const void *cam_16, const void *
     }
     const ByteRange in[4] = {{cam_16, 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
                              {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}, {scratch, nb_frame_scratch_bytes(width, height)}};
-    int rc = frame_check("nb_launch_frame", width, height, flags, ids, depth, rgba, bgra8, in, 4, &g_tls_error);
+    const size_t cells = (size_t)width * height;
+    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = frame_extent_check("nb_launch_frame", width, height, false, flags, &g_tls_error);
+    if (rc == NB_OK) rc = outputs_check("nb_launch_frame", out, 0xFu, kNoOutputs, true, in, 4, kFrameAlias, &g_tls_error);
     if (rc != NB_OK) return rc;
     rc = check_device(&g_tls_error);
     if (rc != NB_OK) return rc;
@@ -2518,7 +2421,10 @@ NB_EXPORT int nb_launch_frame_msaa(uint32_t n_total, const void *cam_16, const v
     }
     const ByteRange in[4] = {{cam_16, 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
                              {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}, {scratch, nb_frame_msaa_scratch_bytes(width, height)}};
-    int rc = frame_msaa_check("nb_launch_frame_msaa", width, height, flags, ids8, depth8, rgba, bgra8, in, 4, &g_tls_error);
+    const size_t cells = (size_t)width * height, words = cells * NB_EYES_SAMPLES;
+    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = frame_extent_check("nb_launch_frame_msaa", width, height, true, flags, &g_tls_error);
+    if (rc == NB_OK) rc = outputs_check("nb_launch_frame_msaa", out, 0xFu, kNoOutputs8, true, in, 4, kFrameAlias, &g_tls_error);
     if (rc != NB_OK) return rc;
     rc = check_device(&g_tls_error);
     if (rc != NB_OK) return rc;

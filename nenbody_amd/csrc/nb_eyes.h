@@ -5,6 +5,17 @@
 
 namespace nbk {
 
+// The 8 samples of a column (rule step M1): sample k at c + kEyeSampleX16[k] / 16, the x half of Vulkan's standard 8-sample pattern.
+// nb_eyes_sample_offsets hands these out; the kernels carry them as one nibble each (nb_raster.inc), tied to this list in
+// nb_kernels.hip.
+static constexpr uint32_t kEyeSampleX16[8] = {9, 7, 13, 5, 3, 1, 11, 15};
+constexpr uint32_t sample_nibbles(const uint32_t (&v)[8])
+{
+    uint32_t p = 0;
+    for (int k = 0; k < 8; ++k) p |= v[k] << (4 * k);
+    return p;
+}
+
 // Every entity's eye view for eyes [first, first+count) of n_total bodies: cams = count cameras (eye e is
 // body first + e), inst = n_total model matrices, 16 floats each, column-major, both 16-byte aligned; ids / depth: count x width
 // each, either may be NULL.  The caller has checked the arguments (1 <= width <= NB_EYES_MAX_WIDTH, count >= 1).

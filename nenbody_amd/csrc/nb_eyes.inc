@@ -4,6 +4,8 @@
 // and which instance wrote each pixel.
 // Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit: NOT in the two units whose device code kernel_code_sha()
 // hashes (nenbody_amd/_lib.py), so the stamp of profiles/hbm_traffic.json stays that of the benchmarked kernels.  Launcher: nb_eyes.h.
+// The vertex products, the clip, the depth of a parameter, the fragment and the sRGB bytes are nb_raster.inc's, shared with the
+// frame; this file adds the projection onto a row, the column range and its lower depth bound, the cover, the shade and the kernel.
 //
 // The rule, one binary32 operation per step in the order written (-ffp-contract=off, IEEE '/'); tests/eyes_restatement.py states it
 // again in numpy and the GPU tests compare every bit:
@@ -39,40 +41,14 @@ struct EyeSeg {
     uint32_t lo, hi;         // a superset of the covered columns, [lo, hi)
 };
 
-// what the colour row needs of a clipped edge beyond EyeSeg (rule step 7): the clip parameters and the ends' w
-struct EyeTex {
-    float t_in, t_out, w0, w1;
-};
-
 // One edge P0 -> P1 of clip-space vertices (x, y, z, w): clipped, projected, its column range.  false: dropped, or covers no column.
-__device__ __forceinline__ bool eye_edge(const float *P0, const float *P1, float h, uint32_t width, EyeSeg &s, EyeTex *tx = nullptr)
+// tx: what the colour row needs of the clipped edge beyond EyeSeg.
+__device__ __forceinline__ bool eye_edge(const float *P0, const float *P1, float h, uint32_t width, EyeSeg &s, Tex *tx = nullptr)
 {
-    float t_in = 0.0f, t_out = 1.0f;
-    const float b0v[4] = {P0[2], P0[3] - P0[2], P0[3] + P0[1], P0[3] - P0[1]};   // near, far, y = -w, y = +w
-    const float b1v[4] = {P1[2], P1[3] - P1[2], P1[3] + P1[1], P1[3] - P1[1]};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float b0 = b0v[k], b1 = b1v[k];
-        if (b0 < 0.0f && b1 < 0.0f) return false;
-        if (b0 < 0.0f && b1 >= 0.0f) {
-            const float r = b0 / (b0 - b1);
-            if (r > t_in) t_in = r;        // max(t_in, r); a NaN r changes nothing
-        } else if (b1 < 0.0f && b0 >= 0.0f) {
-            const float r = b0 / (b0 - b1);
-            if (r < t_out) t_out = r;      // min(t_out, r)
-        }
-    }
-    if (t_in > t_out) return false;
     float Q0[4], Q1[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float D = P1[r] - P0[r];
-        const float a = t_in * D, b = t_out * D;
-        Q0[r] = (t_in > 0.0f) ? P0[r] + a : P0[r];
-        Q1[r] = (t_out < 1.0f) ? P0[r] + b : P1[r];
-    }
-    if (!(Q0[3] > 0.0f && Q1[3] > 0.0f)) return false;
-    if (tx) tx->t_in = t_in, tx->t_out = t_out, tx->w0 = Q0[3], tx->w1 = Q1[3];
+    Tex x;
+    if (!raster_clip(P0, P1, Q0, Q1, x)) return false;
+    if (tx) *tx = x;
     const float u0 = Q0[0] / Q0[3], u1 = Q1[0] / Q1[3];
     const float p0 = u0 * h, p1 = u1 * h;
     s.xs0 = p0 + h;
@@ -107,104 +83,51 @@ __device__ __forceinline__ void eye_cover(uint64_t *keys, uint32_t c, const EyeS
     if (!(s.xa <= xc && xc < s.xb)) return;
     if ((((uint64_t)s.klow << 32) | j) >= eye_key_load(keys + c)) return;       // nothing this segment writes here can win
     const float t = (xc - s.xs0) / s.dx;
-    const float q = t * s.dd;
-    float d = s.d0 + q;
-    if (!(d < 1.0f)) return;                                                    // Less against the clear value; NaN never passes
-    if (!(d > 0.0f)) d = 0.0f;
-    const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | j;
+    float d;
+    if (!raster_depth(s.d0, s.dd, t, d)) return;
+    const uint64_t key = raster_key(d, j);
     if (key < eye_key_load(keys + c)) __hip_atomic_fetch_min(keys + c, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-__device__ __forceinline__ float eye_bcast(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
-__device__ __forceinline__ uint32_t eye_bcast(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
+// segment s of lane src for its whole wave, its range starting at that lane's `rest`
+__device__ __forceinline__ EyeSeg eye_seg_bcast(const EyeSeg &s, uint32_t rest, int src)
+{
+    EyeSeg b;
+    b.xs0 = eye_bcast(s.xs0, src), b.xs1 = eye_bcast(s.xs1, src), b.d0 = eye_bcast(s.d0, src), b.d1 = eye_bcast(s.d1, src);
+    b.dx = eye_bcast(s.dx, src), b.dd = eye_bcast(s.dd, src), b.xa = eye_bcast(s.xa, src), b.xb = eye_bcast(s.xb, src);
+    b.klow = eye_bcast(s.klow, src), b.lo = eye_bcast(rest, src), b.hi = eye_bcast(s.hi, src);
+    return b;
+}
 
 // The colour of column c of one eye (rule steps 6-11), its key resolved: the winner's three edges again with eye_edge's own arithmetic,
 // the first that covers c, is a candidate and gives the key's depth bits, then the texture coordinate, one texel, the vignette.
 __device__ __forceinline__ float4 eye_shade(uint64_t key, uint32_t c, const float *C, const float4 *__restrict__ inst, float h,
                                             uint32_t width, const float4 *__restrict__ skin, uint32_t tw, uint32_t th)
 {
-    const float4 clear = make_float4(0.1f, 0.2f, 0.3f, 1.0f);
-    if (key == ~0ull) return clear;
+    if (key == ~0ull) return raster_clear();
     const uint32_t j = (uint32_t)key, dbits = (uint32_t)(key >> 32);
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
-    float M[16], P[3][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float4 v = inst[(size_t)j * 4 + k];
-        M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-    }
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-        float w[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-            w[r] = ((t0 + t1) + t2) + t3;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float t0 = C[r] * w[0], t1 = C[4 + r] * w[1], t2 = C[8 + r] * w[2], t3 = C[12 + r] * w[3];
-            P[v][r] = ((t0 + t1) + t2) + t3;
-        }
-    }
+    float P[3][4];
+    raster_vertices(C, inst, j, P);
     const float xc = (float)c + 0.5f;
     int edge = -1;
-    float s = 0.0f;
+    float t_at = 0.0f;
+    Tex at{};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         EyeSeg g{};
-        EyeTex x{};
+        Tex x{};
         if (edge >= 0 || !eye_edge(P[k], P[k == 2 ? 0 : k + 1], h, width, g, &x)) continue;
         if (!(g.xa <= xc && xc < g.xb)) continue;
         const float t = (xc - g.xs0) / g.dx;
-        const float q = t * g.dd;
-        float d = g.d0 + q;
-        if (!(d < 1.0f)) continue;
-        if (!(d > 0.0f)) d = 0.0f;
-        if (__float_as_uint(d) != dbits) continue;
-        edge = k;
-        const float s0 = x.t_in > 0.0f ? x.t_in : 0.0f, s1 = x.t_out < 1.0f ? x.t_out : 1.0f;   // step 7
-        const float i0 = 1.0f / x.w0, i1 = 1.0f / x.w1;
-        const float a0 = s0 * i0, a1 = s1 * i1;
-        const float da = a1 - a0, di = i1 - i0;
-        const float pa = t * da, pi = t * di;
-        const float num = a0 + pa, den = i0 + pi;
-        s = num / den;
-        if (!(s > 0.0f)) s = 0.0f;
-        if (s > 1.0f) s = 1.0f;
+        float d;
+        if (!raster_depth(g.d0, g.dd, t, d) || __float_as_uint(d) != dbits) continue;
+        edge = k, t_at = t, at = x;
     }
-    if (edge < 0) return clear;   // (the key came from one of the three: not reached)
-    const float r1 = 1.0f - s;
-    const float u = edge == 0 ? 0.0f : edge == 1 ? s : r1;       // step 8: the vertices carry (0,0), (0,1), (1,1)
-    const float v = edge == 0 ? s : edge == 1 ? 1.0f : r1;
-    float4 tex = make_float4(1.0f, 1.0f, 1.0f, 1.0f);            // no skin: 1 x 1 white
-    if (skin) {                                                  // step 9: ClampToEdge, one nearest sample
-        const float fu = u * (float)tw, fv = v * (float)th;
-        const uint32_t fx = (uint32_t)floorf(fu), fy = (uint32_t)floorf(fv);   // 0 <= u, v <= 1: in range of the conversion
-        const uint32_t ix = fx < tw - 1u ? fx : tw - 1u, iy = fy < th - 1u ? fy : th - 1u;
-        tex = skin[(size_t)iy * tw + ix];
-    }
-    const float du = u - 0.5f, dv = v - 0.5f;                    // step 10
-    const float uu = du * du, vv = dv * dv;
-    const float m2 = uu + vv;
-    const float f = 1.0f - m2;
-    return make_float4(tex.x * f, tex.y * f, tex.z * f, 1.0f);
+    if (edge < 0) return raster_clear();   // (the key came from one of the three: not reached)
+    return raster_fragment(at, edge, t_at, skin, tw, th);
 }
 
-// the sRGB byte of a linear value: the number of thresholds T[1..255] that are <= c (T strictly increasing; a NaN gives 0)
-__device__ __forceinline__ uint32_t eye_srgb_byte(const float *T, float c)
-{
-    uint32_t b = 0;
-#pragma unroll
-    for (uint32_t step = 128; step; step >>= 1)
-        if (T[b + step] <= c) b += step;     // b + step <= 255
-    return b;
-}
-
-#define NB_SRGB_TABLE static __device__ const
-#include "nb_srgb_tables.h"
-#undef NB_SRGB_TABLE
-
+#ifdef __HIPCC__
 // kColour = false: ids / depth alone (nb_eyes, nb_launch_eyes).  kColour = true: the shading pass too, while the eye's keys are still
 // in LDS -- a lane per column -- with T behind the keys in LDS (width * 8 + 1024 bytes); rgba is a float4 row, bgra8 a uint32 row.
 template <bool kColour>
@@ -223,53 +146,17 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_kernel(uint32_t n_total, uint3
     }
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const float h = (float)width * 0.5f;     // exact
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
     for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
         for (uint32_t c = tid; c < width; c += kEyeBlock) eye_keys[c] = ~0ull;
         __syncthreads();
         float C[16];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 v = cams[(size_t)e * 4 + k];
-            C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w;
-        }
+        raster_load16(cams + (size_t)e * 4, C);
         const uint32_t self = first + e;
         for (uint32_t j0 = 0; j0 < n_total; j0 += kEyeBlock) {   // every lane of the workgroup runs every pass (the wave loops below)
             const uint32_t j = j0 + tid;
             float P[3][4] = {};
             bool live = j < n_total && (see_self || j != self);
-            if (live) {
-                float M[16];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float4 v = inst[(size_t)j * 4 + k];
-                    M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-                }
-                float w[3][4];
-#pragma unroll
-                for (int v = 0; v < 3; ++v)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-                        w[v][r] = ((t0 + t1) + t2) + t3;
-                    }
-#pragma unroll
-                for (int v = 0; v < 3; ++v) {   // the near plane's row first: a body wholly behind the eye stops here
-                    const float t0 = C[2] * w[v][0], t1 = C[6] * w[v][1], t2 = C[10] * w[v][2], t3 = C[14] * w[v][3];
-                    P[v][2] = ((t0 + t1) + t2) + t3;
-                }
-                live = !(P[0][2] < 0.0f && P[1][2] < 0.0f && P[2][2] < 0.0f);
-                if (live) {
-#pragma unroll
-                    for (int v = 0; v < 3; ++v)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            if (r == 2) continue;
-                            const float t0 = C[r] * w[v][0], t1 = C[4 + r] * w[v][1], t2 = C[8 + r] * w[v][2], t3 = C[12 + r] * w[v][3];
-                            P[v][r] = ((t0 + t1) + t2) + t3;
-                        }
-                }
-            }
+            if (live) live = raster_vertices_culled(C, inst, j, P);   // a body wholly behind the eye stops at its z rows
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 EyeSeg s{};
@@ -284,10 +171,7 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_kernel(uint32_t n_total, uint3
                 while (wide) {
                     const int src = __ffsll((unsigned long long)wide) - 1;
                     wide &= wide - 1;
-                    EyeSeg b;
-                    b.xs0 = eye_bcast(s.xs0, src), b.xs1 = eye_bcast(s.xs1, src), b.d0 = eye_bcast(s.d0, src), b.d1 = eye_bcast(s.d1, src);
-                    b.dx = eye_bcast(s.dx, src), b.dd = eye_bcast(s.dd, src), b.xa = eye_bcast(s.xa, src), b.xb = eye_bcast(s.xb, src);
-                    b.klow = eye_bcast(s.klow, src), b.lo = eye_bcast(rest, src), b.hi = eye_bcast(s.hi, src);
+                    const EyeSeg b = eye_seg_bcast(s, rest, src);
                     const uint32_t bj = eye_bcast(j, src);
                     for (uint32_t c = b.lo + lane; c < b.hi; c += 64u) eye_cover(eye_keys, c, b, bj);
                 }
@@ -296,15 +180,13 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_kernel(uint32_t n_total, uint3
         __syncthreads();
         for (uint32_t c = tid; c < width; c += kEyeBlock) {   // coalesced rows of ids and depths
             const uint64_t key = eye_keys[c];
-            const bool none = key == ~0ull;
             const size_t o = (size_t)e * width + c;
-            if (ids) ids[o] = none ? 0xFFFFFFFFu : (uint32_t)key;
-            if (depth) depth[o] = none ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+            if (ids) ids[o] = raster_key_id(key);
+            if (depth) depth[o] = raster_key_depth(key);
             if constexpr (kColour) {
                 const float4 px = eye_shade(key, c, C, inst, h, width, skin, tw, th);
                 if (rgba) rgba[o] = px;
-                if (bgra8)   // bytes in memory B, G, R, A
-                    bgra8[o] = eye_srgb_byte(enc, px.z) | eye_srgb_byte(enc, px.y) << 8 | eye_srgb_byte(enc, px.x) << 16 | 0xFF000000u;
+                if (bgra8) bgra8[o] = raster_bgra8(enc, px);
             }
         }
         __syncthreads();   // the next eye re-initialises the keys
@@ -331,3 +213,4 @@ hipError_t launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, 
                        th, (float4 *)rgba, bgra8);
     return hipGetLastError();
 }
+#endif   // __HIPCC__

@@ -1,7 +1,8 @@
 // nb_eyes_msaa.inc -- every entity's eye view through 8 samples per column, resolved (DESIGN.md section 10, steps M1-M5): what the
 // reference's eye targets hold with msaa_samples = 8 (src/main.rs:652; sample_count, :263; resolve_target, :547, :611).
-// Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit after nb_frame.inc; nb_eyes.inc is used as it is (eye_edge,
-// eye_key_load, eye_bcast, eye_srgb_byte, kSrgbEncodeT) and not edited.  Launcher: nb_eyes.h.
+// Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit after nb_frame.inc.  The edge is nb_eyes.inc's (eye_edge,
+// EyeSeg, eye_key_load, eye_seg_bcast); the vertex products, the depth of a parameter, the fragment, the mean, the sample offsets and
+// the sRGB bytes are nb_raster.inc's; this file adds the cover of a sample, the 8-sample shade and the kernel.  Launcher: nb_eyes.h.
 //
 // The rule continues section 10's steps 1-11, one binary32 operation per step in the order written (-ffp-contract=off, IEEE '/');
 // tests/eyes_msaa_restatement.py states it again in numpy and the GPU tests compare every bit:
@@ -21,11 +22,7 @@
 // ends wherever the sample is covered).  Then ids8 / depth8 go out as the keys lie, and a lane per column shades: each distinct body
 // among the column's samples has its edges rebuilt once, each distinct (body, edge) is shaded once.
 
-static constexpr uint32_t kMsaaSamples = 8;
 static constexpr uint32_t kMsaaOwnCols = 4;               // columns of a span its own lane walks; the rest goes to the whole wave
-static constexpr uint32_t kMsaaOffsets16 = 0xFB135D79u;   // nibble k = 16 o_k
-
-__device__ __forceinline__ float eye_msaa_offset(uint32_t k) { return (float)((kMsaaOffsets16 >> (4u * k)) & 15u) * 0.0625f; }   // exact
 
 // sample k of column c of segment s of body j; keys: the eye's, sample-minor
 __device__ __forceinline__ void eye_msaa_cover(uint64_t *keys, uint32_t c, uint32_t k, const EyeSeg &s, uint32_t j)
@@ -35,43 +32,10 @@ __device__ __forceinline__ void eye_msaa_cover(uint64_t *keys, uint32_t c, uint3
     uint64_t *slot = keys + (c * kMsaaSamples + k);
     if ((((uint64_t)s.klow << 32) | j) >= eye_key_load(slot)) return;           // nothing this segment writes here can win
     const float t = (x - s.xs0) / s.dx;
-    const float q = t * s.dd;
-    float d = s.d0 + q;
-    if (!(d < 1.0f)) return;                                                    // Less against the clear value; NaN never passes
-    if (!(d > 0.0f)) d = 0.0f;
-    const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | j;
+    float d;
+    if (!raster_depth(s.d0, s.dd, t, d)) return;
+    const uint64_t key = raster_key(d, j);
     if (key < eye_key_load(slot)) __hip_atomic_fetch_min(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// M4: the fragment of edge `edge` (clipped: g, x) in the column whose centre is xc -- steps 7-10
-__device__ __forceinline__ float4 eye_msaa_fragment(const EyeSeg &g, const EyeTex &x, int edge, float xc, const float4 *__restrict__ skin,
-                                                    uint32_t tw, uint32_t th)
-{
-    const float t = (xc - g.xs0) / g.dx;
-    const float s0 = x.t_in > 0.0f ? x.t_in : 0.0f, s1 = x.t_out < 1.0f ? x.t_out : 1.0f;   // step 7
-    const float i0 = 1.0f / x.w0, i1 = 1.0f / x.w1;
-    const float a0 = s0 * i0, a1 = s1 * i1;
-    const float da = a1 - a0, di = i1 - i0;
-    const float pa = t * da, pi = t * di;
-    const float num = a0 + pa, den = i0 + pi;
-    float s = num / den;
-    if (!(s > 0.0f)) s = 0.0f;                                   // (also a NaN: an extrapolated t may make den zero or negative)
-    if (s > 1.0f) s = 1.0f;
-    const float r1 = 1.0f - s;
-    const float u = edge == 0 ? 0.0f : edge == 1 ? s : r1;       // step 8: the vertices carry (0,0), (0,1), (1,1)
-    const float v = edge == 0 ? s : edge == 1 ? 1.0f : r1;
-    float4 tex = make_float4(1.0f, 1.0f, 1.0f, 1.0f);            // no skin: 1 x 1 white
-    if (skin) {                                                  // step 9: ClampToEdge, one nearest sample
-        const float fu = u * (float)tw, fv = v * (float)th;
-        const uint32_t fx = (uint32_t)floorf(fu), fy = (uint32_t)floorf(fv);   // 0 <= u, v <= 1: in range of the conversion
-        const uint32_t ix = fx < tw - 1u ? fx : tw - 1u, iy = fy < th - 1u ? fy : th - 1u;
-        tex = skin[(size_t)iy * tw + ix];
-    }
-    const float du = u - 0.5f, dv = v - 0.5f;                    // step 10
-    const float uu = du * du, vv = dv * dv;
-    const float m2 = uu + vv;
-    const float f = 1.0f - m2;
-    return make_float4(tex.x * f, tex.y * f, tex.z * f, 1.0f);
 }
 
 // M3-M5 for column c of one eye, its eight keys resolved (every array index below is a constant after unrolling: no scratch)
@@ -89,41 +53,16 @@ __device__ __forceinline__ float4 eye_msaa_shade(const uint64_t *keys, uint32_t 
         ar[k] = 0.1f, ag[k] = 0.2f, ab[k] = 0.3f, aa[k] = 1.0f;  // the clear colour
     }
     const float xc = (float)c + 0.5f;
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
     while (todo) {
-        uint32_t j = 0;                                          // the body of the lowest sample left
-#pragma unroll
-        for (int k = kMsaaSamples - 1; k >= 0; --k)
-            if (todo >> k & 1u) j = id[k];
-        uint32_t mine = 0;                                       // its samples
-#pragma unroll
-        for (uint32_t k = 0; k < kMsaaSamples; ++k)
-            if ((todo >> k & 1u) && id[k] == j) mine |= 1u << k;
+        uint32_t j;                                              // the body of the lowest sample left, and its samples
+        uint32_t mine = raster_lowest_body(todo, id, j);
         todo &= ~mine;
-        float M[16], P[3][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 v = inst[(size_t)j * 4 + k];
-            M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-        }
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            float w[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-                w[r] = ((t0 + t1) + t2) + t3;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t0 = C[r] * w[0], t1 = C[4 + r] * w[1], t2 = C[8 + r] * w[2], t3 = C[12 + r] * w[3];
-                P[v][r] = ((t0 + t1) + t2) + t3;
-            }
-        }
+        float P[3][4];
+        raster_vertices(C, inst, j, P);
 #pragma unroll
         for (int e = 0; e < 3; ++e) {                            // M3: the first edge in draw order
             EyeSeg g{};
-            EyeTex x{};
+            Tex x{};
             if (!mine || !eye_edge(P[e], P[e == 2 ? 0 : e + 1], h, width, g, &x)) continue;
             uint32_t hit = 0;
 #pragma unroll
@@ -132,29 +71,22 @@ __device__ __forceinline__ float4 eye_msaa_shade(const uint64_t *keys, uint32_t 
                 const float xk = (float)c + eye_msaa_offset(k);
                 if (!(g.xa <= xk && xk < g.xb)) continue;
                 const float t = (xk - g.xs0) / g.dx;
-                const float q = t * g.dd;
-                float d = g.d0 + q;
-                if (!(d < 1.0f)) continue;
-                if (!(d > 0.0f)) d = 0.0f;
-                if (__float_as_uint(d) == db[k]) hit |= 1u << k;
+                float d;
+                if (raster_depth(g.d0, g.dd, t, d) && __float_as_uint(d) == db[k]) hit |= 1u << k;
             }
             if (!hit) continue;
             mine &= ~hit;
-            const float4 px = eye_msaa_fragment(g, x, e, xc, skin, tw, th);   // M4: once per (column, body, edge)
+            const float4 px = raster_fragment(x, e, (xc - g.xs0) / g.dx, skin, tw, th);   // M4: once per (column, body, edge)
 #pragma unroll
             for (uint32_t k = 0; k < kMsaaSamples; ++k)
                 if (hit >> k & 1u) ar[k] = px.x, ag[k] = px.y, ab[k] = px.z, aa[k] = px.w;
         }
         // (a sample left in `mine` keeps the clear colour: its key came from one of the three edges, so this is not reached)
     }
-    float4 o;                                                    // M5
-    o.x = (((ar[0] + ar[1]) + (ar[2] + ar[3])) + ((ar[4] + ar[5]) + (ar[6] + ar[7]))) * 0.125f;
-    o.y = (((ag[0] + ag[1]) + (ag[2] + ag[3])) + ((ag[4] + ag[5]) + (ag[6] + ag[7]))) * 0.125f;
-    o.z = (((ab[0] + ab[1]) + (ab[2] + ab[3])) + ((ab[4] + ab[5]) + (ab[6] + ab[7]))) * 0.125f;
-    o.w = (((aa[0] + aa[1]) + (aa[2] + aa[3])) + ((aa[4] + aa[5]) + (aa[6] + aa[7]))) * 0.125f;
-    return o;
+    return make_float4(raster_mean8(ar), raster_mean8(ag), raster_mean8(ab), raster_mean8(aa));   // M5
 }
 
+#ifdef __HIPCC__
 __global__ __launch_bounds__(kEyeBlock) void eyes_msaa_kernel(uint32_t n_total, uint32_t first, uint32_t count,
                                                              const float4 *__restrict__ cams, const float4 *__restrict__ inst,
                                                              uint32_t width, uint32_t see_self, const float4 *__restrict__ skin,
@@ -169,53 +101,17 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_msaa_kernel(uint32_t n_total, 
     enc[threadIdx.x] = kSrgbEncodeT[threadIdx.x];   // (the first barrier below orders it)
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const float h = (float)width * 0.5f;      // exact
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
     for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
         for (uint32_t i = tid; i < cells; i += kEyeBlock) msaa_keys[i] = ~0ull;
         __syncthreads();
         float C[16];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 v = cams[(size_t)e * 4 + k];
-            C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w;
-        }
+        raster_load16(cams + (size_t)e * 4, C);
         const uint32_t self = first + e;
         for (uint32_t j0 = 0; j0 < n_total; j0 += kEyeBlock) {   // every lane of the workgroup runs every pass (the wave loops below)
             const uint32_t j = j0 + tid;
             float P[3][4] = {};
             bool live = j < n_total && (see_self || j != self);
-            if (live) {
-                float M[16];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float4 v = inst[(size_t)j * 4 + k];
-                    M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-                }
-                float w[3][4];
-#pragma unroll
-                for (int v = 0; v < 3; ++v)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-                        w[v][r] = ((t0 + t1) + t2) + t3;
-                    }
-#pragma unroll
-                for (int v = 0; v < 3; ++v) {   // the near plane's row first: a body wholly behind the eye stops here
-                    const float t0 = C[2] * w[v][0], t1 = C[6] * w[v][1], t2 = C[10] * w[v][2], t3 = C[14] * w[v][3];
-                    P[v][2] = ((t0 + t1) + t2) + t3;
-                }
-                live = !(P[0][2] < 0.0f && P[1][2] < 0.0f && P[2][2] < 0.0f);
-                if (live) {
-#pragma unroll
-                    for (int v = 0; v < 3; ++v)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            if (r == 2) continue;
-                            const float t0 = C[r] * w[v][0], t1 = C[4 + r] * w[v][1], t2 = C[8 + r] * w[v][2], t3 = C[12 + r] * w[v][3];
-                            P[v][r] = ((t0 + t1) + t2) + t3;
-                        }
-                }
-            }
+            if (live) live = raster_vertices_culled(C, inst, j, P);   // a body wholly behind the eye stops at its z rows
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 EyeSeg s{};
@@ -232,10 +128,7 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_msaa_kernel(uint32_t n_total, 
                 while (wide) {
                     const int src = __ffsll((unsigned long long)wide) - 1;
                     wide &= wide - 1;
-                    EyeSeg b;
-                    b.xs0 = eye_bcast(s.xs0, src), b.xs1 = eye_bcast(s.xs1, src), b.d0 = eye_bcast(s.d0, src), b.d1 = eye_bcast(s.d1, src);
-                    b.dx = eye_bcast(s.dx, src), b.dd = eye_bcast(s.dd, src), b.xa = eye_bcast(s.xa, src), b.xb = eye_bcast(s.xb, src);
-                    b.klow = eye_bcast(s.klow, src), b.lo = eye_bcast(rest, src), b.hi = eye_bcast(s.hi, src);
+                    const EyeSeg b = eye_seg_bcast(s, rest, src);
                     const uint32_t bj = eye_bcast(j, src);
                     for (uint32_t c = b.lo + (lane >> 3); c < b.hi; c += 8u) eye_msaa_cover(msaa_keys, c, lane & 7u, b, bj);   // c < width
                 }
@@ -246,17 +139,15 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_msaa_kernel(uint32_t n_total, 
         if (ids8 || depth8)
             for (uint32_t i = tid; i < cells; i += kEyeBlock) {   // the keys as they lie: (e * width + c) * 8 + k
                 const uint64_t key = msaa_keys[i];
-                const bool none = key == ~0ull;
-                if (ids8) ids8[row + i] = none ? 0xFFFFFFFFu : (uint32_t)key;
-                if (depth8) depth8[row + i] = none ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+                if (ids8) ids8[row + i] = raster_key_id(key);
+                if (depth8) depth8[row + i] = raster_key_depth(key);
             }
         if (rgba || bgra8)
             for (uint32_t c = tid; c < width; c += kEyeBlock) {
                 const float4 px = eye_msaa_shade(msaa_keys, c, C, inst, h, width, skin, tw, th);
                 const size_t o = (size_t)e * width + c;
                 if (rgba) rgba[o] = px;
-                if (bgra8)   // bytes in memory B, G, R, A
-                    bgra8[o] = eye_srgb_byte(enc, px.z) | eye_srgb_byte(enc, px.y) << 8 | eye_srgb_byte(enc, px.x) << 16 | 0xFF000000u;
+                if (bgra8) bgra8[o] = raster_bgra8(enc, px);
             }
         __syncthreads();   // the next eye re-initialises the keys
     }
@@ -278,3 +169,4 @@ hipError_t launch_eyes_msaa(uint32_t n_total, uint32_t first, uint32_t count, co
                        (const float4 *)inst, width, flags & 1u, (const float4 *)skin, tw, th, ids8, depth8, (float4 *)rgba, bgra8);
     return hipGetLastError();
 }
+#endif   // __HIPCC__

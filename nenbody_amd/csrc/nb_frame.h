@@ -3,7 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nb_eyes.h"
+
 namespace nbk {
+
+// The y half of the 8 samples of a pixel (rule step FM1; the x half is kEyeSampleX16): sample k at r + kFrameSampleY16[k] / 16.
+static constexpr uint32_t kFrameSampleY16[8] = {5, 11, 9, 3, 13, 7, 15, 1};
 
 // The scene camera's frame of n_total bodies: cam = one camera, inst = n_total model matrices, 16 floats each,
 // column-major, both 16-byte aligned (inst may be NULL where n_total = 0); skin = tw x th linear RGBA texels, row 0 first, 16-byte

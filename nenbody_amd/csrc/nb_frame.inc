@@ -1,9 +1,9 @@
 // nb_frame.inc -- the scene camera's frame (DESIGN.md section 11): what the reference's display pass leaves in its W x H target
 // (src/main.rs:948-960: every instance's LineStrip triangle through the one scene camera, depth test Less against a clear of 1.0,
 // the skin under the vignette, the clear colour (0.1, 0.2, 0.3, 1), a Bgra8UnormSrgb target), and which instance wrote each pixel.
-// Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit right after nb_eyes.inc, whose eye_bcast, eye_srgb_byte and
-// kSrgbEncodeT it uses as they are; nb_eyes.inc itself is not edited (the clip is restated here with the y ends the frame needs).
-// Launcher: nb_frame.h.
+// Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit after nb_eyes.inc.  The vertex products, the clip, the depth of
+// a parameter, the fragment and the sRGB bytes are nb_raster.inc's, shared with the eye rows; this file adds the projection onto the
+// plane, the major axis and its range, the step, the cover, the shade and the three kernels.  Launcher: nb_frame.h.
 //
 // The rule continues section 10's, one binary32 operation per step in the order written (-ffp-contract=off, IEEE '/');
 // tests/frame_restatement.py states it again in numpy and the GPU tests compare every bit:
@@ -40,42 +40,15 @@ struct FrameSeg {
     uint32_t xmajor;     // 1: a = x, b = y; 0: a = y, b = x
 };
 
-// what the colour needs of a clipped edge beyond FrameSeg (section 10 step 7): the clip parameters and the ends' w
-struct FrameTex {
-    float t_in, t_out, w0, w1;
-};
-
 // One edge P0 -> P1 of clip-space vertices (x, y, z, w): clipped (F2), projected (F3), its major axis and range (F4).
-// false: dropped, or covers no step.
+// false: dropped, or covers no step.  tx: what the colour needs of the clipped edge beyond FrameSeg.
 __device__ __forceinline__ bool frame_edge(const float *P0, const float *P1, float h, float g, uint32_t width, uint32_t height, FrameSeg &s,
-                                           FrameTex *tx = nullptr)
+                                           Tex *tx = nullptr)
 {
-    float t_in = 0.0f, t_out = 1.0f;
-    const float b0v[4] = {P0[2], P0[3] - P0[2], P0[3] + P0[1], P0[3] - P0[1]};   // near, far, y = -w, y = +w
-    const float b1v[4] = {P1[2], P1[3] - P1[2], P1[3] + P1[1], P1[3] - P1[1]};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float b0 = b0v[k], b1 = b1v[k];
-        if (b0 < 0.0f && b1 < 0.0f) return false;
-        if (b0 < 0.0f && b1 >= 0.0f) {
-            const float r = b0 / (b0 - b1);
-            if (r > t_in) t_in = r;        // max(t_in, r); a NaN r changes nothing
-        } else if (b1 < 0.0f && b0 >= 0.0f) {
-            const float r = b0 / (b0 - b1);
-            if (r < t_out) t_out = r;      // min(t_out, r)
-        }
-    }
-    if (t_in > t_out) return false;
     float Q0[4], Q1[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float D = P1[r] - P0[r];
-        const float a = t_in * D, b = t_out * D;
-        Q0[r] = (t_in > 0.0f) ? P0[r] + a : P0[r];
-        Q1[r] = (t_out < 1.0f) ? P0[r] + b : P1[r];
-    }
-    if (!(Q0[3] > 0.0f && Q1[3] > 0.0f)) return false;
-    if (tx) tx->t_in = t_in, tx->t_out = t_out, tx->w0 = Q0[3], tx->w1 = Q1[3];
+    Tex x;
+    if (!raster_clip(P0, P1, Q0, Q1, x)) return false;
+    if (tx) *tx = x;
     const float u0 = Q0[0] / Q0[3], u1 = Q1[0] / Q1[3];
     const float v0 = Q0[1] / Q0[3], v1 = Q1[1] / Q1[3];
     const float p0 = u0 * h, p1 = u1 * h, q0 = v0 * g, q1 = v1 * g;
@@ -116,10 +89,7 @@ __device__ __forceinline__ bool frame_step(const FrameSeg &s, uint32_t m, uint32
     const float qb = t * s.db;
     const float o = s.b0 + qb;
     if (!(o >= 0.0f && o < s.blim)) return false;                               // a NaN covers nothing
-    const float qd = t * s.dd;
-    d = s.d0 + qd;
-    if (!(d < 1.0f)) return false;                                              // Less against the clear value; NaN never passes
-    if (!(d > 0.0f)) d = 0.0f;
+    if (!raster_depth(s.d0, s.dd, t, d)) return false;
     const uint32_t f = (uint32_t)o;                                             // floor(o): 0 <= o < blim <= 4096
     pixel = s.xmajor ? f * width + m : m * width + f;                           // m < hi <= the major extent: inside the plane
     return true;
@@ -134,10 +104,50 @@ __device__ __forceinline__ void frame_cover(uint64_t *keys, uint32_t m, const Fr
     float t, d;
     uint32_t pixel;
     if (!frame_step(s, m, width, t, pixel, d)) return;
-    const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | j;
+    const uint64_t key = raster_key(d, j);
     if (key < frame_key_load(keys + pixel)) __hip_atomic_fetch_min(keys + pixel, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// segment s of lane src for its whole wave, its range starting at that lane's `rest`
+__device__ __forceinline__ FrameSeg frame_seg_bcast(const FrameSeg &s, uint32_t rest, int src)
+{
+    FrameSeg b;
+    b.a0 = eye_bcast(s.a0, src), b.da = eye_bcast(s.da, src), b.b0 = eye_bcast(s.b0, src), b.db = eye_bcast(s.db, src);
+    b.d0 = eye_bcast(s.d0, src), b.dd = eye_bcast(s.dd, src), b.amin = eye_bcast(s.amin, src), b.amax = eye_bcast(s.amax, src);
+    b.blim = eye_bcast(s.blim, src), b.lo = eye_bcast(rest, src), b.hi = eye_bcast(s.hi, src), b.xmajor = eye_bcast(s.xmajor, src);
+    return b;
+}
+
+// The colour of pixel (col, row), its key resolved (F6): the winner's three edges again with frame_edge's own arithmetic, the first
+// that has this pixel among its F4 pixels, is a candidate and gives the key's depth bits, then section 10 steps 7-10.
+__device__ __forceinline__ float4 frame_shade(uint64_t key, uint32_t col, uint32_t row, const float *C, const float4 *__restrict__ inst,
+                                              uint32_t width, uint32_t height, const float4 *__restrict__ skin, uint32_t tw, uint32_t th)
+{
+    if (key == ~0ull) return raster_clear();
+    const uint32_t j = (uint32_t)key, dbits = (uint32_t)(key >> 32);
+    const float h = (float)width * 0.5f, g = (float)height * 0.5f;
+    float P[3][4];
+    raster_vertices(C, inst, j, P);
+    const uint32_t here = row * width + col;
+    int edge = -1;
+    float t_at = 0.0f;
+    Tex at{};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        FrameSeg e{};
+        Tex x{};
+        if (edge >= 0 || !frame_edge(P[k], P[k == 2 ? 0 : k + 1], h, g, width, height, e, &x)) continue;
+        float t, d;
+        uint32_t pixel;
+        if (!frame_step(e, e.xmajor ? col : row, width, t, pixel, d)) continue;
+        if (pixel != here || __float_as_uint(d) != dbits) continue;
+        edge = k, t_at = t, at = x;
+    }
+    if (edge < 0) return raster_clear();   // (the key came from one of the three: not reached)
+    return raster_fragment(at, edge, t_at, skin, tw, th);
+}
+
+#ifdef __HIPCC__
 __global__ __launch_bounds__(kFrameBlock) void frame_clear_kernel(uint64_t *__restrict__ keys, uint32_t pixels)
 {
     const uint32_t p = blockIdx.x * (uint32_t)kFrameBlock + threadIdx.x;
@@ -150,48 +160,12 @@ __global__ __launch_bounds__(kFrameBlock) void frame_edges_kernel(uint32_t n_tot
 {
     const uint32_t lane = threadIdx.x & 63u;
     const float h = (float)width * 0.5f, g = (float)height * 0.5f;   // exact
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
     float C[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float4 v = cam[k];
-        C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w;
-    }
+    raster_load16(cam, C);
     const uint32_t j = blockIdx.x * (uint32_t)kFrameBlock + threadIdx.x;
     float P[3][4] = {};
     bool live = j < n_total;   // (no lane leaves early: every lane of a wave runs the wave loops below)
-    if (live) {
-        float M[16];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 v = inst[(size_t)j * 4 + k];
-            M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-        }
-        float w[3][4];
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-                w[v][r] = ((t0 + t1) + t2) + t3;
-            }
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {   // the near plane's row first: a body wholly behind the camera stops here
-            const float t0 = C[2] * w[v][0], t1 = C[6] * w[v][1], t2 = C[10] * w[v][2], t3 = C[14] * w[v][3];
-            P[v][2] = ((t0 + t1) + t2) + t3;
-        }
-        live = !(P[0][2] < 0.0f && P[1][2] < 0.0f && P[2][2] < 0.0f);
-        if (live) {
-#pragma unroll
-            for (int v = 0; v < 3; ++v)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (r == 2) continue;
-                    const float t0 = C[r] * w[v][0], t1 = C[4 + r] * w[v][1], t2 = C[8 + r] * w[v][2], t3 = C[12 + r] * w[v][3];
-                    P[v][r] = ((t0 + t1) + t2) + t3;
-                }
-        }
-    }
+    if (live) live = raster_vertices_culled(C, inst, j, P);   // a body wholly behind the camera stops at its z rows
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         FrameSeg s{};
@@ -206,85 +180,11 @@ __global__ __launch_bounds__(kFrameBlock) void frame_edges_kernel(uint32_t n_tot
         while (wide) {
             const int src = __ffsll((unsigned long long)wide) - 1;
             wide &= wide - 1;
-            FrameSeg b;
-            b.a0 = eye_bcast(s.a0, src), b.da = eye_bcast(s.da, src), b.b0 = eye_bcast(s.b0, src), b.db = eye_bcast(s.db, src);
-            b.d0 = eye_bcast(s.d0, src), b.dd = eye_bcast(s.dd, src), b.amin = eye_bcast(s.amin, src), b.amax = eye_bcast(s.amax, src);
-            b.blim = eye_bcast(s.blim, src), b.lo = eye_bcast(rest, src), b.hi = eye_bcast(s.hi, src), b.xmajor = eye_bcast(s.xmajor, src);
+            const FrameSeg b = frame_seg_bcast(s, rest, src);
             const uint32_t bj = eye_bcast(j, src);
             for (uint32_t m = b.lo + lane; m < b.hi; m += 64u) frame_cover(keys, m, b, bj, width);
         }
     }
-}
-
-// The colour of pixel (col, row), its key resolved (F6): the winner's three edges again with frame_edge's own arithmetic, the first
-// that has this pixel among its F4 pixels, is a candidate and gives the key's depth bits, then section 10 steps 7-10.
-__device__ __forceinline__ float4 frame_shade(uint64_t key, uint32_t col, uint32_t row, const float *C, const float4 *__restrict__ inst,
-                                              uint32_t width, uint32_t height, const float4 *__restrict__ skin, uint32_t tw, uint32_t th)
-{
-    const float4 clear = make_float4(0.1f, 0.2f, 0.3f, 1.0f);
-    if (key == ~0ull) return clear;
-    const uint32_t j = (uint32_t)key, dbits = (uint32_t)(key >> 32);
-    const float h = (float)width * 0.5f, g = (float)height * 0.5f;
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
-    float M[16], P[3][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float4 v = inst[(size_t)j * 4 + k];
-        M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-    }
-#pragma unroll
-    for (int v = 0; v < 3; ++v) {
-        float w[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-            w[r] = ((t0 + t1) + t2) + t3;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float t0 = C[r] * w[0], t1 = C[4 + r] * w[1], t2 = C[8 + r] * w[2], t3 = C[12 + r] * w[3];
-            P[v][r] = ((t0 + t1) + t2) + t3;
-        }
-    }
-    const uint32_t here = row * width + col;
-    int edge = -1;
-    float s = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        FrameSeg e{};
-        FrameTex x{};
-        if (edge >= 0 || !frame_edge(P[k], P[k == 2 ? 0 : k + 1], h, g, width, height, e, &x)) continue;
-        float t, d;
-        uint32_t pixel;
-        if (!frame_step(e, e.xmajor ? col : row, width, t, pixel, d)) continue;
-        if (pixel != here || __float_as_uint(d) != dbits) continue;
-        edge = k;
-        const float s0 = x.t_in > 0.0f ? x.t_in : 0.0f, s1 = x.t_out < 1.0f ? x.t_out : 1.0f;   // step 7
-        const float i0 = 1.0f / x.w0, i1 = 1.0f / x.w1;
-        const float a0 = s0 * i0, a1 = s1 * i1;
-        const float da = a1 - a0, di = i1 - i0;
-        const float pa = t * da, pi = t * di;
-        const float num = a0 + pa, den = i0 + pi;
-        s = num / den;
-        if (!(s > 0.0f)) s = 0.0f;
-        if (s > 1.0f) s = 1.0f;
-    }
-    if (edge < 0) return clear;   // (the key came from one of the three: not reached)
-    const float r1 = 1.0f - s;
-    const float u = edge == 0 ? 0.0f : edge == 1 ? s : r1;       // step 8: the vertices carry (0,0), (0,1), (1,1)
-    const float v = edge == 0 ? s : edge == 1 ? 1.0f : r1;
-    float4 tex = make_float4(1.0f, 1.0f, 1.0f, 1.0f);            // no skin: 1 x 1 white
-    if (skin) {                                                  // step 9: ClampToEdge, one nearest sample
-        const float fu = u * (float)tw, fv = v * (float)th;
-        const uint32_t fx = (uint32_t)floorf(fu), fy = (uint32_t)floorf(fv);   // 0 <= u, v <= 1: in range of the conversion
-        const uint32_t ix = fx < tw - 1u ? fx : tw - 1u, iy = fy < th - 1u ? fy : th - 1u;
-        tex = skin[(size_t)iy * tw + ix];
-    }
-    const float du = u - 0.5f, dv = v - 0.5f;                    // step 10
-    const float uu = du * du, vv = dv * dv;
-    const float m2 = uu + vv;
-    const float f = 1.0f - m2;
-    return make_float4(tex.x * f, tex.y * f, tex.z * f, 1.0f);
 }
 
 __global__ __launch_bounds__(kFrameBlock) void frame_resolve_kernel(const float4 *__restrict__ cam, const float4 *__restrict__ inst,
@@ -301,21 +201,15 @@ __global__ __launch_bounds__(kFrameBlock) void frame_resolve_kernel(const float4
     const uint32_t p = blockIdx.x * (uint32_t)kFrameBlock + threadIdx.x;
     if (p >= pixels) return;
     const uint64_t key = keys[p];
-    const bool none = key == ~0ull;
-    if (ids) ids[p] = none ? 0xFFFFFFFFu : (uint32_t)key;
-    if (depth) depth[p] = none ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+    if (ids) ids[p] = raster_key_id(key);
+    if (depth) depth[p] = raster_key_depth(key);
     if (!rgba && !bgra8) return;
     float C[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float4 v = cam[k];
-        C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w;
-    }
+    raster_load16(cam, C);
     const uint32_t row = p / width, col = p - row * width;
     const float4 px = frame_shade(key, col, row, C, inst, width, height, skin, tw, th);
     if (rgba) rgba[p] = px;
-    if (bgra8)   // bytes in memory B, G, R, A
-        bgra8[p] = eye_srgb_byte(enc, px.z) | eye_srgb_byte(enc, px.y) << 8 | eye_srgb_byte(enc, px.x) << 16 | 0xFF000000u;
+    if (bgra8) bgra8[p] = raster_bgra8(enc, px);
 }
 
 hipError_t launch_frame(uint32_t n_total, const float *cam, const float *inst, uint32_t width, uint32_t height, const float *skin,
@@ -331,3 +225,4 @@ hipError_t launch_frame(uint32_t n_total, const float *cam, const float *inst, u
                        (const uint64_t *)keys, (const float4 *)skin, tw, th, ids, depth, (float4 *)rgba, bgra8);
     return hipGetLastError();
 }
+#endif   // __HIPCC__

@@ -1,9 +1,10 @@
 // nb_frame_msaa.inc -- the scene camera's frame through 8 samples per pixel, resolved (DESIGN.md section 11.1, steps FM1-FM5): what
 // the reference's display pass leaves in its target with msaa_samples = 8 (src/main.rs:652; the display target, :685-690; its pass
 // resolving into the swapchain image, :545-548, :948-960).
-// Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit after nb_eyes_msaa.inc.  nb_eyes.inc, nb_frame.inc and
-// nb_eyes_msaa.inc are used as they are (frame_edge, FrameSeg, FrameTex, frame_key_load, frame_clear_kernel; eye_bcast, eye_srgb_byte,
-// kSrgbEncodeT; eye_msaa_offset, eye_msaa_fragment) and not edited.  Launcher: nb_frame.h.
+// Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit after nb_eyes_msaa.inc.  The edge and the clear pass are
+// nb_frame.inc's (frame_edge, FrameSeg, frame_key_load, frame_seg_bcast, frame_clear_kernel); the vertex products, the depth of a
+// parameter, the fragment, the mean, the sample offsets and the sRGB bytes are nb_raster.inc's; this file adds the step and the cover
+// of a sample, the 8-sample shade and the two kernels.  Launcher: nb_frame.h.
 //
 // The rule continues section 11's F1-F6, one binary32 operation per step in the order written (-ffp-contract=off, IEEE '/');
 // tests/frame_msaa_restatement.py states it again in numpy and the GPU tests compare every bit:
@@ -29,9 +30,6 @@
 // has its edges rebuilt once through frame_edge, each distinct (body, edge) is shaded once at the pixel centre.
 
 static constexpr uint32_t kFrameMsaaOwnSteps = 2;            // major-axis steps of an edge its own lane walks (x 8 samples each)
-static constexpr uint32_t kFrameMsaaOffsetsY16 = 0x1F7D39B5u;   // nibble k = 16 oy_k (ox: kMsaaOffsets16)
-
-__device__ __forceinline__ float frame_msaa_offset_y(uint32_t k) { return (float)((kFrameMsaaOffsetsY16 >> (4u * k)) & 15u) * 0.0625f; }   // exact
 
 // Sample k of step m of segment s (FM2): its parameter, the pixel it belongs to (an index into the H x W plane), its depth.
 // false: no pixel, or no candidate.
@@ -47,10 +45,7 @@ __device__ __forceinline__ bool frame_msaa_step(const FrameSeg &s, uint32_t m, u
     const float q = 0.5f - ob;                                                  // exact
     const float e = o + q;
     if (!(e >= 0.0f && e < s.blim)) return false;                               // a NaN covers nothing
-    const float qd = t * s.dd;
-    d = s.d0 + qd;
-    if (!(d < 1.0f)) return false;                                              // Less against the clear value; NaN never passes
-    if (!(d > 0.0f)) d = 0.0f;
+    if (!raster_depth(s.d0, s.dd, t, d)) return false;
     const uint32_t f = (uint32_t)e;                                             // floor(e): 0 <= e < blim <= 2048
     pixel = s.xmajor ? f * width + m : m * width + f;                           // m < hi <= the major extent: inside the plane
     return true;
@@ -63,7 +58,7 @@ __device__ __forceinline__ void frame_msaa_cover(uint64_t *keys, uint32_t m, uin
     uint32_t pixel;
     if (!frame_msaa_step(s, m, k, width, t, pixel, d)) return;
     uint64_t *slot = keys + ((size_t)pixel * kMsaaSamples + k);
-    const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | j;
+    const uint64_t key = raster_key(d, j);
     if (key < frame_key_load(slot)) __hip_atomic_fetch_min(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -84,41 +79,16 @@ __device__ __forceinline__ float4 frame_msaa_shade(const uint64_t *keys8, uint32
     }
     const float h = (float)width * 0.5f, g = (float)height * 0.5f;
     const uint32_t here = row * width + col;
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
     while (todo) {
-        uint32_t j = 0;                                          // the body of the lowest sample left
-#pragma unroll
-        for (int k = kMsaaSamples - 1; k >= 0; --k)
-            if (todo >> k & 1u) j = id[k];
-        uint32_t mine = 0;                                       // its samples
-#pragma unroll
-        for (uint32_t k = 0; k < kMsaaSamples; ++k)
-            if ((todo >> k & 1u) && id[k] == j) mine |= 1u << k;
+        uint32_t j;                                              // the body of the lowest sample left, and its samples
+        uint32_t mine = raster_lowest_body(todo, id, j);
         todo &= ~mine;
-        float M[16], P[3][4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 v = inst[(size_t)j * 4 + k];
-            M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-        }
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            float w[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-                w[r] = ((t0 + t1) + t2) + t3;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t0 = C[r] * w[0], t1 = C[4 + r] * w[1], t2 = C[8 + r] * w[2], t3 = C[12 + r] * w[3];
-                P[v][r] = ((t0 + t1) + t2) + t3;
-            }
-        }
+        float P[3][4];
+        raster_vertices(C, inst, j, P);
 #pragma unroll
         for (int e = 0; e < 3; ++e) {                            // FM3: the first edge in draw order
             FrameSeg s{};
-            FrameTex x{};
+            Tex x{};
             if (!mine || !frame_edge(P[e], P[e == 2 ? 0 : e + 1], h, g, width, height, s, &x)) continue;
             const uint32_t m = s.xmajor ? col : row;
             uint32_t hit = 0;
@@ -132,73 +102,30 @@ __device__ __forceinline__ float4 frame_msaa_shade(const uint64_t *keys8, uint32
             }
             if (!hit) continue;
             mine &= ~hit;
-            EyeSeg cs{};                                         // FM4: once per (pixel, body, edge), at the centre of step m
-            EyeTex cx{};
-            cs.xs0 = s.a0, cs.dx = s.da;
-            cx.t_in = x.t_in, cx.t_out = x.t_out, cx.w0 = x.w0, cx.w1 = x.w1;
-            const float4 px = eye_msaa_fragment(cs, cx, e, (float)m + 0.5f, skin, tw, th);
+            const float mc = (float)m + 0.5f;                    // FM4: once per (pixel, body, edge), at the centre of step m
+            const float4 px = raster_fragment(x, e, (mc - s.a0) / s.da, skin, tw, th);
 #pragma unroll
             for (uint32_t k = 0; k < kMsaaSamples; ++k)
                 if (hit >> k & 1u) ar[k] = px.x, ag[k] = px.y, ab[k] = px.z, aa[k] = px.w;
         }
         // (a sample left in `mine` keeps the clear colour: its key came from one of the three edges, so this is not reached)
     }
-    float4 o;                                                    // FM5
-    o.x = (((ar[0] + ar[1]) + (ar[2] + ar[3])) + ((ar[4] + ar[5]) + (ar[6] + ar[7]))) * 0.125f;
-    o.y = (((ag[0] + ag[1]) + (ag[2] + ag[3])) + ((ag[4] + ag[5]) + (ag[6] + ag[7]))) * 0.125f;
-    o.z = (((ab[0] + ab[1]) + (ab[2] + ab[3])) + ((ab[4] + ab[5]) + (ab[6] + ab[7]))) * 0.125f;
-    o.w = (((aa[0] + aa[1]) + (aa[2] + aa[3])) + ((aa[4] + aa[5]) + (aa[6] + aa[7]))) * 0.125f;
-    return o;
+    return make_float4(raster_mean8(ar), raster_mean8(ag), raster_mean8(ab), raster_mean8(aa));   // FM5
 }
 
+#ifdef __HIPCC__
 __global__ __launch_bounds__(kFrameBlock) void frame_msaa_edges_kernel(uint32_t n_total, const float4 *__restrict__ cam,
                                                                        const float4 *__restrict__ inst, uint32_t width, uint32_t height,
                                                                        uint64_t *__restrict__ keys)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const float h = (float)width * 0.5f, g = (float)height * 0.5f;   // exact
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
     float C[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float4 v = cam[k];
-        C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w;
-    }
+    raster_load16(cam, C);
     const uint32_t j = blockIdx.x * (uint32_t)kFrameBlock + threadIdx.x;
     float P[3][4] = {};
     bool live = j < n_total;   // (no lane leaves early: every lane of a wave runs the wave loops below)
-    if (live) {
-        float M[16];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float4 v = inst[(size_t)j * 4 + k];
-            M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w;
-        }
-        float w[3][4];
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f;
-                w[v][r] = ((t0 + t1) + t2) + t3;
-            }
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {   // the near plane's row first: a body wholly behind the camera stops here
-            const float t0 = C[2] * w[v][0], t1 = C[6] * w[v][1], t2 = C[10] * w[v][2], t3 = C[14] * w[v][3];
-            P[v][2] = ((t0 + t1) + t2) + t3;
-        }
-        live = !(P[0][2] < 0.0f && P[1][2] < 0.0f && P[2][2] < 0.0f);
-        if (live) {
-#pragma unroll
-            for (int v = 0; v < 3; ++v)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (r == 2) continue;
-                    const float t0 = C[r] * w[v][0], t1 = C[4 + r] * w[v][1], t2 = C[8 + r] * w[v][2], t3 = C[12 + r] * w[v][3];
-                    P[v][r] = ((t0 + t1) + t2) + t3;
-                }
-        }
-    }
+    if (live) live = raster_vertices_culled(C, inst, j, P);   // a body wholly behind the camera stops at its z rows
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         FrameSeg s{};
@@ -215,10 +142,7 @@ __global__ __launch_bounds__(kFrameBlock) void frame_msaa_edges_kernel(uint32_t 
         while (wide) {
             const int src = __ffsll((unsigned long long)wide) - 1;
             wide &= wide - 1;
-            FrameSeg b;
-            b.a0 = eye_bcast(s.a0, src), b.da = eye_bcast(s.da, src), b.b0 = eye_bcast(s.b0, src), b.db = eye_bcast(s.db, src);
-            b.d0 = eye_bcast(s.d0, src), b.dd = eye_bcast(s.dd, src), b.amin = eye_bcast(s.amin, src), b.amax = eye_bcast(s.amax, src);
-            b.blim = eye_bcast(s.blim, src), b.lo = eye_bcast(rest, src), b.hi = eye_bcast(s.hi, src), b.xmajor = eye_bcast(s.xmajor, src);
+            const FrameSeg b = frame_seg_bcast(s, rest, src);
             const uint32_t bj = eye_bcast(j, src);
             for (uint32_t m = b.lo + (lane >> 3); m < b.hi; m += 8u) frame_msaa_cover(keys, m, lane & 7u, b, bj, width);   // m < the major extent
         }
@@ -244,9 +168,8 @@ __global__ __launch_bounds__(kFrameBlock) void frame_msaa_resolve_kernel(const f
             const uint32_t i = base + q * (uint32_t)kFrameBlock + threadIdx.x;
             if (i < cells) {
                 const uint64_t key = keys[i];
-                const bool none = key == ~0ull;
-                if (ids8) ids8[i] = none ? 0xFFFFFFFFu : (uint32_t)key;
-                if (depth8) depth8[i] = none ? 1.0f : __uint_as_float((uint32_t)(key >> 32));
+                if (ids8) ids8[i] = raster_key_id(key);
+                if (depth8) depth8[i] = raster_key_depth(key);
             }
         }
     }
@@ -256,16 +179,11 @@ __global__ __launch_bounds__(kFrameBlock) void frame_msaa_resolve_kernel(const f
 #pragma unroll
     for (uint32_t k = 0; k < kMsaaSamples; ++k) k8[k] = keys[(size_t)p * kMsaaSamples + k];
     float C[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float4 v = cam[k];
-        C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w;
-    }
+    raster_load16(cam, C);
     const uint32_t row = p / width, col = p - row * width;
     const float4 px = frame_msaa_shade(k8, col, row, C, inst, width, height, skin, tw, th);
     if (rgba) rgba[p] = px;
-    if (bgra8)   // bytes in memory B, G, R, A
-        bgra8[p] = eye_srgb_byte(enc, px.z) | eye_srgb_byte(enc, px.y) << 8 | eye_srgb_byte(enc, px.x) << 16 | 0xFF000000u;
+    if (bgra8) bgra8[p] = raster_bgra8(enc, px);
 }
 
 hipError_t launch_frame_msaa(uint32_t n_total, const float *cam, const float *inst, uint32_t width, uint32_t height, const float *skin,
@@ -282,3 +200,4 @@ hipError_t launch_frame_msaa(uint32_t n_total, const float *cam, const float *in
                        (float4 *)rgba, bgra8);
     return hipGetLastError();
 }
+#endif   // __HIPCC__

@@ -38,6 +38,7 @@
 //   nb_nbody_fast.inc    FAST kernels + fixed-order combine               (this unit)
 //   nb_aux.inc           model matrices, cameras, random walk, self-test  (this unit)
 //   nb_boids.inc         boids controller, one-lane and producer/consumer (SLP-off unit)
+//   nb_raster.inc        what the four files below share: vertices, clip, depth, fragment, sRGB bytes (SLP-off unit; device functions only)
 //   nb_eyes.inc          every entity's eye view: depth + entity id per column (SLP-off unit; its own launcher, nb_eyes.h)
 //   nb_frame.inc         the scene camera's frame: ids, depth and colour per pixel (SLP-off unit; its own launcher, nb_frame.h)
 //   nb_eyes_msaa.inc     the eye view through 8 samples per column, resolved (SLP-off unit; launcher in nb_eyes.h)
@@ -51,6 +52,10 @@
 #include <type_traits>
 
 #include "nb_kernels.h"
+#ifdef NBK_NOSLP_TU
+#include "nb_eyes.h"
+#include "nb_frame.h"
+#endif
 
 namespace nbk {
 
@@ -66,10 +71,13 @@ static constexpr int kWaves = kBlock / 64;
 #include "nb_nbody_ring.inc"  // the same on a shard of a multi-GPU job: the blocks on a ring, each against the half that follows it
 #elif defined(NBK_NOSLP_TU)
 #include "nb_boids.inc"
-#include "nb_eyes.inc"        // every entity's eye view: outside the two units kernel_code_sha() stamps the evidence with
-#include "nb_frame.inc"       // the scene camera's frame: likewise; uses nb_eyes.inc's broadcast and sRGB helpers
-#include "nb_eyes_msaa.inc"   // the eye view through 8 samples per column: likewise; uses nb_eyes.inc's edge, broadcast and sRGB helpers
-#include "nb_frame_msaa.inc"  // the frame through 8 samples per pixel: likewise; uses nb_frame.inc's edge and clear, nb_eyes_msaa.inc's fragment
+#include "nb_raster.inc"      // the rule the four files below share, once: outside the two units kernel_code_sha() stamps the evidence with
+static_assert(kMsaaOffsets16 == sample_nibbles(kEyeSampleX16) && kFrameMsaaOffsetsY16 == sample_nibbles(kFrameSampleY16),
+              "the kernels' sample offsets are the ones nb_eyes_sample_offsets / nb_frame_sample_offsets hand out");
+#include "nb_eyes.inc"        // every entity's eye view: likewise
+#include "nb_frame.inc"       // the scene camera's frame: likewise
+#include "nb_eyes_msaa.inc"   // the eye view through 8 samples per column: likewise; uses nb_eyes.inc's edge
+#include "nb_frame_msaa.inc"  // the frame through 8 samples per pixel: likewise; uses nb_frame.inc's edge and clear
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

@@ -1,9 +1,10 @@
-// eyes_msaa_host.cpp -- the device functions of the 8-sample eye kernel (eye_msaa_cover, eye_msaa_shade, eye_msaa_fragment of
-// nb_eyes_msaa.inc, with eye_edge and eye_srgb_byte of nb_eyes.inc) compiled for the HOST and driven sample by sample, so that
-// tests/test_eyes_msaa_host.py can compare their arithmetic with the rule's restatement without a GPU.  The test cuts the two
-// includes off before their kernels (which need a device) into eyes_msaa_parts.inc; the few device builtins they use are stated
-// below.  Build with -ffp-contract=off -msse2 -mfpmath=sse: one binary32 operation per step, as on the device.
-// usage: eyes_msaa_host E N FIRST WIDTH SEE_SELF TW TH CAMS.bin INST.bin SKIN.bin OUT.bin   (TW = 0: the white skin)
+// eyes_msaa_host.cpp -- the device functions of the eye kernels (eye_msaa_cover and eye_msaa_shade of nb_eyes_msaa.inc, eye_edge,
+// eye_cover and eye_shade of nb_eyes.inc, the vertices, clip, depth, fragment and sRGB bytes of nb_raster.inc) compiled for the HOST
+// and driven sample by sample, so that tests/test_eyes_msaa_host.py can compare their arithmetic with the rule's restatements
+// without a GPU.  The three files are included whole (their kernels and launchers sit behind __HIPCC__); the few device builtins
+// they use are stated below.  Build with -ffp-contract=off -msse2 -mfpmath=sse: one binary32 operation per step, as on the device.
+// usage: eyes_msaa_host E N FIRST WIDTH SEE_SELF TW TH CAMS.bin INST.bin SKIN.bin OUT.bin [one]   (TW = 0: the white skin;
+// one: the one-sample rows -- keys by eye_cover, colour by eye_shade -- where the default is the 8-sample ones)
 #include <cstdint>
 #include <cmath>
 #include <cstring>
@@ -23,7 +24,9 @@ static inline float __int_as_float(int u) { float f; memcpy(&f, &u, 4); return f
 static inline uint64_t __hip_atomic_load(uint64_t *p, int, int) { return *p; }
 static inline void __hip_atomic_fetch_min(uint64_t *p, uint64_t v, int, int) { if (v < *p) *p = v; }
 static inline int __builtin_amdgcn_readlane(int v, int) { return v; }
-#include "eyes_msaa_parts.inc"
+#include "nb_raster.inc"
+#include "nb_eyes.inc"
+#include "nb_eyes_msaa.inc"
 static std::vector<char> slurp(const char *p) { FILE *f = fopen(p, "rb"); if (!f) exit(9); fseek(f, 0, SEEK_END); long n = ftell(f); fseek(f, 0, SEEK_SET); std::vector<char> b(n); if (fread(b.data(), 1, n, f) != (size_t)n) exit(9); fclose(f); return b; }
 int main(int argc, char **argv)
 {
@@ -33,34 +36,33 @@ int main(int argc, char **argv)
     std::vector<char> sb; if (tw) sb = slurp(argv[10]);
     const float4 *cams = (const float4 *)cb.data(), *inst = (const float4 *)ib.data(), *skin = tw ? (const float4 *)sb.data() : nullptr;
     const float h = (float)width * 0.5f;
-    const float ax[3] = {-1.0f, 1.0f, -1.0f}, ay[3] = {-1.0f, 0.0f, 1.0f};
+    const bool one = argc > 12 && !strcmp(argv[12], "one");
+    const uint32_t samples = one ? 1 : 8;
     FILE *out = fopen(argv[11], "wb");
-    std::vector<uint64_t> keys(width * 8);
-    std::vector<uint32_t> ids8(width * 8), bg(width); std::vector<float> d8(width * 8); std::vector<float4> rg(width);
+    std::vector<uint64_t> keys(width * samples);
+    std::vector<uint32_t> ids8(width * samples), bg(width); std::vector<float> d8(width * samples); std::vector<float4> rg(width);
     for (uint32_t e = 0; e < E; ++e) {
         for (auto &k : keys) k = ~0ull;
         float C[16];
-        for (int k = 0; k < 4; ++k) { const float4 v = cams[e * 4 + k]; C[4 * k] = v.x, C[4 * k + 1] = v.y, C[4 * k + 2] = v.z, C[4 * k + 3] = v.w; }
+        raster_load16(cams + (size_t)e * 4, C);
         for (uint32_t j = 0; j < n; ++j) {
             if (!see_self && j == first + e) continue;
-            float M[16], P[3][4];
-            for (int k = 0; k < 4; ++k) { const float4 v = inst[j * 4 + k]; M[4 * k] = v.x, M[4 * k + 1] = v.y, M[4 * k + 2] = v.z, M[4 * k + 3] = v.w; }
-            for (int v = 0; v < 3; ++v) {
-                float w[4];
-                for (int r = 0; r < 4; ++r) { const float t0 = M[r] * ax[v], t1 = M[4 + r] * ay[v], t2 = M[8 + r] * 0.0f, t3 = M[12 + r] * 1.0f; w[r] = ((t0 + t1) + t2) + t3; }
-                for (int r = 0; r < 4; ++r) { const float t0 = C[r] * w[0], t1 = C[4 + r] * w[1], t2 = C[8 + r] * w[2], t3 = C[12 + r] * w[3]; P[v][r] = ((t0 + t1) + t2) + t3; }
-            }
+            float P[3][4];
+            if (!raster_vertices_culled(C, inst, j, P)) continue;   // as eyes_kernel: the z row first, the cull
             for (int k = 0; k < 3; ++k) {
                 EyeSeg s{};
                 if (!eye_edge(P[k], P[k == 2 ? 0 : k + 1], h, width, s)) continue;
-                for (uint32_t c = s.lo; c < s.hi; ++c) for (uint32_t m = 0; m < 8; ++m) eye_msaa_cover(keys.data(), c, m, s, j);
+                for (uint32_t c = s.lo; c < s.hi; ++c) {
+                    if (one) eye_cover(keys.data(), c, s, j);
+                    else for (uint32_t m = 0; m < 8; ++m) eye_msaa_cover(keys.data(), c, m, s, j);
+                }
             }
         }
-        for (uint32_t i = 0; i < width * 8; ++i) { const bool none = keys[i] == ~0ull; ids8[i] = none ? 0xFFFFFFFFu : (uint32_t)keys[i]; d8[i] = none ? 1.0f : __uint_as_float((uint32_t)(keys[i] >> 32)); }
+        for (uint32_t i = 0; i < width * samples; ++i) { ids8[i] = raster_key_id(keys[i]); d8[i] = raster_key_depth(keys[i]); }
         for (uint32_t c = 0; c < width; ++c) {
-            const float4 px = eye_msaa_shade(keys.data(), c, C, inst, h, width, skin, tw, th);
+            const float4 px = one ? eye_shade(keys[c], c, C, inst, h, width, skin, tw, th) : eye_msaa_shade(keys.data(), c, C, inst, h, width, skin, tw, th);
             rg[c] = px;
-            bg[c] = eye_srgb_byte(kSrgbEncodeT, px.z) | eye_srgb_byte(kSrgbEncodeT, px.y) << 8 | eye_srgb_byte(kSrgbEncodeT, px.x) << 16 | 0xFF000000u;
+            bg[c] = raster_bgra8(kSrgbEncodeT, px);
         }
         fwrite(ids8.data(), 4, ids8.size(), out); fwrite(d8.data(), 4, d8.size(), out); fwrite(rg.data(), 16, rg.size(), out); fwrite(bg.data(), 4, bg.size(), out);
     }
