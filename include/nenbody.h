@@ -207,6 +207,34 @@ int nb_eyes_sample_offsets(float *out8);   /* host arithmetic, no device */
 int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width, uint32_t flags,
                  uint32_t *ids8, float *depth8, float *rgba, uint32_t *bgra8);
 
+/* What a controller makes of the eye rows.  The SEEN SET of an eye is formed from its resolved row (ids[c],
+ * depth[c] as nb_eyes leaves them): the values other than NB_EYES_NONE that occur in ids, compared as unsigned 32-bit numbers.
+ *   seen_count[e]          their number, at most width
+ *   seen_ids[e*width + k]  k < count: the members in ascending order; the other slots read NB_EYES_NONE
+ *   seen_depth[...]        the value whose bit pattern is the unsigned minimum of the bit patterns of depth[c] over the member's
+ *                          columns: on a resolved row the nearest depth at which e sees the body; the other slots read 1.0f
+ *   seen_cols[...]         the number of columns holding the member; the other slots read 0
+ * A function of the row alone: the same bits from run to run.
+ * nb_eyes_seen: the seen sets of the eyes of bodies [first, first+count) of the context's current state, rows as nb_eyes forms them
+ * (flags may be NB_EYES_SEE_SELF).  Host outputs: seen_count count words, the others count*width; any may be NULL, not all.
+ * count = 0 is a no-op. */
+int nb_eyes_seen(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width, uint32_t flags,
+                 uint32_t *seen_count, uint32_t *seen_ids, float *seen_depth, uint32_t *seen_cols);
+
+/* k applications of update_instance_boids (src/main.rs:443-526) restricted to what each entity SEES, device-resident and
+ * asynchronous on the context's stream; may be mixed freely with the other steps.  One application to the state (P, V):
+ *   V1  the eye rows of every body as nb_eyes forms them from (P, V) with flags = 0 (cameras from up_xyz, cp16 as nb_cameras; an eye
+ *       does not see its own body), and their seen sets
+ *   V2  body n runs the three folds of main.rs:471-504 with the same operations, operand order and predicates over the entries of
+ *       its seen list in list order (ascending body index) instead of over old_positions / old_velocities .iter().enumerate()
+ *   V3  the epilogue of main.rs:506-521, unchanged
+ * A body that sees nobody gets velocity (0, 0, 0) and stays where it is -- the reference's law applied to an empty fold.
+ * Eyes are processed `batch` at a time, which bounds the device rows and lists; every batch size gives the same bits.  batch = 0:
+ * the library's choice, the most eyes whose id rows and lists (8 bytes a column, 4 bytes of count an eye) stay together at or below
+ * 64 MiB -- 8 188 at width 1024.  params == NULL -> defaults.  1 <= width <= NB_EYES_MAX_WIDTH. */
+int nb_step_boids_seen(nb_ctx *ctx, uint32_t k, const nb_boids_params *params, const float *up_xyz, const float *cp16, uint32_t width,
+                       uint32_t batch);
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which
@@ -420,6 +448,22 @@ int nb_launch_cameras(uint32_t count, const void *eyes, const void *dirs, const 
  * must not alias each other or an input.  count = 0 is a no-op. */
 int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
                    uint32_t flags, void *ids, void *depth, void *stream);
+
+/* The seen sets of `count` rows of `width` columns (nb_eyes_seen's rule), stateless, on caller-owned device memory: ids_rows (uint32) /
+ * depth_rows (float): count*width each, as nb_launch_eyes leaves them or the caller's own; seen_count: count words; seen_ids, seen_depth,
+ * seen_cols: count*width each.  depth_rows, seen_depth and seen_cols may be NULL; seen_depth needs depth_rows.  Everything 4-byte
+ * aligned; no output may overlap another output or an input.  1 <= width <= NB_EYES_MAX_WIDTH.  count = 0 is a no-op.  One kernel
+ * on `stream`. */
+int nb_launch_seen(uint32_t count, uint32_t width, const void *ids_rows, const void *depth_rows, void *seen_count, void *seen_ids,
+                   void *seen_depth, void *seen_cols, void *stream);
+
+/* One boids step over seen lists (nb_step_boids_seen's V2-V3) for bodies [first, first+count) of a set of n_total: body first+e folds
+ * over the first seen_count[e] entries (at most `stride`) of seen_ids[e*stride ..] in list order.  An entry equal to the body's own
+ * index is skipped (the `n != i` test); an entry >= n_total is skipped without being read; a duplicate folds twice.  Buffers as
+ * nb_launch_boids_step's; the lists 4-byte aligned, stride >= 1; the outputs must not alias the inputs or the lists. */
+int nb_launch_boids_seen_step(const nb_boids_params *params, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
+                              const void *vel_in, const void *seen_count, const void *seen_ids, uint32_t stride, void *pos_out,
+                              void *vel_out, void *stream);
 
 /* nb_eyes_colour's rule, stateless, on caller-owned device memory: as nb_launch_eyes, plus skin = tw x th linear RGBA texels (row 0
  * first, 16-byte aligned, 1 <= tw, th <= NB_EYES_MAX_SKIN), or NULL for the 1 x 1 white skin (tw, th ignored); rgba: count*width*4

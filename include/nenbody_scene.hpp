@@ -115,6 +115,49 @@ public:
         e.depth.resize(cells);
         return e;
     }
+    // The seen set of every eye (nb_eyes_seen): which entities occur in the eye's row of eyes() (same arguments), ascending, with
+    // the nearest depth and the number of columns of each.  Row e of ids / depth / cols has `width` slots, count[e] of them used;
+    // the others read NB_EYES_NONE, 1.0f and 0.
+    struct Seen {
+        uint32_t width = 0;
+        std::vector<uint32_t> count, ids;
+        std::vector<float> depth;
+        std::vector<uint32_t> cols;
+    };
+    Seen seen(const Mat4 &cp, uint32_t width = 1024, uint32_t first = 0, uint32_t count = UINT32_MAX, bool see_self = false,
+              const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (count == UINT32_MAX) count = first <= positions.size() ? (uint32_t)positions.size() - first : 0;
+        Seen s;
+        s.width = width;
+        const size_t cells = (size_t)count * width;
+        s.count.resize(count ? count : 1);    // (pointers the library can check even where count = 0)
+        s.ids.resize(cells ? cells : 1);
+        s.depth.resize(cells ? cells : 1);
+        s.cols.resize(cells ? cells : 1);
+        check(nb_eyes_seen(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, s.count.data(),
+                           s.ids.data(), s.depth.data(), s.cols.data()),
+              ctx_);
+        s.count.resize(count);
+        s.ids.resize(cells);
+        s.depth.resize(cells);
+        s.cols.resize(cells);
+        return s;
+    }
+    // one update_instance_boids restricted to what each entity sees (nb_step_boids_seen: body n folds over the entities of its own
+    // row of eyes() instead of over every entity; one that sees nobody stops); host mirrors refreshed.  batch: eyes processed at a
+    // time, 0 = the library's choice.
+    void step_boids_seen(const Mat4 &cp, uint32_t width = 1024, const nb_boids_params *params = nullptr, uint32_t batch = 0,
+                         const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        step_boids_seen_n(1, cp, width, params, batch, up);
+        check(nb_download(ctx_, positions[0].data(), velocities[0].data(), instances[0][0].data()), ctx_);
+    }
+    void step_boids_seen_n(uint32_t k, const Mat4 &cp, uint32_t width = 1024, const nb_boids_params *params = nullptr, uint32_t batch = 0,
+                           const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        check(nb_step_boids_seen(ctx_, k, params, up.data(), cp[0].data(), width, batch), ctx_);
+    }
     // The skin the colour rows sample: tw x th linear RGBA texels, row 0 first; an empty vector: the 1 x 1 white skin.
     void set_skin(const std::vector<std::array<float, 4>> &rgba_linear, uint32_t tw, uint32_t th)
     {

@@ -83,6 +83,9 @@ extern "C" {
     fn nb_eyes_colour(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids: *mut u32, depth: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
     fn nb_eyes_sample_offsets(out8: *mut f32) -> c_int;
     fn nb_eyes_msaa(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, ids8: *mut u32, depth8: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
+    // what a controller makes of the eye rows: the seen set of every eye, and the boids step over it (null params = reference constants)
+    fn nb_eyes_seen(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, seen_count: *mut u32, seen_ids: *mut u32, seen_depth: *mut f32, seen_cols: *mut u32) -> c_int;
+    fn nb_step_boids_seen(ctx: *mut NbCtx, k: u32, params: *const NbBoidsParams, up_xyz: *const f32, cp16: *const f32, width: u32, batch: u32) -> c_int;
     fn nb_srgb_decode_table(out256: *mut f32) -> c_int;
     fn nb_srgb_encode(linear: *const f32, n: usize, out: *mut u8) -> c_int;
     // the scene camera's frame (the reference's display pass, src/main.rs:948-960)
@@ -180,6 +183,16 @@ pub struct Eyes {
     pub width: u32,
     pub ids: Vec<u32>,   // the nearest instance per column, NB_EYES_NONE where none
     pub depth: Vec<f32>, // the depth attachment's value, 1.0 where none
+}
+
+/// What `Scene::seen` returns: per eye the entities that occur in its row, ascending; row e of `ids` / `depth` / `cols` has `width`
+/// slots, `count[e]` of them used.
+pub struct Seen {
+    pub width: u32,
+    pub count: Vec<u32>,
+    pub ids: Vec<u32>,   // NB_EYES_NONE behind the used slots
+    pub depth: Vec<f32>, // the nearest depth at which the eye sees the entity, 1.0 behind the used slots
+    pub cols: Vec<u32>,  // the number of columns the entity holds, 0 behind the used slots
 }
 
 /// What `Scene::eyes_colour` returns: the same plus the colour attachment.
@@ -337,6 +350,46 @@ impl Scene {
         e.ids.truncate(cells);
         e.depth.truncate(cells);
         Ok(e)
+    }
+
+    /// The seen set of every eye (nb_eyes_seen) for bodies [first, first + count): which entities occur in the eye's row of `eyes`.
+    pub fn seen(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32, first: u32, count: u32, see_self: bool) -> Result<Seen, SceneError> {
+        let cells = count as usize * width as usize;
+        let mut s = Seen { width, count: vec![0; (count as usize).max(1)], ids: vec![0; cells.max(1)], depth: vec![0.0; cells.max(1)], cols: vec![0; cells.max(1)] };
+        let up = [up.x, up.y, up.z];
+        let flags = if see_self { NB_EYES_SEE_SELF } else { 0 };
+        check(
+            unsafe {
+                nb_eyes_seen(
+                    self.ctx, first, count, up.as_ptr(), cp.as_ptr() as *const f32, width, flags,
+                    s.count.as_mut_ptr(), s.ids.as_mut_ptr(), s.depth.as_mut_ptr(), s.cols.as_mut_ptr(),
+                )
+            },
+            self.ctx,
+        )?;
+        s.count.truncate(count as usize);
+        s.ids.truncate(cells);
+        s.depth.truncate(cells);
+        s.cols.truncate(cells);
+        Ok(s)
+    }
+
+    /// One update_instance_boids restricted to what each entity sees (nb_step_boids_seen): entity n folds over the entities of its
+    /// own eye row instead of over every entity; one that sees nobody stops.  Replaces the call at src/main.rs:925; mirrors refreshed.
+    pub fn step_boids_seen(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32) -> Result<(), SceneError> {
+        let up = [up.x, up.y, up.z];
+        check(unsafe { nb_step_boids_seen(self.ctx, 1, std::ptr::null(), up.as_ptr(), cp.as_ptr() as *const f32, width, 0) }, self.ctx)?;
+        check(
+            unsafe {
+                nb_download(
+                    self.ctx,
+                    self.positions.as_mut_ptr() as *mut f32,
+                    self.velocities.as_mut_ptr() as *mut f32,
+                    self.instances.as_mut_ptr() as *mut f32,
+                )
+            },
+            self.ctx,
+        )
     }
 
     /// The skin the colour rows sample: `tw` x `th` linear RGBA texels, row 0 first (`skin_from_srgb8` for the decoded

@@ -118,6 +118,12 @@ PROTOTYPES = {
     "nb_eyes_msaa": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nb_launch_eyes_msaa": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_eyes_seen": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_launch_seen": (c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_step_boids_seen": (c_int, [c_void_p, c_uint32, POINTER(NbBoidsParams), c_void_p, c_void_p, c_uint32, c_uint32]),
+    "nb_launch_boids_seen_step": (
+        c_int, [POINTER(NbBoidsParams), c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
+                c_void_p]),
     "nb_srgb_decode_table": (c_int, [c_void_p]),
     "nb_srgb_encode": (c_int, [c_void_p, c_size_t, c_void_p]),
     "nb_camera_at": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

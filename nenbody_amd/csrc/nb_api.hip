@@ -22,6 +22,7 @@
 #include "nb_kernels.h"
 #include "nb_eyes.h"
 #include "nb_frame.h"
+#include "nb_seen.h"
 #define NB_SRGB_TABLE static const
 #define NB_SRGB_WANT_DECODE
 #include "nb_srgb_tables.h"
@@ -852,6 +853,11 @@ struct nb_ctx {
     float *eye_rgba = nullptr;    // nb_eyes_colour's rows, likewise: eye_rgba_cap / eye_bgra_cap columns (4 floats / one word each)
     uint32_t *eye_bgra = nullptr;
     size_t eye_rgba_cap = 0, eye_bgra_cap = 0;
+    uint32_t *seen_count = nullptr;  // nb_eyes_seen's and nb_step_boids_seen's lists, likewise: seen_*_cap entries (one count an eye, one slot a column)
+    uint32_t *seen_ids = nullptr;
+    float *seen_depth = nullptr;
+    uint32_t *seen_cols = nullptr;
+    size_t seen_count_cap = 0, seen_ids_cap = 0, seen_depth_cap = 0, seen_cols_cap = 0;
     float *skin = nullptr;        // nb_eyes_skin's texels (skin_w x skin_h x 4 floats); null: the 1 x 1 white skin
     uint32_t skin_w = 0, skin_h = 0;
     uint64_t *frame_keys = nullptr;  // nb_frame's and nb_frame_msaa's key plane, grown on demand: frame_keys_cap keys (their rows are the eye rows above)
@@ -941,6 +947,10 @@ NB_EXPORT void nb_destroy(nb_ctx *ctx)
     if (ctx->eye_depth) (void)hipFree(ctx->eye_depth);
     if (ctx->eye_rgba) (void)hipFree(ctx->eye_rgba);
     if (ctx->eye_bgra) (void)hipFree(ctx->eye_bgra);
+    if (ctx->seen_count) (void)hipFree(ctx->seen_count);
+    if (ctx->seen_ids) (void)hipFree(ctx->seen_ids);
+    if (ctx->seen_depth) (void)hipFree(ctx->seen_depth);
+    if (ctx->seen_cols) (void)hipFree(ctx->seen_cols);
     if (ctx->skin) (void)hipFree(ctx->skin);
     if (ctx->frame_keys) (void)hipFree(ctx->frame_keys);
     if (ctx->frame_cam) (void)hipFree(ctx->frame_cam);
@@ -2467,5 +2477,6 @@ NB_EXPORT int nb_launch_unpack(uint32_t count, const void *rec4, void *xyz, void
     NB_LAUNCH_TLS(nbk::launch_unpack(count, (const float4 *)rec4, (float *)xyz, (hipStream_t)stream));
 }
 
+#include "nb_seen_api.inc"
 #include "nb_peers.inc"
 #include "nb_shard.inc"

@@ -43,6 +43,7 @@
 //   nb_frame.inc         the scene camera's frame: ids, depth and colour per pixel (SLP-off unit; its own launcher, nb_frame.h)
 //   nb_eyes_msaa.inc     the eye view through 8 samples per column, resolved (SLP-off unit; launcher in nb_eyes.h)
 //   nb_frame_msaa.inc    the scene camera's frame through 8 samples per pixel, resolved (SLP-off unit; launcher in nb_frame.h)
+//   nb_seen.inc          the seen set of every eye row; the boids step over what each body sees (SLP-off unit; launchers in nb_seen.h)
 //   nb_launch.inc        host-side launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,6 +56,7 @@
 #ifdef NBK_NOSLP_TU
 #include "nb_eyes.h"
 #include "nb_frame.h"
+#include "nb_seen.h"
 #endif
 
 namespace nbk {
@@ -78,6 +80,7 @@ static_assert(kMsaaOffsets16 == sample_nibbles(kEyeSampleX16) && kFrameMsaaOffse
 #include "nb_frame.inc"       // the scene camera's frame: likewise
 #include "nb_eyes_msaa.inc"   // the eye view through 8 samples per column: likewise; uses nb_eyes.inc's edge
 #include "nb_frame_msaa.inc"  // the frame through 8 samples per pixel: likewise; uses nb_frame.inc's edge and clear
+#include "nb_seen.inc"        // the seen set of every eye row and the boids step over it: likewise; uses nb_boids.inc's accumulators and epilogue
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

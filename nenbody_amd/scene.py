@@ -197,6 +197,47 @@ class Scene:
                                 depth.ctypes.data), self._ctx)
         return ids, depth
 
+    def _eye_setup(self, width, up, cp):
+        if cp is None:   # (an invalid width is the library's to refuse)
+            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MAX_WIDTH else np.zeros((4, 4), np.float32)
+        return np.ascontiguousarray(up, np.float32).reshape(3), np.ascontiguousarray(cp, np.float32).reshape(16)
+
+    def seen(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, first: int = 0, count: Optional[int] = None,
+             see_self: bool = False):
+        """The seen set of every eye (nb_eyes_seen) for bodies [first, first + count) of the current state: which
+        entities occur in the eye's row of :meth:`eyes` (same arguments), in ascending order, with the nearest depth and the number of
+        columns of each.  Returns (count uint32 (count,), ids uint32 (count, width) -- NB_EYES_NONE behind the first count[e] slots --,
+        depth float32 (count, width) -- 1.0 there --, cols uint32 (count, width) -- 0 there)."""
+        if count is None:
+            count = self.n - first
+        if first < 0 or count < 0:
+            raise ValueError("first and count must be >= 0")
+        upv, cpm = self._eye_setup(width, up, cp)
+        w = max(int(width), 0)
+        cnt = np.empty(count, np.uint32)
+        ids = np.empty((count, w), np.uint32)
+        depth = np.empty((count, w), np.float32)
+        cols = np.empty((count, w), np.uint32)
+        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
+        check(self._lib.nb_eyes_seen(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, cnt.ctypes.data,
+                                     ids.ctypes.data, depth.ctypes.data, cols.ctypes.data), self._ctx)
+        return cnt, ids, depth, cols
+
+    def step_boids_seen(self, params: Optional[NbBoidsParams] = None, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None,
+                        batch: int = 0) -> None:
+        """One update_instance_boids restricted to what each entity sees (nb_step_boids_seen): body n folds
+        over the entities of its own eye row of :meth:`eyes` instead of over every entity; one that sees nobody stops.  Then refresh
+        the host mirrors.  ``batch``: eyes processed at a time (0: the library's choice); every value gives the same bits."""
+        self.step_boids_seen_n(1, params, width, up, cp, batch)
+        self._refresh(True)
+
+    def step_boids_seen_n(self, k: int, params: Optional[NbBoidsParams] = None, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None,
+                          batch: int = 0) -> None:
+        """k such updates, device-resident and asynchronous; host mirrors are NOT refreshed."""
+        upv, cpm = self._eye_setup(width, up, cp)
+        check(self._lib.nb_step_boids_seen(self._ctx, int(k), ctypes.byref(params) if params is not None else None, upv.ctypes.data,
+                                           cpm.ctypes.data, width, int(batch)), self._ctx)
+
     def set_skin(self, rgba=None) -> None:
         """The skin the colour rows sample (nb_eyes_skin): an array (th, tw, 4), row 0 first as the image file stores it -- floats
         are linear RGBA, uint8 is an sRGB image (Rgba8UnormSrgb: colour through :func:`srgb_decode`, alpha / 255).  None: the 1 x 1
