@@ -390,40 +390,63 @@ size_t plan_scratch_bytes(const Plan &pl, uint32_t count)
     return pl.slices > 1 ? (size_t)pl.slices * count * sizeof(float4) : 0;
 }
 
-// The launch API is stateless; a rank calls it with the same shape every step.  A few plans per thread are kept, keyed by
-// everything make_plan reads (no lock: one thread drives one GPU).
-int cached_plan(const nb_params &p, uint32_t n_total, uint32_t count, const Plan **out, std::string *err)
+// The launch API is stateless; a rank calls it with the same shape every step.  A few planned shapes per thread are kept (no lock:
+// one thread drives one GPU), keyed by everything the planners read: the parameters, the shape words and the overrides'
+// generation.  The key is compared with memcmp, so plan_key() zeroes it whole -- padding included -- before it fills it.
+struct PlanKey {
+    nb_params p;
+    uint32_t shape[4];
+    uint32_t generation;
+};
+PlanKey plan_key(const nb_params &p, uint32_t s0, uint32_t s1, uint32_t s2 = 0, uint32_t s3 = 0)
 {
+    PlanKey k;
+    std::memset(&k, 0, sizeof(k));
+    k.p = p;
+    k.shape[0] = s0;
+    k.shape[1] = s1;
+    k.shape[2] = s2;
+    k.shape[3] = s3;
+    k.generation = overrides().generation;
+    return k;
+}
+// N entries, replaced in turn.  get(): the cached value for `key`, else make(&value) -- kept only when it succeeds.
+template <typename Key, typename Value, int N>
+class PlanCache {
     struct Entry {
         bool valid = false;
-        nb_params p{};
-        uint32_t n_total = 0, count = 0, generation = 0;
-        Plan pl{};
+        Key key;
+        Value value;
     };
-    constexpr int kEntries = 4;
-    thread_local Entry cache[kEntries];
-    thread_local int next = 0;
-    const uint32_t gen = overrides().generation;
-    for (int i = 0; i < kEntries; ++i) {
-        const Entry &e = cache[i];
-        if (e.valid && e.n_total == n_total && e.count == count && e.generation == gen && std::memcmp(&e.p, &p, sizeof(p)) == 0) {
-            *out = &e.pl;
-            return NB_OK;
-        }
+    Entry entries_[N];
+    int next_ = 0;
+
+public:
+    template <typename Make>
+    int get(const Key &key, const Value **out, Make make)
+    {
+        for (const Entry &e : entries_)
+            if (e.valid && std::memcmp(&e.key, &key, sizeof(Key)) == 0) {
+                *out = &e.value;
+                return NB_OK;
+            }
+        Value v;
+        int rc = make(&v);
+        if (rc != NB_OK) return rc;
+        Entry &e = entries_[next_];
+        next_ = (next_ + 1) % N;
+        e.valid = true;
+        e.key = key;
+        e.value = v;
+        *out = &e.value;
+        return NB_OK;
     }
-    Plan pl;
-    int rc = make_plan(p, n_total, count, &pl, err);
-    if (rc != NB_OK) return rc;
-    Entry &e = cache[next];
-    next = (next + 1) % kEntries;
-    e.valid = true;
-    e.p = p;
-    e.n_total = n_total;
-    e.count = count;
-    e.generation = gen;
-    e.pl = pl;
-    *out = &e.pl;
-    return NB_OK;
+};
+
+int cached_plan(const nb_params &p, uint32_t n_total, uint32_t count, const Plan **out, std::string *err)
+{
+    thread_local PlanCache<PlanKey, Plan, 4> cache;
+    return cache.get(plan_key(p, n_total, count), out, [&](Plan *pl) { return make_plan(p, n_total, count, pl, err); });
 }
 
 // ---- roctx ranges (tracing) -----------------------------------------------------------------
@@ -555,25 +578,43 @@ int check_status(StatusWord *sw, std::string *err)
     return check_status_word(sw->w, err);
 }
 
-int launch_step_planned(const nb_params &p, const Plan &pl, uint32_t n_total, uint32_t first, uint32_t count,
-                        const void *pos_in, void *pos_out, void *vel, void *scratch, hipStream_t stream, std::string *err,
-                        StatusWord *sw = nullptr)
+// What every step launch fills alike: the buffers, the shape, the constants and the plan's two verdicts.  The fields only some forms
+// read (the guard bits, j_chunk, the j range and its hole, partial rows, the block chain's knobs) stay with the caller.
+nbk::StepArgs step_args(const nb_params &p, const Plan &pl, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
+                        void *pos_out, void *vel)
 {
     nbk::StepArgs a{};
     a.pos_in = (const float4 *)pos_in;
     a.pos_out = (float4 *)pos_out;
     a.vel = (float4 *)vel;
-    a.partial = (float4 *)scratch;
     a.n_total = n_total;
     a.first = first;
     a.count = count;
     a.dt = p.dt;
     a.G = p.G;
     a.bias = p.bias;
-    a.lo_bits = pl.lo_bits;
-    a.hi_bits = pl.hi_bits;
     a.force_ieee = pl.force_ieee;
     a.force_3d = pl.force_3d;
+    return a;
+}
+
+// A launcher's answer as a status: NB_ERR_HIP with `what` (the caller's own text, up to and including ": ") and the runtime's words.
+// The string is built only for a failure.
+int launch_status(hipError_t e, const char *what, std::string *err)
+{
+    if (e == hipSuccess) return NB_OK;
+    *err = std::string(what) + hipGetErrorString(e);
+    return NB_ERR_HIP;
+}
+
+int launch_step_planned(const nb_params &p, const Plan &pl, uint32_t n_total, uint32_t first, uint32_t count,
+                        const void *pos_in, void *pos_out, void *vel, void *scratch, hipStream_t stream, std::string *err,
+                        StatusWord *sw = nullptr)
+{
+    nbk::StepArgs a = step_args(p, pl, n_total, first, count, pos_in, pos_out, vel);
+    a.partial = (float4 *)scratch;
+    a.lo_bits = pl.lo_bits;
+    a.hi_bits = pl.hi_bits;
     a.j_chunk = pl.j_chunk;
     a.no_packed = pl.no_packed;
     a.spin_budget = pl.spin_budget;
@@ -602,11 +643,7 @@ int launch_step_planned(const nb_params &p, const Plan &pl, uint32_t n_total, ui
                "builds libnenbody_hip_legacy.so, which holds every form)";
         return NB_ERR_UNSUPPORTED;
     }
-    if (e != hipSuccess) {
-        *err = std::string("nb: kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(e, "nb: kernel launch failed: ", err);
 }
 
 int check_device(std::string *err)
@@ -814,6 +851,41 @@ int select_device_of(const void *dev_ptr, std::string *err)
             return NB_ERR_HIP;
         }
     }
+    return NB_OK;
+}
+
+// ---- the preamble of the stateless launch API ------------------------------------------------------------------------
+nb_params params_or_default(const nb_params *params)
+{
+    nb_params p;
+    if (params)
+        p = *params;
+    else
+        nb_default_params(&p);
+    return p;
+}
+nb_boids_params boids_params_or_default(const nb_boids_params *params)
+{
+    nb_boids_params p;
+    if (params)
+        p = *params;
+    else
+        nb_boids_default_params(&p);
+    return p;
+}
+
+// A device is present, and the device that owns the caller's buffers (`anchor`: one of them) is current.  Two rules say when the
+// library makes it so, and every entry keeps the rule it was written with:
+//   kForNullStream  nb_launch_step, nb_launch_step_phase and the nb_launch_ring_* entries: a caller that brings a stream has made that
+//                   stream's device current; the NULL stream says nothing about the device, so only then do the buffers decide.
+//   kAlways         the boids, eyes, frame and seen entries: the buffers decide whatever the stream.
+// (nb_launch_instances / _cameras / _random_step / _pack / _unpack select nothing: NB_LAUNCH_TLS asks for a device only.)
+enum class SelectDevice { kForNullStream, kAlways };
+int device_for_launch(const void *anchor, const void *stream, SelectDevice rule)
+{
+    int rc = check_device(&g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (rule == SelectDevice::kAlways || !stream) return select_device_of(anchor, &g_tls_error);
     return NB_OK;
 }
 
@@ -1097,11 +1169,7 @@ NB_EXPORT int nb_create(uint32_t n, uint32_t n_devices, const nb_params *params,
             "nb_create: n_devices must be 1 (one process drives one GPU; shard with nb_launch_step and an all-gather)";
         return NB_ERR_UNSUPPORTED;
     }
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     Plan plan;
     int rc = make_plan(p, n, n, &plan, &g_tls_error);
     if (rc != NB_OK) return rc;
@@ -1209,11 +1277,7 @@ NB_EXPORT int nb_step_boids(nb_ctx *ctx, uint32_t k, const nb_boids_params *para
         ctx->err = "nb_step_boids: no state uploaded (call nb_upload first)";
         return NB_ERR_STATE;
     }
-    nb_boids_params p;
-    if (params)
-        p = *params;
-    else
-        nb_boids_default_params(&p);
+    const nb_boids_params p = boids_params_or_default(params);
     nbk::BoidsArgs a;
     uint32_t tile = 0;
     int rc = make_boids_args(p, ctx->n, 0, ctx->n, &a, &tile, &ctx->err);
@@ -1464,34 +1528,57 @@ static int download_rows(nb_ctx *ctx, uint32_t *ids, float *depth, float *rgba, 
     return NB_OK;
 }
 
-NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
-                      uint32_t flags, uint32_t *ids, float *depth)
+// What differs between the entries of one view body (the eyes' or the frame's; the context's or the stateless one's).
+struct ViewForm {
+    const char *fn;           // the entry's name, for its messages
+    bool msaa;                // 8 samples a cell: the narrower limit, eight words a cell of ids and depth
+    uint32_t need;            // the outputs of which one at least must be wanted (bit a: out[a]) ...
+    const char *none_msg;     // ... and what to say otherwise
+    bool aligned4;            // the outputs must be 4-byte aligned
+    const char *align16_msg;  // stateless entries: what must be 16-byte aligned
+};
+
+// The context's eye entries: check, stage, launch, download.  `launch` is the entry's own launch on the context's rows and
+// stream (its failure text names the call: NB_HIP).
+template <typename Launch>
+static int ctx_eyes(nb_ctx *ctx, const ViewForm &f, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
+                    uint32_t flags, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8, Launch launch)
 {
     if (!ctx) {
-        g_tls_error = "nb_eyes: ctx is null";
+        g_tls_error = std::string(f.fn) + ": ctx is null";
         return NB_ERR_INVALID;
     }
     if (!up_xyz || !cp16) {
-        ctx->err = "nb_eyes: null argument";
+        ctx->err = std::string(f.fn) + ": null argument";
         return NB_ERR_INVALID;
     }
-    const size_t cells = (size_t)count * width;
+    const size_t cells = (size_t)count * width, words = f.msaa ? cells * NB_EYES_SAMPLES : cells;
     const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {nullptr, 0}, {nullptr, 0}};
-    int rc = eyes_range_check("nb_eyes", ctx->n, first, count, width, false, flags, &ctx->err);
-    if (rc == NB_OK) rc = outputs_check("nb_eyes", out, 0x3u, kNoIdsDepth, false, in, 2, kEyesAlias, &ctx->err);
+    const ByteRange out[4] = {{ids, words * 4u}, {depth, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = eyes_range_check(f.fn, ctx->n, first, count, width, f.msaa, flags, &ctx->err);
+    if (rc == NB_OK) rc = outputs_check(f.fn, out, f.need, f.none_msg, f.aligned4, in, 2, kEyesAlias, &ctx->err);
     if (rc != NB_OK) return rc;
     if (!ctx->uploaded) {
-        ctx->err = "nb_eyes: no state uploaded";
+        ctx->err = std::string(f.fn) + ": no state uploaded";
         return NB_ERR_STATE;
     }
     if (count == 0) return NB_OK;
-    rc = grow_rows(ctx, ids, depth, nullptr, nullptr, cells, cells);
+    rc = grow_rows(ctx, ids, depth, rgba, bgra8, words, cells);
     if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
+    if (rc == NB_OK) rc = launch();
     if (rc != NB_OK) return rc;
-    NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags,
-                                 ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr, ctx->stream));
-    return download_rows(ctx, ids, depth, nullptr, nullptr, cells, cells);
+    return download_rows(ctx, ids, depth, rgba, bgra8, words, cells);
+}
+
+NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
+                      uint32_t flags, uint32_t *ids, float *depth)
+{
+    static const ViewForm f = {"nb_eyes", false, 0x3u, kNoIdsDepth, false, nullptr};
+    return ctx_eyes(ctx, f, first, count, up_xyz, cp16, width, flags, ids, depth, nullptr, nullptr, [&]() -> int {
+        NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags,
+                                     ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr, ctx->stream));
+        return NB_OK;
+    });
 }
 
 NB_EXPORT int nb_srgb_decode_table(float *out256)
@@ -1547,32 +1634,13 @@ NB_EXPORT int nb_eyes_skin(nb_ctx *ctx, const float *rgba_linear, uint32_t tw, u
 NB_EXPORT int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
                              uint32_t flags, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8)
 {
-    if (!ctx) {
-        g_tls_error = "nb_eyes_colour: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!up_xyz || !cp16) {
-        ctx->err = "nb_eyes_colour: null argument";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)count * width;
-    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = eyes_range_check("nb_eyes_colour", ctx->n, first, count, width, false, flags, &ctx->err);
-    if (rc == NB_OK) rc = outputs_check("nb_eyes_colour", out, 0xCu, kNoColour, true, in, 2, kEyesAlias, &ctx->err);
-    if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = "nb_eyes_colour: no state uploaded";
-        return NB_ERR_STATE;
-    }
-    if (count == 0) return NB_OK;
-    rc = grow_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
-    if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
-    if (rc != NB_OK) return rc;
-    NB_HIP(ctx, nbk::launch_eyes_colour(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
-                                        ctx->skin_w, ctx->skin_h, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
-                                        rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    return download_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
+    static const ViewForm f = {"nb_eyes_colour", false, 0xCu, kNoColour, true, nullptr};
+    return ctx_eyes(ctx, f, first, count, up_xyz, cp16, width, flags, ids, depth, rgba, bgra8, [&]() -> int {
+        NB_HIP(ctx, nbk::launch_eyes_colour(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
+                                            ctx->skin_w, ctx->skin_h, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
+                                            rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        return NB_OK;
+    });
 }
 
 NB_EXPORT int nb_eyes_sample_offsets(float *out8)
@@ -1591,32 +1659,13 @@ NB_EXPORT int nb_eyes_sample_offsets(float *out8)
 NB_EXPORT int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
                            uint32_t flags, uint32_t *ids8, float *depth8, float *rgba, uint32_t *bgra8)
 {
-    if (!ctx) {
-        g_tls_error = "nb_eyes_msaa: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!up_xyz || !cp16) {
-        ctx->err = "nb_eyes_msaa: null argument";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)count * width, words = cells * NB_EYES_SAMPLES;
-    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
-    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = eyes_range_check("nb_eyes_msaa", ctx->n, first, count, width, true, flags, &ctx->err);
-    if (rc == NB_OK) rc = outputs_check("nb_eyes_msaa", out, 0xFu, kNoOutputs8, true, in, 2, kEyesAlias, &ctx->err);
-    if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = "nb_eyes_msaa: no state uploaded";
-        return NB_ERR_STATE;
-    }
-    if (count == 0) return NB_OK;
-    rc = grow_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
-    if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
-    if (rc != NB_OK) return rc;
-    NB_HIP(ctx, nbk::launch_eyes_msaa(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
-                                      ctx->skin_w, ctx->skin_h, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
-                                      rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    return download_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
+    static const ViewForm f = {"nb_eyes_msaa", true, 0xFu, kNoOutputs8, true, nullptr};
+    return ctx_eyes(ctx, f, first, count, up_xyz, cp16, width, flags, ids8, depth8, rgba, bgra8, [&]() -> int {
+        NB_HIP(ctx, nbk::launch_eyes_msaa(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
+                                          ctx->skin_w, ctx->skin_h, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
+                                          rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        return NB_OK;
+    });
 }
 
 NB_EXPORT size_t nb_frame_scratch_bytes(uint32_t width, uint32_t height)
@@ -1655,36 +1704,48 @@ static int stage_frame(nb_ctx *ctx, const float *cam16, size_t keys)
     return NB_OK;
 }
 
+// The context's frame entries: check, stage, launch, download (as ctx_eyes; `keys`: the key plane's entries, one a sample).
+template <typename Launch>
+static int ctx_frame(nb_ctx *ctx, const ViewForm &f, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids,
+                     float *depth, float *rgba, uint32_t *bgra8, Launch launch)
+{
+    if (!ctx) {
+        g_tls_error = std::string(f.fn) + ": ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (!cam16) {
+        ctx->err = std::string(f.fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    const size_t cells = (size_t)width * height, words = f.msaa ? cells * NB_EYES_SAMPLES : cells;
+    const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
+    const ByteRange out[4] = {{ids, words * 4u}, {depth, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = frame_extent_check(f.fn, width, height, f.msaa, flags, &ctx->err);
+    if (rc == NB_OK) rc = outputs_check(f.fn, out, f.need, f.none_msg, f.aligned4, in, 1, kFrameAlias, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (!ctx->uploaded) {
+        ctx->err = std::string(f.fn) + ": no state uploaded";
+        return NB_ERR_STATE;
+    }
+    rc = grow_rows(ctx, ids, depth, rgba, bgra8, words, cells);
+    if (rc == NB_OK) rc = stage_frame(ctx, cam16, words);
+    if (rc == NB_OK) rc = stage_matrices(ctx, 0, 0, nullptr, nullptr);
+    if (rc == NB_OK) rc = launch();
+    if (rc != NB_OK) return rc;
+    return download_rows(ctx, ids, depth, rgba, bgra8, words, cells);
+}
+
 // The scene camera's frame: the rows are the eye rows, the key plane is the frame's own.
 NB_EXPORT int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids, float *depth,
                        float *rgba, uint32_t *bgra8)
 {
-    if (!ctx) {
-        g_tls_error = "nb_frame: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!cam16) {
-        ctx->err = "nb_frame: null argument";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)width * height;
-    const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = frame_extent_check("nb_frame", width, height, false, flags, &ctx->err);
-    if (rc == NB_OK) rc = outputs_check("nb_frame", out, 0xFu, kNoOutputs, true, in, 1, kFrameAlias, &ctx->err);
-    if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = "nb_frame: no state uploaded";
-        return NB_ERR_STATE;
-    }
-    rc = grow_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
-    if (rc == NB_OK) rc = stage_frame(ctx, cam16, cells);
-    if (rc == NB_OK) rc = stage_matrices(ctx, 0, 0, nullptr, nullptr);
-    if (rc != NB_OK) return rc;
-    NB_HIP(ctx, nbk::launch_frame(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
-                                  ctx->skin_h, ctx->frame_keys, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
-                                  rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    return download_rows(ctx, ids, depth, rgba, bgra8, cells, cells);
+    static const ViewForm f = {"nb_frame", false, 0xFu, kNoOutputs, true, nullptr};
+    return ctx_frame(ctx, f, cam16, width, height, flags, ids, depth, rgba, bgra8, [&]() -> int {
+        NB_HIP(ctx, nbk::launch_frame(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
+                                      ctx->skin_h, ctx->frame_keys, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
+                                      rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        return NB_OK;
+    });
 }
 
 NB_EXPORT size_t nb_frame_msaa_scratch_bytes(uint32_t width, uint32_t height)
@@ -1711,32 +1772,13 @@ NB_EXPORT int nb_frame_sample_offsets(float *out16)
 NB_EXPORT int nb_frame_msaa(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids8, float *depth8,
                             float *rgba, uint32_t *bgra8)
 {
-    if (!ctx) {
-        g_tls_error = "nb_frame_msaa: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!cam16) {
-        ctx->err = "nb_frame_msaa: null argument";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)width * height, words = cells * NB_EYES_SAMPLES;
-    const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
-    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = frame_extent_check("nb_frame_msaa", width, height, true, flags, &ctx->err);
-    if (rc == NB_OK) rc = outputs_check("nb_frame_msaa", out, 0xFu, kNoOutputs8, true, in, 1, kFrameAlias, &ctx->err);
-    if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = "nb_frame_msaa: no state uploaded";
-        return NB_ERR_STATE;
-    }
-    rc = grow_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
-    if (rc == NB_OK) rc = stage_frame(ctx, cam16, words);
-    if (rc == NB_OK) rc = stage_matrices(ctx, 0, 0, nullptr, nullptr);
-    if (rc != NB_OK) return rc;
-    NB_HIP(ctx, nbk::launch_frame_msaa(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
-                                       ctx->skin_h, ctx->frame_keys, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
-                                       rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
-    return download_rows(ctx, ids8, depth8, rgba, bgra8, words, cells);
+    static const ViewForm f = {"nb_frame_msaa", true, 0xFu, kNoOutputs8, true, nullptr};
+    return ctx_frame(ctx, f, cam16, width, height, flags, ids8, depth8, rgba, bgra8, [&]() -> int {
+        NB_HIP(ctx, nbk::launch_frame_msaa(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
+                                           ctx->skin_h, ctx->frame_keys, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
+                                           rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        return NB_OK;
+    });
 }
 
 NB_EXPORT int nb_sync(nb_ctx *ctx)
@@ -1815,11 +1857,7 @@ NB_EXPORT int nb_download(nb_ctx *ctx, float *pos_xyz, float *vel_xyz, float *in
 
 NB_EXPORT size_t nb_scratch_bytes(const nb_params *params, uint32_t n_total, uint32_t count)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     Plan pl;
     std::string err;
     if (make_plan(p, n_total, count, &pl, &err) != NB_OK) return 0;
@@ -1829,11 +1867,7 @@ NB_EXPORT size_t nb_scratch_bytes(const nb_params *params, uint32_t n_total, uin
 NB_EXPORT int nb_launch_step(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
                              void *pos_out, void *vel, void *scratch, size_t scratch_bytes, void *stream)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     if (!pos_in || !pos_out || !vel || pos_in == pos_out) {
         g_tls_error = "nb_launch_step: pos_in, pos_out, vel must be non-null and pos_out must not alias pos_in";
         return NB_ERR_INVALID;
@@ -1850,12 +1884,8 @@ NB_EXPORT int nb_launch_step(const nb_params *params, uint32_t n_total, uint32_t
         g_tls_error = "nb_launch_step: scratch smaller than nb_scratch_bytes()";
         return NB_ERR_INVALID;
     }
-    rc = check_device(&g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kForNullStream);
     if (rc != NB_OK) return rc;
-    if (!stream) {  // a caller that brings a stream has made that stream's device current; the NULL stream says nothing
-        rc = select_device_of(pos_in, &g_tls_error);
-        if (rc != NB_OK) return rc;
-    }
     return launch_step_planned(p, *pl, n_total, first, count, pos_in, pos_out, vel, scratch, (hipStream_t)stream, &g_tls_error);
 }
 
@@ -1928,49 +1958,15 @@ namespace {
 int cached_phase_plan(const nb_params &p, uint32_t n_total, uint32_t count, uint32_t j_lo, uint32_t j_hi, const PhasePlan **out,
                       std::string *err)
 {
-    struct Entry {
-        bool valid = false;
-        nb_params p{};
-        uint32_t n_total = 0, count = 0, j_lo = 0, j_hi = 0, generation = 0;
-        PhasePlan pp{};
-    };
-    constexpr int kEntries = 2;
-    thread_local Entry cache[kEntries];
-    thread_local int next = 0;
-    const uint32_t gen = overrides().generation;
-    for (int i = 0; i < kEntries; ++i) {
-        const Entry &e = cache[i];
-        if (e.valid && e.n_total == n_total && e.count == count && e.j_lo == j_lo && e.j_hi == j_hi && e.generation == gen &&
-            std::memcmp(&e.p, &p, sizeof(p)) == 0) {
-            *out = &e.pp;
-            return NB_OK;
-        }
-    }
-    PhasePlan pp;
-    int rc = make_phase_plan(p, n_total, count, j_lo, j_hi, &pp, err);
-    if (rc != NB_OK) return rc;
-    Entry &e = cache[next];
-    next = (next + 1) % kEntries;
-    e.valid = true;
-    e.p = p;
-    e.n_total = n_total;
-    e.count = count;
-    e.j_lo = j_lo;
-    e.j_hi = j_hi;
-    e.generation = gen;
-    e.pp = pp;
-    *out = &e.pp;
-    return NB_OK;
+    thread_local PlanCache<PlanKey, PhasePlan, 2> cache;
+    return cache.get(plan_key(p, n_total, count, j_lo, j_hi), out,
+                     [&](PhasePlan *pp) { return make_phase_plan(p, n_total, count, j_lo, j_hi, pp, err); });
 }
 }  // namespace
 
 NB_EXPORT size_t nb_scratch_bytes_phased(const nb_params *params, uint32_t n_total, uint32_t count, uint32_t j_lo, uint32_t j_hi)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     PhasePlan pp;
     std::string err;
     if (make_phase_plan(p, n_total, count, j_lo, j_hi, &pp, &err) != NB_OK) return 0;
@@ -1983,20 +1979,9 @@ int launch_phase_planned(const nb_params &p, const PhasePlan &pp, uint32_t n_tot
                          int phase, const void *pos_in, void *pos_out, void *vel, void *scratch, hipStream_t stream, std::string *err)
 {
     const Plan &pl = pp.base;
-    nbk::StepArgs a{};
-    a.pos_in = (const float4 *)pos_in;
-    a.pos_out = (float4 *)pos_out;
-    a.vel = (float4 *)vel;
-    char *const rows = (char *)scratch + (pp.fsl ? nbk::strict_bc_scratch_bytes(n_total) : 0);  // the partial rows: behind the planes area
+    nbk::StepArgs a = step_args(p, pl, n_total, first, count, pos_in, pos_out, vel);
+    char *const rows = pp.fsl ? nbk::plane_scratch(scratch, n_total).behind : (char *)scratch;  // the partial rows: behind the planes area
     a.partial = (float4 *)rows;
-    a.n_total = n_total;
-    a.first = first;
-    a.count = count;
-    a.dt = p.dt;
-    a.G = p.G;
-    a.bias = p.bias;
-    a.force_ieee = pl.force_ieee;
-    a.force_3d = pl.force_3d;
     a.always_partial = 1;
     hipError_t e = hipSuccess;
     if (phase == NB_PHASE_RANGE) {  // records [j_lo, j_lo + len[0]) -> partial rows [0, slices[0])
@@ -2027,11 +2012,7 @@ int launch_phase_planned(const nb_params &p, const PhasePlan &pp, uint32_t n_tot
             e = hipMemsetAsync(rows + (size_t)pp.slices[0] * count * sizeof(float4), 0, (size_t)pp.slices[1] * count * sizeof(float4), stream);
         if (e == hipSuccess) e = nbk::launch_integrate_partials(a, pp.slices[0] + pp.slices[1], stream);
     }
-    if (e != hipSuccess) {
-        *err = std::string("nb: kernel launch failed (step phase): ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(e, "nb: kernel launch failed (step phase): ", err);
 }
 }  // namespace
 
@@ -2039,11 +2020,7 @@ NB_EXPORT int nb_launch_step_phase(const nb_params *params, uint32_t n_total, ui
                                    uint32_t j_hi, int phase, const void *pos_in, void *pos_out, void *vel, void *scratch,
                                    size_t scratch_bytes, void *stream)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     if (!pos_in || !pos_out || !vel || pos_in == pos_out || !scratch || (phase != NB_PHASE_RANGE && phase != NB_PHASE_REST)) {
         g_tls_error = "nb_launch_step_phase: pos_in, pos_out, vel, scratch must be non-null, pos_out must not alias pos_in, phase is "
                       "NB_PHASE_RANGE or NB_PHASE_REST";
@@ -2061,12 +2038,8 @@ NB_EXPORT int nb_launch_step_phase(const nb_params *params, uint32_t n_total, ui
         g_tls_error = "nb_launch_step_phase: scratch smaller than nb_scratch_bytes_phased()";
         return NB_ERR_INVALID;
     }
-    rc = check_device(&g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kForNullStream);
     if (rc != NB_OK) return rc;
-    if (!stream) {  // as nb_launch_step: the NULL stream says nothing about the device, the buffers do
-        rc = select_device_of(pos_in, &g_tls_error);
-        if (rc != NB_OK) return rc;
-    }
     return launch_phase_planned(p, pp, n_total, first, count, j_lo, phase, pos_in, pos_out, vel, scratch, (hipStream_t)stream, &g_tls_error);
 }
 
@@ -2098,11 +2071,7 @@ NB_EXPORT int nb_diag_plan(const nb_params *params, uint32_t n_total, uint32_t c
         g_tls_error = "nb_diag_plan: out is null";
         return NB_ERR_INVALID;
     }
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     Plan pl;
     int rc = make_plan(p, n_total, count, &pl, &g_tls_error);
     if (rc != NB_OK) return rc;
@@ -2145,11 +2114,7 @@ NB_EXPORT int nb_debug_reload_env(void)
 NB_EXPORT int nb_launch_boids_step(const nb_boids_params *params, uint32_t n_total, uint32_t first, uint32_t count,
                                    const void *pos_in, const void *vel_in, void *pos_out, void *vel_out, void *stream)
 {
-    nb_boids_params p;
-    if (params)
-        p = *params;
-    else
-        nb_boids_default_params(&p);
+    const nb_boids_params p = boids_params_or_default(params);
     if (!pos_in || !vel_in || !pos_out || !vel_out || pos_in == pos_out || vel_in == vel_out) {
         g_tls_error = "nb_launch_boids_step: buffers must be non-null and the outputs must not alias the inputs";
         return NB_ERR_INVALID;
@@ -2158,29 +2123,18 @@ NB_EXPORT int nb_launch_boids_step(const nb_boids_params *params, uint32_t n_tot
     uint32_t tile = 0;
     int rc = make_boids_args(p, n_total, first, count, &a, &tile, &g_tls_error);
     if (rc != NB_OK) return rc;
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(pos_in, &g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
     a.pos_in = (const float4 *)pos_in;
     a.vel_in = (const float4 *)vel_in;
     a.pos_out = (float4 *)pos_out;
     a.vel_out = (float4 *)vel_out;
-    hipError_t e = nbk::launch_boids(a, tile, boids_form(a.count), (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: boids kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(nbk::launch_boids(a, tile, boids_form(a.count), (hipStream_t)stream), "nb: boids kernel launch failed: ", &g_tls_error);
 }
 
 NB_EXPORT size_t nb_boids_split_scratch_bytes(const nb_boids_params *params, uint32_t n_total, uint32_t count)
 {
-    nb_boids_params p;
-    if (params)
-        p = *params;
-    else
-        nb_boids_default_params(&p);
+    const nb_boids_params p = boids_params_or_default(params);
     nbk::BoidsArgs a;
     uint32_t tile = 0, slices = 0, chunk = 0;
     std::string err;
@@ -2194,11 +2148,7 @@ NB_EXPORT int nb_launch_boids_step_split(const nb_boids_params *params, uint32_t
                                          const void *pos_in, const void *vel_in, void *pos_out, void *vel_out, void *scratch,
                                          size_t scratch_bytes, void *stream)
 {
-    nb_boids_params p;
-    if (params)
-        p = *params;
-    else
-        nb_boids_default_params(&p);
+    const nb_boids_params p = boids_params_or_default(params);
     if (!pos_in || !vel_in || !pos_out || !vel_out || !scratch || pos_in == pos_out || vel_in == vel_out) {
         g_tls_error = "nb_launch_boids_step_split: buffers must be non-null and the outputs must not alias the inputs";
         return NB_ERR_INVALID;
@@ -2212,33 +2162,23 @@ NB_EXPORT int nb_launch_boids_step_split(const nb_boids_params *params, uint32_t
         g_tls_error = "nb_launch_boids_step_split: scratch smaller than nb_boids_split_scratch_bytes()";
         return NB_ERR_INVALID;
     }
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(pos_in, &g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
     a.pos_in = (const float4 *)pos_in;
     a.vel_in = (const float4 *)vel_in;
     a.pos_out = (float4 *)pos_out;
     a.vel_out = (float4 *)vel_out;
     boids_split_pointers(&a, scratch, slices, chunk);
-    hipError_t e = nbk::launch_boids_split(a, tile, slices, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: boids kernel launch failed (split form): ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(nbk::launch_boids_split(a, tile, slices, (hipStream_t)stream), "nb: boids kernel launch failed (split form): ",
+                         &g_tls_error);
 }
 
-#define NB_LAUNCH_TLS(call)                                                                  \
-    do {                                                                                     \
-        int rc_ = check_device(&g_tls_error);                                                \
-        if (rc_ != NB_OK) return rc_;                                                        \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            g_tls_error = std::string("nb: " #call " failed: ") + hipGetErrorString(e_);     \
-            return NB_ERR_HIP;                                                               \
-        }                                                                                    \
-        return NB_OK;                                                                        \
+// the small launches: a device is asked for, none is selected; the failure's text names the call
+#define NB_LAUNCH_TLS(call)                                                   \
+    do {                                                                      \
+        int rc_ = check_device(&g_tls_error);                                 \
+        if (rc_ != NB_OK) return rc_;                                         \
+        return launch_status((call), "nb: " #call " failed: ", &g_tls_error); \
     } while (0)
 
 NB_EXPORT int nb_launch_instances(uint32_t count, const void *pos, const void *vel, void *inst_16n, void *stream)
@@ -2261,193 +2201,131 @@ NB_EXPORT int nb_launch_cameras(uint32_t count, const void *eyes, const void *di
                                       (hipStream_t)stream));
 }
 
+// The stateless eye entries: every check, then the device of inst_16n, then `launch` (the entry's own nbk::launch_*).
+// nb_launch_eyes passes no skin and no colour rows: NULL takes part in no check.
+static const char kAlign16Eyes[] = ": cams_16 and inst_16n must be 16-byte aligned";
+static const char kAlign16Colour[] = ": cams_16, inst_16n, skin and rgba must be 16-byte aligned";
+static const char kAlign16Frame[] = ": cam_16, inst_16n, skin and rgba must be 16-byte aligned";
+static const char kSkinExtent[] = ": tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
+
+template <typename Launch>
+static int launch_eyes_form(const ViewForm &f, uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n,
+                            uint32_t width, uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids, void *depth, void *rgba,
+                            void *bgra8, void *stream, Launch launch)
+{
+    if (!cams_16 || !inst_16n) {
+        g_tls_error = std::string(f.fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
+        g_tls_error = std::string(f.fn) + f.align16_msg;
+        return NB_ERR_INVALID;
+    }
+    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
+        g_tls_error = std::string(f.fn) + kSkinExtent;
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[3] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
+                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}};
+    const size_t cells = (size_t)count * width, words = f.msaa ? cells * NB_EYES_SAMPLES : cells;
+    const ByteRange out[4] = {{ids, words * 4u}, {depth, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = eyes_range_check(f.fn, n_total, first, count, width, f.msaa, flags, &g_tls_error);
+    if (rc == NB_OK) rc = outputs_check(f.fn, out, f.need, f.none_msg, f.aligned4, in, 3, kEyesAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = device_for_launch(inst_16n, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    return launch_status(launch(), "nb: eyes kernel launch failed: ", &g_tls_error);
+}
+
+// The stateless frame entries likewise; the device is the scratch's.
+template <typename Launch>
+static int launch_frame_form(const ViewForm &f, uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height,
+                             uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids, void *depth, void *rgba,
+                             void *bgra8, void *stream, Launch launch)
+{
+    if (!cam_16 || !scratch || (n_total && !inst_16n)) {
+        g_tls_error = std::string(f.fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)cam_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
+        g_tls_error = std::string(f.fn) + f.align16_msg;
+        return NB_ERR_INVALID;
+    }
+    if ((uintptr_t)scratch & 7u) {
+        g_tls_error = std::string(f.fn) + ": scratch must be 8-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
+        g_tls_error = std::string(f.fn) + kSkinExtent;
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[4] = {{cam_16, 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
+                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0},
+                             {scratch, f.msaa ? nb_frame_msaa_scratch_bytes(width, height) : nb_frame_scratch_bytes(width, height)}};
+    const size_t cells = (size_t)width * height, words = f.msaa ? cells * NB_EYES_SAMPLES : cells;
+    const ByteRange out[4] = {{ids, words * 4u}, {depth, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
+    int rc = frame_extent_check(f.fn, width, height, f.msaa, flags, &g_tls_error);
+    if (rc == NB_OK) rc = outputs_check(f.fn, out, f.need, f.none_msg, f.aligned4, in, 4, kFrameAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = device_for_launch(scratch, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    return launch_status(launch(), "nb: frame kernel launch failed: ", &g_tls_error);
+}
+
 NB_EXPORT int nb_launch_eyes(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n, uint32_t width,
                              uint32_t flags, void *ids, void *depth, void *stream)
 {
-    if (!cams_16 || !inst_16n) {
-        g_tls_error = "nb_launch_eyes: null argument";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)cams_16 | (uintptr_t)inst_16n) & 15u) {
-        g_tls_error = "nb_launch_eyes: cams_16 and inst_16n must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    const size_t cells = (size_t)count * width;
-    const ByteRange in[2] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)}};
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {nullptr, 0}, {nullptr, 0}};
-    int rc = eyes_range_check("nb_launch_eyes", n_total, first, count, width, false, flags, &g_tls_error);
-    if (rc == NB_OK) rc = outputs_check("nb_launch_eyes", out, 0x3u, kNoIdsDepth, false, in, 2, kEyesAlias, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    if (count == 0) return NB_OK;
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(inst_16n, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    hipError_t e = nbk::launch_eyes(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags, (uint32_t *)ids,
-                                    (float *)depth, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    static const ViewForm f = {"nb_launch_eyes", false, 0x3u, kNoIdsDepth, false, kAlign16Eyes};
+    return launch_eyes_form(f, n_total, first, count, cams_16, inst_16n, width, flags, nullptr, 0, 0, ids, depth, nullptr, nullptr, stream, [&] {
+        return nbk::launch_eyes(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags, (uint32_t *)ids,
+                                (float *)depth, (hipStream_t)stream);
+    });
 }
 
 NB_EXPORT int nb_launch_eyes_colour(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n,
                                     uint32_t width, uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids, void *depth,
                                     void *rgba, void *bgra8, void *stream)
 {
-    if (!cams_16 || !inst_16n) {
-        g_tls_error = "nb_launch_eyes_colour: null argument";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)cams_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
-        g_tls_error = "nb_launch_eyes_colour: cams_16, inst_16n, skin and rgba must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
-        g_tls_error = "nb_launch_eyes_colour: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
-        return NB_ERR_INVALID;
-    }
-    const ByteRange in[3] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
-                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}};
-    const size_t cells = (size_t)count * width;
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = eyes_range_check("nb_launch_eyes_colour", n_total, first, count, width, false, flags, &g_tls_error);
-    if (rc == NB_OK) rc = outputs_check("nb_launch_eyes_colour", out, 0xCu, kNoColour, true, in, 3, kEyesAlias, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    if (count == 0) return NB_OK;
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(inst_16n, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    hipError_t e = nbk::launch_eyes_colour(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags,
-                                           (const float *)skin, tw, th, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8,
-                                           (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    static const ViewForm f = {"nb_launch_eyes_colour", false, 0xCu, kNoColour, true, kAlign16Colour};
+    return launch_eyes_form(f, n_total, first, count, cams_16, inst_16n, width, flags, skin, tw, th, ids, depth, rgba, bgra8, stream, [&] {
+        return nbk::launch_eyes_colour(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags, (const float *)skin,
+                                       tw, th, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8, (hipStream_t)stream);
+    });
 }
 
 NB_EXPORT int nb_launch_eyes_msaa(uint32_t n_total, uint32_t first, uint32_t count, const void *cams_16, const void *inst_16n,
                                   uint32_t width, uint32_t flags, const void *skin, uint32_t tw, uint32_t th, void *ids8, void *depth8,
                                   void *rgba, void *bgra8, void *stream)
 {
-    if (!cams_16 || !inst_16n) {
-        g_tls_error = "nb_launch_eyes_msaa: null argument";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)cams_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
-        g_tls_error = "nb_launch_eyes_msaa: cams_16, inst_16n, skin and rgba must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
-        g_tls_error = "nb_launch_eyes_msaa: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
-        return NB_ERR_INVALID;
-    }
-    const ByteRange in[3] = {{cams_16, (size_t)count * 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
-                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}};
-    const size_t cells = (size_t)count * width, words = cells * NB_EYES_SAMPLES;
-    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = eyes_range_check("nb_launch_eyes_msaa", n_total, first, count, width, true, flags, &g_tls_error);
-    if (rc == NB_OK) rc = outputs_check("nb_launch_eyes_msaa", out, 0xFu, kNoOutputs8, true, in, 3, kEyesAlias, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    if (count == 0) return NB_OK;
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(inst_16n, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    hipError_t e = nbk::launch_eyes_msaa(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags,
-                                         (const float *)skin, tw, th, (uint32_t *)ids8, (float *)depth8, (float *)rgba, (uint32_t *)bgra8,
-                                         (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: eyes kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    static const ViewForm f = {"nb_launch_eyes_msaa", true, 0xFu, kNoOutputs8, true, kAlign16Colour};
+    return launch_eyes_form(f, n_total, first, count, cams_16, inst_16n, width, flags, skin, tw, th, ids8, depth8, rgba, bgra8, stream, [&] {
+        return nbk::launch_eyes_msaa(n_total, first, count, (const float *)cams_16, (const float *)inst_16n, width, flags, (const float *)skin,
+                                     tw, th, (uint32_t *)ids8, (float *)depth8, (float *)rgba, (uint32_t *)bgra8, (hipStream_t)stream);
+    });
 }
 
 NB_EXPORT int nb_launch_frame(uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height, uint32_t flags,
                               const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids, void *depth, void *rgba, void *bgra8,
                               void *stream)
 {
-    if (!cam_16 || !scratch || (n_total && !inst_16n)) {
-        g_tls_error = "nb_launch_frame: null argument";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)cam_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
-        g_tls_error = "nb_launch_frame: cam_16, inst_16n, skin and rgba must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if ((uintptr_t)scratch & 7u) {
-        g_tls_error = "nb_launch_frame: scratch must be 8-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
-        g_tls_error = "nb_launch_frame: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
-        return NB_ERR_INVALID;
-    }
-    const ByteRange in[4] = {{cam_16, 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
-                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}, {scratch, nb_frame_scratch_bytes(width, height)}};
-    const size_t cells = (size_t)width * height;
-    const ByteRange out[4] = {{ids, cells * 4u}, {depth, cells * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = frame_extent_check("nb_launch_frame", width, height, false, flags, &g_tls_error);
-    if (rc == NB_OK) rc = outputs_check("nb_launch_frame", out, 0xFu, kNoOutputs, true, in, 4, kFrameAlias, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(scratch, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    hipError_t e = nbk::launch_frame(n_total, (const float *)cam_16, (const float *)inst_16n, width, height, (const float *)skin, tw, th,
-                                     (uint64_t *)scratch, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8,
-                                     (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: frame kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    static const ViewForm f = {"nb_launch_frame", false, 0xFu, kNoOutputs, true, kAlign16Frame};
+    return launch_frame_form(f, n_total, cam_16, inst_16n, width, height, flags, skin, tw, th, scratch, ids, depth, rgba, bgra8, stream, [&] {
+        return nbk::launch_frame(n_total, (const float *)cam_16, (const float *)inst_16n, width, height, (const float *)skin, tw, th,
+                                 (uint64_t *)scratch, (uint32_t *)ids, (float *)depth, (float *)rgba, (uint32_t *)bgra8, (hipStream_t)stream);
+    });
 }
 
 NB_EXPORT int nb_launch_frame_msaa(uint32_t n_total, const void *cam_16, const void *inst_16n, uint32_t width, uint32_t height, uint32_t flags,
                                    const void *skin, uint32_t tw, uint32_t th, void *scratch, void *ids8, void *depth8, void *rgba,
                                    void *bgra8, void *stream)
 {
-    if (!cam_16 || !scratch || (n_total && !inst_16n)) {
-        g_tls_error = "nb_launch_frame_msaa: null argument";
-        return NB_ERR_INVALID;
-    }
-    if (((uintptr_t)cam_16 | (uintptr_t)inst_16n | (uintptr_t)skin | (uintptr_t)rgba) & 15u) {
-        g_tls_error = "nb_launch_frame_msaa: cam_16, inst_16n, skin and rgba must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if ((uintptr_t)scratch & 7u) {
-        g_tls_error = "nb_launch_frame_msaa: scratch must be 8-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if (skin && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
-        g_tls_error = "nb_launch_frame_msaa: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
-        return NB_ERR_INVALID;
-    }
-    const ByteRange in[4] = {{cam_16, 16 * sizeof(float)}, {inst_16n, (size_t)n_total * 16 * sizeof(float)},
-                             {skin, skin ? (size_t)tw * th * 4 * sizeof(float) : 0}, {scratch, nb_frame_msaa_scratch_bytes(width, height)}};
-    const size_t cells = (size_t)width * height, words = cells * NB_EYES_SAMPLES;
-    const ByteRange out[4] = {{ids8, words * 4u}, {depth8, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = frame_extent_check("nb_launch_frame_msaa", width, height, true, flags, &g_tls_error);
-    if (rc == NB_OK) rc = outputs_check("nb_launch_frame_msaa", out, 0xFu, kNoOutputs8, true, in, 4, kFrameAlias, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(scratch, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    hipError_t e = nbk::launch_frame_msaa(n_total, (const float *)cam_16, (const float *)inst_16n, width, height, (const float *)skin, tw, th,
-                                          (uint64_t *)scratch, (uint32_t *)ids8, (float *)depth8, (float *)rgba, (uint32_t *)bgra8,
-                                          (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: frame kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    static const ViewForm f = {"nb_launch_frame_msaa", true, 0xFu, kNoOutputs8, true, kAlign16Frame};
+    return launch_frame_form(f, n_total, cam_16, inst_16n, width, height, flags, skin, tw, th, scratch, ids8, depth8, rgba, bgra8, stream, [&] {
+        return nbk::launch_frame_msaa(n_total, (const float *)cam_16, (const float *)inst_16n, width, height, (const float *)skin, tw, th,
+                                      (uint64_t *)scratch, (uint32_t *)ids8, (float *)depth8, (float *)rgba, (uint32_t *)bgra8,
+                                      (hipStream_t)stream);
+    });
 }
 
 NB_EXPORT int nb_launch_random_step(uint32_t first, uint32_t count, void *pos, void *vel, uint64_t seed, uint64_t step, void *stream)

@@ -154,11 +154,7 @@ int update_common(const char *who, bool boids, float *inst, size_t n_inst, float
         g_tls_error = std::string(who) + ": more than 2^32-1 bodies";
         return NB_ERR_INVALID;
     }
-    nb_params p;
-    if (np)
-        p = *np;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(np);
 
     UpdateCache &uc = update_cache();
     std::lock_guard<std::mutex> lock(uc.mu);

@@ -73,7 +73,17 @@ hipError_t launch_strict_pc(const StepArgs &a, uint32_t producers, hipStream_t s
 // block-chain form for small shards: quotients stay in registers, running sums pass from wave to wave; needs scratch
 // `status`: a device word the kernel ORs 1 into when a wave gave up waiting (outputs poisoned): the host's sticky error
 hipError_t launch_strict_bc(const StepArgs &a, void *scratch, uint32_t *status, hipStream_t s);
+// The planes area every form with planes keeps at the start of its scratch: flag words, three zero-padded planes of npad floats,
+// a request's worth of slack.  strict_bc_scratch_bytes() is its size; `behind` is the first byte after it, where a form's own
+// rows start (FAST's partial sums, the pairs forms' rows).
 size_t strict_bc_scratch_bytes(uint32_t n_total);
+struct PlaneScratch {
+    uint32_t *flags;
+    float *px, *py, *pz;
+    char *behind;
+    uint32_t npad;
+};
+PlaneScratch plane_scratch(void *scratch, uint32_t n_total);
 // scalar-load form (nb_nbody_sl.inc): one wave per 64 bodies reads x / y / z planes with scalar loads; same scratch as the block chain
 hipError_t launch_strict_sl(const StepArgs &a, uint32_t shape, void *scratch, hipStream_t s);
 // the kernel alone (nb_kernels.hip -DNBK_SL_TU): flags / planes as planes_kernel left them; shape: see nb_nbody_sl.inc

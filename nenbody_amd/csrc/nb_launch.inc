@@ -1,5 +1,10 @@
 // nb_launch.inc -- host-side launchers (grid shapes, template dispatch).
 // Included by nb_kernels.hip inside namespace nbk; see that file for the compilation scheme.
+//
+// The forms that read x / y / z planes (block chain, scalar loads, pairs, ring) lay them into the caller's scratch.  That layout
+// is stated ONCE: plane_scratch() makes the view (PlaneScratch, nb_kernels.h) and strict_bc_scratch_bytes() gives its size from
+// the same constants; next_plane_generation() stamps a launch's flag words, launch_fast_planes() is FAST's planes launch.  No
+// launcher below computes a scratch offset of its own (the ring phases' flag sub-sets, flags + kRingFlags*, are theirs).
 
 // ------------------------------------------------------------------------------------------------
 // host-side launchers
@@ -59,40 +64,67 @@ hipError_t launch_strict_pc(const StepArgs &a, uint32_t producers, hipStream_t s
 #endif
 }
 
-// flags + three zero-padded planes + one request's worth of slack (the scalar-load kernel requests one group past the last full one)
-size_t strict_bc_scratch_bytes(uint32_t n_total) { return (size_t)kBcFlagsBytes + 3u * (size_t)bc_padded(n_total) * sizeof(float) + 64u; }
+// The planes area: flags + three zero-padded planes + one request's worth of slack (the scalar-load kernel requests one group past
+// the last full one).  Its size and the view into it are made from the same three terms.
+constexpr size_t kPlaneSlackBytes = 64;
+size_t strict_bc_scratch_bytes(uint32_t n_total) { return (size_t)kBcFlagsBytes + 3u * (size_t)bc_padded(n_total) * sizeof(float) + kPlaneSlackBytes; }
+
+PlaneScratch plane_scratch(void *scratch, uint32_t n_total)
+{
+    PlaneScratch v;
+    v.npad = bc_padded(n_total);
+    v.flags = (uint32_t *)scratch;
+    v.px = (float *)((char *)scratch + kBcFlagsBytes);
+    v.py = v.px + v.npad;
+    v.pz = v.py + v.npad;
+    v.behind = (char *)scratch + strict_bc_scratch_bytes(n_total);  // = the end of pz + the slack
+    return v;
+}
+
+// The flag words are stamped with a generation number instead of being cleared (nb_nbody_bc.inc); 0 is what zeroed scratch holds,
+// so no launch is ever given it.
+static std::atomic<uint32_t> g_bc_generation{0};
+static uint32_t next_plane_generation()
+{
+    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
+    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
+    return gen;
+}
+
+// flags + planes of the whole set from the records; [lo_bits, hi_bits]: the magnitudes that leave the "IEEE" flag word clear
+static void enqueue_planes(const StepArgs &a, const PlaneScratch &v, uint32_t lo_bits, uint32_t hi_bits, uint32_t gen, hipStream_t s)
+{
+    hipLaunchKernelGGL(planes_kernel, dim3(ceil_div(v.npad, kBlock)), dim3(kBlock), 0, s, a.n_total, v.npad, a.pos_in, v.px, v.py, v.pz,
+                       v.flags, lo_bits, hi_bits, 0u, gen);
+}
+// FAST's: "IEEE" = a coordinate of 2^28 or more (no shared reciprocal)
+constexpr uint32_t kFastPlaneLoBits = 0u, kFastPlaneHiBits = 0x4d7fffffu;
+static hipError_t launch_fast_planes(const StepArgs &a, const PlaneScratch &v, uint32_t gen, hipStream_t s)
+{
+    enqueue_planes(a, v, kFastPlaneLoBits, kFastPlaneHiBits, gen, s);
+    return hipGetLastError();
+}
 
 // block-chain form: flags + planes from the records (scratch: strict_bc_scratch_bytes), then the step: two launches.
-// The flag words are stamped with a generation number instead of being cleared (nb_nbody_bc.inc).
-static std::atomic<uint32_t> g_bc_generation{0};
-
 hipError_t launch_strict_bc(const StepArgs &a, void *scratch, uint32_t *status, hipStream_t s)
 {
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;  // 0 is what zeroed scratch holds
-    hipLaunchKernelGGL(planes_kernel, dim3(ceil_div(npad, kBlock)), dim3(kBlock), 0, s, a.n_total, npad, a.pos_in, px, py, pz, flags,
-                       a.lo_bits, a.hi_bits, 0u, gen);
-    hipLaunchKernelGGL(step_strict_bc_kernel, dim3(ceil_div(a.count, 64)), dim3(kBcThreads), 0, s, a, (const uint32_t *)flags, gen,
-                       (const float *)px, (const float *)py, (const float *)pz, status);
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
+    const uint32_t gen = next_plane_generation();
+    enqueue_planes(a, v, a.lo_bits, a.hi_bits, gen, s);
+    hipLaunchKernelGGL(step_strict_bc_kernel, dim3(ceil_div(a.count, 64)), dim3(kBcThreads), 0, s, a, (const uint32_t *)v.flags, gen,
+                       (const float *)v.px, (const float *)v.py, (const float *)v.pz, status);
     return hipGetLastError();
 }
 
 // scalar-load form: flags + planes (as for the block chain), then one wave per 64 bodies
 hipError_t launch_strict_sl(const StepArgs &a, uint32_t shape, void *scratch, hipStream_t s)
 {
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;  // 0 is what zeroed scratch holds
-    hipLaunchKernelGGL(planes_kernel, dim3(ceil_div(npad, kBlock)), dim3(kBlock), 0, s, a.n_total, npad, a.pos_in, px, py, pz, flags,
-                       a.lo_bits, a.hi_bits, 0u, gen);
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
+    const uint32_t gen = next_plane_generation();
+    enqueue_planes(a, v, a.lo_bits, a.hi_bits, gen, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_strict_sl_kernel(a, shape, flags, gen, px, py, pz, s);
+    return launch_strict_sl_kernel(a, shape, v.flags, gen, v.px, v.py, v.pz, s);
 }
 
 hipError_t launch_strict(const StepArgs &a, uint32_t tile, uint32_t unroll, uint32_t lanes, hipStream_t s)
@@ -206,17 +238,12 @@ hipError_t launch_fast_wave(const StepArgs &a, uint32_t tile, uint32_t ib, uint3
 hipError_t launch_fast_sl(const StepArgs &a_in, uint32_t ib, uint32_t slices, void *scratch, hipStream_t s)
 {
     StepArgs a = a_in;
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    a.partial = (float4 *)((char *)scratch + strict_bc_scratch_bytes(a.n_total));
-    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    hipLaunchKernelGGL(planes_kernel, dim3(ceil_div(npad, kBlock)), dim3(kBlock), 0, s, a.n_total, npad, a.pos_in, px, py, pz, flags, 0u,
-                       0x4d7fffffu, 0u, gen);
-    hipError_t e = hipGetLastError();
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
+    a.partial = (float4 *)v.behind;
+    const uint32_t gen = next_plane_generation();
+    hipError_t e = launch_fast_planes(a, v, gen, s);
     if (e != hipSuccess) return e;
-    e = launch_fast_sl_kernel(a, ib, slices, flags, gen, px, py, pz, s);
+    e = launch_fast_sl_kernel(a, ib, slices, v.flags, gen, v.px, v.py, v.pz, s);
     if (e != hipSuccess || slices == 1 || a.always_partial) return e;
     return launch_integrate_partials(a, slices, s);
 }
@@ -228,53 +255,39 @@ hipError_t launch_fast_sl_phase(const StepArgs &a_in, uint32_t ib, uint32_t slic
                                 hipStream_t s)
 {
     StepArgs a = a_in;
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    a.partial = (float4 *)((char *)scratch + strict_bc_scratch_bytes(a.n_total));
-    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (range)
-        hipLaunchKernelGGL(planes_range_kernel, dim3(ceil_div(a.n_total, kBlock)), dim3(kBlock), 0, s, a.n_total, a.pos_in, px, py, pz, flags, r0, r1,
-                           a.first, a.first + a.count, 0u, 0x4d7fffffu, 0u, gen);
-    else
-        hipLaunchKernelGGL(planes_kernel, dim3(ceil_div(npad, kBlock)), dim3(kBlock), 0, s, a.n_total, npad, a.pos_in, px, py, pz, flags, 0u,
-                           0x4d7fffffu, 0u, gen);
-    hipError_t e = hipGetLastError();
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
+    a.partial = (float4 *)v.behind;
+    const uint32_t gen = next_plane_generation();
+    hipError_t e;
+    if (range) {
+        hipLaunchKernelGGL(planes_range_kernel, dim3(ceil_div(a.n_total, kBlock)), dim3(kBlock), 0, s, a.n_total, a.pos_in, v.px, v.py, v.pz, v.flags,
+                           r0, r1, a.first, a.first + a.count, kFastPlaneLoBits, kFastPlaneHiBits, 0u, gen);
+        e = hipGetLastError();
+    } else {
+        e = launch_fast_planes(a, v, gen, s);
+    }
     if (e != hipSuccess) return e;
-    return launch_fast_sl_kernel(a, ib, slices, flags, gen, px, py, pz, s);
+    return launch_fast_sl_kernel(a, ib, slices, v.flags, gen, v.px, v.py, v.pz, s);
 }
 
 // FAST, every unordered pair once: planes + flags, the superblocks against themselves, the superblock pairs, the rows' combine
 hipError_t launch_fast_pairs(const StepArgs &a, uint32_t w, uint32_t np, uint32_t chunk, void *scratch, hipStream_t s)
 {
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    float *rows = (float *)((char *)scratch + strict_bc_scratch_bytes(a.n_total));
-    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    hipLaunchKernelGGL(planes_kernel, dim3(ceil_div(npad, kBlock)), dim3(kBlock), 0, s, a.n_total, npad, a.pos_in, px, py, pz, flags, 0u,
-                       0x4d7fffffu, 0u, gen);
-    hipError_t e = hipGetLastError();
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
+    const uint32_t gen = next_plane_generation();
+    hipError_t e = launch_fast_planes(a, v, gen, s);
     if (e != hipSuccess) return e;
-    return launch_fast_pairs_kernels(a, w, np, chunk, flags, gen, px, py, pz, rows, s);
+    return launch_fast_pairs_kernels(a, w, np, chunk, v.flags, gen, v.px, v.py, v.pz, (float *)v.behind, s);
 }
 
 // FAST pairs form on a shard: planes + flags, then the ring's sweeps and reduces (nb_nbody_ring.inc)
 hipError_t launch_fast_ring(const StepArgs &a, uint32_t np, uint32_t ga, uint32_t wpb, void *scratch, float4 *sums, hipStream_t s)
 {
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    float *rows = (float *)((char *)scratch + strict_bc_scratch_bytes(a.n_total));
-    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    hipLaunchKernelGGL(planes_kernel, dim3(ceil_div(npad, kBlock)), dim3(kBlock), 0, s, a.n_total, npad, a.pos_in, px, py, pz, flags, 0u,
-                       0x4d7fffffu, 0u, gen);
-    hipError_t e = hipGetLastError();
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
+    const uint32_t gen = next_plane_generation();
+    hipError_t e = launch_fast_planes(a, v, gen, s);
     if (e != hipSuccess) return e;
-    return launch_fast_ring_kernels(a, np, ga, wpb, flags, gen, px, py, pz, rows, sums, s);
+    return launch_fast_ring_kernels(a, np, ga, wpb, v.flags, gen, v.px, v.py, v.pz, (float *)v.behind, sums, s);
 }
 
 // One PHASE of the same step (nb_nbody_ring.inc "PHASES"): what = 1 the pairs inside the rank's own slot that one round of
@@ -283,22 +296,18 @@ hipError_t launch_fast_ring(const StepArgs &a, uint32_t np, uint32_t ga, uint32_
 hipError_t launch_fast_ring_phase(const StepArgs &a, uint32_t np, uint32_t ga, uint32_t wpb, uint32_t c4_own, uint32_t c4_rest, uint32_t cap, uint32_t what,
                                   void *scratch, float4 *sums, hipStream_t s)
 {
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    float *rows = (float *)((char *)scratch + strict_bc_scratch_bytes(a.n_total));
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
     if (what == 1u || what == 2u) {  // (what == 4: RING_OWN behind a fused finish, which left the own slot's planes and flag words)
-        uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-        if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
+        const uint32_t gen = next_plane_generation();
         const bool own = what == 1u;
         const uint32_t r0 = own ? a.first : 0u, r1 = own ? a.first + a.count : a.n_total;
-        hipLaunchKernelGGL(ring_planes_kernel, dim3(ceil_div(r1 - r0, kBlock)), dim3(kBlock), 0, s, a.n_total, a.pos_in, px, py, pz,
-                           flags + (own ? kRingFlagsNext : kRingFlagsRest), r0, r1, gen, own ? (const uint32_t *)nullptr : flags + kRingFlagsNext,
-                           own ? (uint32_t *)nullptr : flags + kRingFlagsOwn);
+        hipLaunchKernelGGL(ring_planes_kernel, dim3(ceil_div(r1 - r0, kBlock)), dim3(kBlock), 0, s, a.n_total, a.pos_in, v.px, v.py, v.pz,
+                           v.flags + (own ? kRingFlagsNext : kRingFlagsRest), r0, r1, gen, own ? (const uint32_t *)nullptr : v.flags + kRingFlagsNext,
+                           own ? (uint32_t *)nullptr : v.flags + kRingFlagsOwn);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    return launch_ring_phase_kernels(a, np, ga, wpb, c4_own, c4_rest, cap, what, flags, px, py, pz, rows, sums, s);
+    return launch_ring_phase_kernels(a, np, ga, wpb, c4_own, c4_rest, cap, what, v.flags, v.px, v.py, v.pz, (float *)v.behind, sums, s);
 }
 
 // The finish of a step in phases, fused (nb_nbody_ring.inc: ring_finish_phase_kernel): RING_SUMS need not be launched (sums == NULL:
@@ -306,13 +315,9 @@ hipError_t launch_fast_ring_phase(const StepArgs &a, uint32_t np, uint32_t ga, u
 hipError_t launch_fast_ring_finish_phase(const StepArgs &a, uint32_t np, uint32_t ga, uint32_t wpb, uint32_t c4_own, uint32_t c4_rest, uint32_t cap, void *scratch,
                                          const float4 *sums, const float4 *recv, hipStream_t s)
 {
-    const uint32_t npad = bc_padded(a.n_total);
-    uint32_t *flags = (uint32_t *)scratch;
-    float *px = (float *)((char *)scratch + kBcFlagsBytes), *py = px + npad, *pz = py + npad;
-    float *rows = (float *)((char *)scratch + strict_bc_scratch_bytes(a.n_total));
-    uint32_t gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    if (gen == 0u) gen = g_bc_generation.fetch_add(1u, std::memory_order_relaxed) + 1u;
-    return launch_ring_finish_phase_kernel(a, np, ga, wpb, c4_own, c4_rest, cap, flags, px, py, pz, rows, sums, recv, gen, s);
+    const PlaneScratch v = plane_scratch(scratch, a.n_total);
+    return launch_ring_finish_phase_kernel(a, np, ga, wpb, c4_own, c4_rest, cap, v.flags, v.px, v.py, v.pz, (float *)v.behind, sums, recv,
+                                           next_plane_generation(), s);
 }
 
 hipError_t launch_instances(uint32_t count, const float4 *pos, const float4 *vel, float4 *inst, hipStream_t s, uint32_t device_libm)

@@ -52,109 +52,44 @@ size_t ring_scratch_bytes(const RingPlan &rp, uint32_t n_total, uint32_t first, 
 }
 int cached_ring_plan(const nb_params &p, uint32_t n_total, uint32_t first, uint32_t count, const RingPlan **out, std::string *err)
 {
-    struct Entry {
-        bool valid = false;
-        nb_params p{};
-        uint32_t n_total = 0, first = 0, count = 0, generation = 0;
-        RingPlan rp{};
-    };
-    constexpr int kEntries = 2;
-    thread_local Entry cache[kEntries];
-    thread_local int next = 0;
-    const uint32_t gen = overrides().generation;
-    for (int i = 0; i < kEntries; ++i) {
-        const Entry &e = cache[i];
-        if (e.valid && e.n_total == n_total && e.first == first && e.count == count && e.generation == gen && std::memcmp(&e.p, &p, sizeof(p)) == 0) {
-            *out = &e.rp;
-            return NB_OK;
-        }
-    }
-    RingPlan rp;
-    int rc = make_ring_plan(p, n_total, first, count, &rp, err);
-    if (rc != NB_OK) return rc;
-    Entry &e = cache[next];
-    next = (next + 1) % kEntries;
-    e.valid = true;
-    e.p = p;
-    e.n_total = n_total;
-    e.first = first;
-    e.count = count;
-    e.generation = gen;
-    e.rp = rp;
-    *out = &e.rp;
-    return NB_OK;
-}
-nbk::StepArgs ring_step_args(const nb_params &p, const RingPlan &rp, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
-                             void *pos_out, void *vel)
-{
-    nbk::StepArgs a{};
-    a.pos_in = (const float4 *)pos_in;
-    a.pos_out = (float4 *)pos_out;
-    a.vel = (float4 *)vel;
-    a.n_total = n_total;
-    a.first = first;
-    a.count = count;
-    a.dt = p.dt;
-    a.G = p.G;
-    a.bias = p.bias;
-    a.force_ieee = rp.base.force_ieee;
-    a.force_3d = rp.base.force_3d;
-    return a;
+    thread_local PlanCache<PlanKey, RingPlan, 2> cache;
+    return cache.get(plan_key(p, n_total, first, count), out, [&](RingPlan *rp) { return make_ring_plan(p, n_total, first, count, rp, err); });
 }
 int launch_ring_fold_planned(const nb_params &p, const RingPlan &rp, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
                              void *sums, void *scratch, hipStream_t stream, std::string *err)
 {
-    const nbk::StepArgs a = ring_step_args(p, rp, n_total, first, count, pos_in, nullptr, nullptr);
+    const nbk::StepArgs a = step_args(p, rp.base, n_total, first, count, pos_in, nullptr, nullptr);
     hipError_t e = nbk::launch_fast_ring(a, rp.np, rp.ga, rp.wpb, scratch, (float4 *)sums, stream);
-    if (e != hipSuccess) {
-        *err = std::string("nb: kernel launch failed (ring fold): ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(e, "nb: kernel launch failed (ring fold): ", err);
 }
 int launch_ring_phase_planned(const nb_params &p, const RingPlan &rp, uint32_t n_total, uint32_t first, uint32_t count, int phase, const void *pos_in,
                               void *sums, void *scratch, hipStream_t stream, std::string *err)
 {
-    const nbk::StepArgs a = ring_step_args(p, rp, n_total, first, count, pos_in, nullptr, nullptr);
+    const nbk::StepArgs a = step_args(p, rp.base, n_total, first, count, pos_in, nullptr, nullptr);
     hipError_t e = nbk::launch_fast_ring_phase(a, rp.np, rp.ga, rp.wpb, rp.c4_own, rp.c4_rest, rp.cap, (uint32_t)phase, scratch, (float4 *)sums, stream);
-    if (e != hipSuccess) {
-        *err = std::string("nb: kernel launch failed (ring fold, phase ") + std::to_string(phase) + "): " + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    if (e == hipSuccess) return NB_OK;
+    return launch_status(e, ("nb: kernel launch failed (ring fold, phase " + std::to_string(phase) + "): ").c_str(), err);
 }
 int launch_ring_finish_planned(const nb_params &p, const RingPlan &rp, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
                                void *pos_out, void *vel, const void *sums, const void *recv, hipStream_t stream, std::string *err)
 {
-    const nbk::StepArgs a = ring_step_args(p, rp, n_total, first, count, pos_in, pos_out, vel);
+    const nbk::StepArgs a = step_args(p, rp.base, n_total, first, count, pos_in, pos_out, vel);
     hipError_t e = nbk::launch_ring_finish(a, (const float4 *)sums, (const float4 *)recv, rp.partners, stream);
-    if (e != hipSuccess) {
-        *err = std::string("nb: kernel launch failed (ring finish): ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(e, "nb: kernel launch failed (ring finish): ", err);
 }
 int launch_ring_finish_phase_planned(const nb_params &p, const RingPlan &rp, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
                                      void *pos_out, void *vel, const void *sums, const void *recv, void *scratch, hipStream_t stream, std::string *err)
 {
-    const nbk::StepArgs a = ring_step_args(p, rp, n_total, first, count, pos_in, pos_out, vel);
+    const nbk::StepArgs a = step_args(p, rp.base, n_total, first, count, pos_in, pos_out, vel);
     hipError_t e = nbk::launch_fast_ring_finish_phase(a, rp.np, rp.ga, rp.wpb, rp.c4_own, rp.c4_rest, rp.cap, scratch, (const float4 *)sums, (const float4 *)recv,
                                                       stream);
-    if (e != hipSuccess) {
-        *err = std::string("nb: kernel launch failed (ring finish, fused): ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(e, "nb: kernel launch failed (ring finish, fused): ", err);
 }
 }  // namespace
 
 NB_EXPORT int nb_ring_partners(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     const RingPlan *rp = nullptr;
     int rc = cached_ring_plan(p, n_total, first, count, &rp, &g_tls_error);
     if (rc != NB_OK) return rc;
@@ -163,11 +98,7 @@ NB_EXPORT int nb_ring_partners(const nb_params *params, uint32_t n_total, uint32
 
 NB_EXPORT size_t nb_ring_scratch_bytes(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     RingPlan rp;
     std::string err;
     if (make_ring_plan(p, n_total, first, count, &rp, &err) != NB_OK || rp.partners == 0u) return 0;
@@ -177,11 +108,7 @@ NB_EXPORT size_t nb_ring_scratch_bytes(const nb_params *params, uint32_t n_total
 NB_EXPORT int nb_launch_ring_fold(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in, void *sums,
                                   void *scratch, size_t scratch_bytes, void *stream)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     if (!pos_in || !sums || !scratch) {
         g_tls_error = "nb_launch_ring_fold: pos_in, sums and scratch must be non-null";
         return NB_ERR_INVALID;
@@ -197,22 +124,14 @@ NB_EXPORT int nb_launch_ring_fold(const nb_params *params, uint32_t n_total, uin
         g_tls_error = "nb_launch_ring_fold: scratch smaller than nb_ring_scratch_bytes()";
         return NB_ERR_INVALID;
     }
-    rc = check_device(&g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kForNullStream);
     if (rc != NB_OK) return rc;
-    if (!stream) {
-        rc = select_device_of(pos_in, &g_tls_error);
-        if (rc != NB_OK) return rc;
-    }
     return launch_ring_fold_planned(p, *rp, n_total, first, count, pos_in, sums, scratch, (hipStream_t)stream, &g_tls_error);
 }
 
 NB_EXPORT int nb_ring_phased(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     const RingPlan *rp = nullptr;
     int rc = cached_ring_plan(p, n_total, first, count, &rp, &g_tls_error);
     if (rc != NB_OK) return rc;
@@ -222,11 +141,7 @@ NB_EXPORT int nb_ring_phased(const nb_params *params, uint32_t n_total, uint32_t
 NB_EXPORT int nb_launch_ring_fold_phase(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count, int phase, const void *pos_in,
                                         void *sums, void *scratch, size_t scratch_bytes, void *stream)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     if (!pos_in || !sums || !scratch) {
         g_tls_error = "nb_launch_ring_fold_phase: pos_in, sums and scratch must be non-null";
         return NB_ERR_INVALID;
@@ -246,23 +161,15 @@ NB_EXPORT int nb_launch_ring_fold_phase(const nb_params *params, uint32_t n_tota
         g_tls_error = "nb_launch_ring_fold_phase: scratch smaller than nb_ring_scratch_bytes()";
         return NB_ERR_INVALID;
     }
-    rc = check_device(&g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kForNullStream);
     if (rc != NB_OK) return rc;
-    if (!stream) {
-        rc = select_device_of(pos_in, &g_tls_error);
-        if (rc != NB_OK) return rc;
-    }
     return launch_ring_phase_planned(p, *rp, n_total, first, count, phase, pos_in, sums, scratch, (hipStream_t)stream, &g_tls_error);
 }
 
 NB_EXPORT int nb_launch_ring_finish(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
                                     void *pos_out, void *vel, const void *sums, const void *recv, void *stream)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     if (!pos_in || !pos_out || !vel || !sums || !recv || pos_in == pos_out) {
         g_tls_error = "nb_launch_ring_finish: pos_in, pos_out, vel, sums, recv must be non-null and pos_out must not alias pos_in";
         return NB_ERR_INVALID;
@@ -274,23 +181,15 @@ NB_EXPORT int nb_launch_ring_finish(const nb_params *params, uint32_t n_total, u
         g_tls_error = "nb_launch_ring_finish: this shape does not take the pairs form on shards (nb_ring_partners() == 0)";
         return NB_ERR_UNSUPPORTED;
     }
-    rc = check_device(&g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kForNullStream);
     if (rc != NB_OK) return rc;
-    if (!stream) {
-        rc = select_device_of(pos_in, &g_tls_error);
-        if (rc != NB_OK) return rc;
-    }
     return launch_ring_finish_planned(p, *rp, n_total, first, count, pos_in, pos_out, vel, sums, recv, (hipStream_t)stream, &g_tls_error);
 }
 
 NB_EXPORT int nb_launch_ring_finish_phase(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
                                           void *pos_out, void *vel, const void *sums, const void *recv, void *scratch, size_t scratch_bytes, void *stream)
 {
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     if (!pos_in || !pos_out || !vel || !recv || !scratch || pos_in == pos_out) {
         g_tls_error = "nb_launch_ring_finish_phase: pos_in, pos_out, vel, recv, scratch must be non-null and pos_out must not alias pos_in";
         return NB_ERR_INVALID;
@@ -306,11 +205,7 @@ NB_EXPORT int nb_launch_ring_finish_phase(const nb_params *params, uint32_t n_to
         g_tls_error = "nb_launch_ring_finish_phase: scratch smaller than nb_ring_scratch_bytes()";
         return NB_ERR_INVALID;
     }
-    rc = check_device(&g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kForNullStream);
     if (rc != NB_OK) return rc;
-    if (!stream) {
-        rc = select_device_of(pos_in, &g_tls_error);
-        if (rc != NB_OK) return rc;
-    }
     return launch_ring_finish_phase_planned(p, *rp, n_total, first, count, pos_in, pos_out, vel, sums, recv, scratch, (hipStream_t)stream, &g_tls_error);
 }

@@ -37,17 +37,11 @@ NB_EXPORT int nb_launch_seen(uint32_t count, uint32_t width, const void *ids_row
     if (rc == NB_OK) rc = outputs_check("nb_launch_seen", out, 0xFu, kNoSeenOutputs, true, in, 2, kSeenAlias, &g_tls_error);
     if (rc != NB_OK) return rc;
     if (count == 0) return NB_OK;
-    rc = check_device(&g_tls_error);
+    rc = device_for_launch(ids_rows, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    rc = select_device_of(ids_rows, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    hipError_t e = nbk::launch_seen(count, width, (const uint32_t *)ids_rows, (const float *)depth_rows, (uint32_t *)seen_count,
-                                    (uint32_t *)seen_ids, (float *)seen_depth, (uint32_t *)seen_cols, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: seen kernel launch failed: ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(nbk::launch_seen(count, width, (const uint32_t *)ids_rows, (const float *)depth_rows, (uint32_t *)seen_count,
+                                          (uint32_t *)seen_ids, (float *)seen_depth, (uint32_t *)seen_cols, (hipStream_t)stream),
+                         "nb: seen kernel launch failed: ", &g_tls_error);
 }
 
 // the context's list rows for `eyes` eyes of `cells` slots together (depth / cols: wanted or not)
@@ -102,11 +96,7 @@ NB_EXPORT int nb_launch_boids_seen_step(const nb_boids_params *params, uint32_t 
                                         const void *vel_in, const void *seen_count, const void *seen_ids, uint32_t stride, void *pos_out,
                                         void *vel_out, void *stream)
 {
-    nb_boids_params p;
-    if (params)
-        p = *params;
-    else
-        nb_boids_default_params(&p);
+    const nb_boids_params p = boids_params_or_default(params);
     if (!pos_in || !vel_in || !pos_out || !vel_out || !seen_count || !seen_ids || pos_in == pos_out || vel_in == vel_out) {
         g_tls_error = "nb_launch_boids_seen_step: buffers must be non-null and the outputs must not alias the inputs";
         return NB_ERR_INVALID;
@@ -131,20 +121,14 @@ NB_EXPORT int nb_launch_boids_seen_step(const nb_boids_params *params, uint32_t 
                 g_tls_error = "nb_launch_boids_seen_step: the outputs must not alias the lists";
                 return NB_ERR_INVALID;
             }
-    rc = check_device(&g_tls_error);
-    if (rc != NB_OK) return rc;
-    rc = select_device_of(pos_in, &g_tls_error);
+    rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
     a.pos_in = (const float4 *)pos_in;
     a.vel_in = (const float4 *)vel_in;
     a.pos_out = (float4 *)pos_out;
     a.vel_out = (float4 *)vel_out;
-    hipError_t e = nbk::launch_boids_seen(a, (const uint32_t *)seen_count, (const uint32_t *)seen_ids, stride, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_tls_error = std::string("nb: boids kernel launch failed (seen form): ") + hipGetErrorString(e);
-        return NB_ERR_HIP;
-    }
-    return NB_OK;
+    return launch_status(nbk::launch_boids_seen(a, (const uint32_t *)seen_count, (const uint32_t *)seen_ids, stride, (hipStream_t)stream),
+                         "nb: boids kernel launch failed (seen form): ", &g_tls_error);
 }
 
 NB_EXPORT int nb_step_boids_seen(nb_ctx *ctx, uint32_t k, const nb_boids_params *params, const float *up_xyz, const float *cp16,
@@ -164,11 +148,7 @@ NB_EXPORT int nb_step_boids_seen(nb_ctx *ctx, uint32_t k, const nb_boids_params 
         ctx->err = "nb_step_boids_seen: no state uploaded (call nb_upload first)";
         return NB_ERR_STATE;
     }
-    nb_boids_params p;
-    if (params)
-        p = *params;
-    else
-        nb_boids_default_params(&p);
+    const nb_boids_params p = boids_params_or_default(params);
     nbk::BoidsArgs a;
     uint32_t tile = 0;
     rc = make_boids_args(p, ctx->n, 0, ctx->n, &a, &tile, &ctx->err);

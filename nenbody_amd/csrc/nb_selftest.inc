@@ -8,11 +8,7 @@ NB_EXPORT int nb_selftest_divide(const nb_params *params, uint64_t pairs, uint64
         g_tls_error = "nb_selftest_divide: mismatches is null";
         return NB_ERR_INVALID;
     }
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    nb_params p = params_or_default(params);
     p.mode = NB_MODE_STRICT;
     Plan pl;
     int rc = make_plan(p, 1024, 1024, &pl, &g_tls_error);
@@ -340,11 +336,7 @@ NB_EXPORT int nb_diag_step_clock(const nb_params *params, uint32_t n, double sec
         g_tls_error = "nb_diag_step_clock: need clock_mhz != NULL, n > 0 and 0 < seconds <= 5";
         return NB_ERR_INVALID;
     }
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    nb_params p = params_or_default(params);
     Plan pl;
     int rc = make_plan(p, n, n, &pl, &g_tls_error);
     if (rc != NB_OK) return rc;
@@ -386,19 +378,11 @@ NB_EXPORT int nb_diag_step_clock(const nb_params *params, uint32_t n, double sec
             // the stamped step: the same launch with StepArgs::stamps set
             if (rc == NB_OK) e = hipEventRecord(e0, c->stream);
             if (rc == NB_OK && e == hipSuccess) {
-                nbk::StepArgs a{};
-                a.pos_in = c->pos[c->cur];
-                a.pos_out = c->pos[c->cur ^ 1];
-                a.vel = c->vel;
+                nbk::StepArgs a = step_args(p, pl, n, 0, n, c->pos[c->cur], c->pos[c->cur ^ 1], c->vel);
                 a.partial = (float4 *)c->scratch;
-                a.n_total = a.count = a.j_count = n;
-                a.dt = p.dt;
-                a.G = p.G;
-                a.bias = p.bias;
+                a.j_count = n;
                 a.lo_bits = pl.lo_bits;
                 a.hi_bits = pl.hi_bits;
-                a.force_ieee = pl.force_ieee;
-                a.force_3d = pl.force_3d;
                 a.j_chunk = pl.j_chunk;
                 a.no_packed = pl.no_packed;
                 a.hole_lo = 0xffffffffu;

@@ -331,11 +331,7 @@ NB_EXPORT int nb_shard_create(uint32_t n, int rank, int world, const nb_params *
         g_tls_error = "nb_shard_create: need n > 0 and 0 <= rank < world";
         return NB_ERR_INVALID;
     }
-    nb_params p;
-    if (params)
-        p = *params;
-    else
-        nb_default_params(&p);
+    const nb_params p = params_or_default(params);
     const uint32_t slot = (uint32_t)(((uint64_t)n + (uint32_t)world - 1u) / (uint32_t)world);
     const uint64_t lo = (uint64_t)rank * slot;
     const uint32_t first = lo < n ? (uint32_t)lo : n;
@@ -1037,11 +1033,7 @@ NB_EXPORT int nb_shard_step_boids(nb_shard *sh, uint32_t k, const nb_boids_param
     sh->own_ready = false;
     rc = shard_join_exchange(sh);
     if (rc != NB_OK) return rc;
-    nb_boids_params bp;
-    if (params)
-        bp = *params;
-    else
-        nb_boids_default_params(&bp);
+    const nb_boids_params bp = boids_params_or_default(params);
     const size_t padded = (size_t)sh->slot * sh->world * sizeof(float4);
     const size_t lo = (size_t)sh->rank * sh->slot;
     for (int i = 0; i < 2; ++i)

@@ -11,6 +11,7 @@ torch is plumbing here: device buffers, the stream, the collective.  The step it
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import time
 from typing import List, Optional, Tuple
@@ -50,27 +51,31 @@ class HipBackend:
     def scratch_bytes(self, params: NbParams, n_total: int, count: int) -> int:
         return int(self.lib.nb_scratch_bytes(ctypes.byref(params), n_total, count))
 
-    def step(self, params, n_total, first, count, pos_in, pos_out, vel, scratch) -> None:
+    @staticmethod
+    def _launch(anchor, call, scope=True) -> None:
+        """One launch-API call for the buffers `anchor` stands for: ``call(stream)``, the stream being torch's current one on the
+        anchor's device, its status checked.  scope: with that device current over the call (the launch and the device status
+        word belong to the buffers' device); the entries that select the device themselves go without."""
         import torch
 
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
+        stream = torch.cuda.current_stream(anchor.device).cuda_stream
+        with torch.cuda.device(anchor.device) if scope else contextlib.nullcontext():
+            check(call(stream))
+
+    def step(self, params, n_total, first, count, pos_in, pos_out, vel, scratch) -> None:
         sp = scratch.data_ptr() if scratch is not None and scratch.numel() else None
         sb = scratch.numel() if scratch is not None else 0
-        with torch.cuda.device(pos_in.device):   # the launch and the device status word belong to the buffers' device
-            check(self.lib.nb_launch_step(ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), pos_out.data_ptr(),
-                                          vel.data_ptr(), sp, sb, stream))
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_step(
+            ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), pos_out.data_ptr(), vel.data_ptr(), sp, sb, stream))
 
     def scratch_bytes_phased(self, params: NbParams, n_total: int, count: int, j_lo: int, j_hi: int) -> int:
         return int(self.lib.nb_scratch_bytes_phased(ctypes.byref(params), n_total, count, j_lo, j_hi))
 
     def step_phase(self, params, n_total, first, count, j_lo, j_hi, phase, pos_in, pos_out, vel, scratch) -> None:
         """FAST only: ``nb_launch_step_phase`` -- phase 0 folds records [j_lo, j_hi), phase 1 the rest and integrates."""
-        import torch
-
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
-        with torch.cuda.device(pos_in.device):
-            check(self.lib.nb_launch_step_phase(ctypes.byref(params), n_total, first, count, j_lo, j_hi, phase, pos_in.data_ptr(),
-                                                pos_out.data_ptr(), vel.data_ptr(), scratch.data_ptr(), scratch.numel(), stream))
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_step_phase(
+            ctypes.byref(params), n_total, first, count, j_lo, j_hi, phase, pos_in.data_ptr(), pos_out.data_ptr(), vel.data_ptr(),
+            scratch.data_ptr(), scratch.numel(), stream))
 
     # -- FAST on shards, every unordered pair once ("half shell": nb_launch_ring_fold / _finish, include/nenbody.h) ----------
     def ring_partners(self, params: NbParams, n_total: int, first: int, count: int) -> int:
@@ -84,12 +89,8 @@ class HipBackend:
         return int(self.lib.nb_ring_scratch_bytes(ctypes.byref(params), n_total, first, count))
 
     def ring_fold(self, params, n_total, first, count, pos_in, sums, scratch) -> None:
-        import torch
-
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
-        with torch.cuda.device(pos_in.device):
-            check(self.lib.nb_launch_ring_fold(ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), sums.data_ptr(),
-                                               scratch.data_ptr(), scratch.numel(), stream))
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_ring_fold(
+            ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), sums.data_ptr(), scratch.data_ptr(), scratch.numel(), stream))
 
     def ring_phased(self, params: NbParams, n_total: int, first: int, count: int) -> bool:
         """can this shape run its step in phases (``nb_launch_ring_fold_phase``: both exchanges behind compute)?"""
@@ -101,46 +102,31 @@ class HipBackend:
     def ring_fold_phase(self, params, n_total, first, count, phase, pos_in, sums, scratch) -> None:
         """one phase of the fold: NB_RING_OWN reads only the rank's own slot of pos_in, NB_RING_REST the whole snapshot (and leaves
         the sums of the ranks in front final), NB_RING_SUMS makes the rank's own sums"""
-        import torch
-
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
-        with torch.cuda.device(pos_in.device):
-            check(self.lib.nb_launch_ring_fold_phase(ctypes.byref(params), n_total, first, count, int(phase), pos_in.data_ptr(),
-                                                     sums.data_ptr(), scratch.data_ptr(), scratch.numel(), stream))
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_ring_fold_phase(
+            ctypes.byref(params), n_total, first, count, int(phase), pos_in.data_ptr(), sums.data_ptr(), scratch.data_ptr(),
+            scratch.numel(), stream))
 
     def ring_finish(self, params, n_total, first, count, pos_in, pos_out, vel, sums, recv) -> None:
-        import torch
-
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
-        with torch.cuda.device(pos_in.device):
-            check(self.lib.nb_launch_ring_finish(ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), pos_out.data_ptr(),
-                                                 vel.data_ptr(), sums.data_ptr(), recv.data_ptr(), stream))
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_ring_finish(
+            ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), pos_out.data_ptr(), vel.data_ptr(), sums.data_ptr(),
+            recv.data_ptr(), stream))
 
     def ring_finish_phase(self, params, n_total, first, count, pos_in, pos_out, vel, sums, recv, scratch) -> None:
         """the finish of a step in phases, fused (``nb_launch_ring_finish_phase``): with ``sums`` None it adds the rank's own
         records itself (NB_RING_SUMS is not launched); it leaves the planes of the new own slot in ``scratch``, so the next step
         starts with NB_RING_OWN_READY"""
-        import torch
-
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
-        with torch.cuda.device(pos_in.device):
-            check(self.lib.nb_launch_ring_finish_phase(ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), pos_out.data_ptr(),
-                                                       vel.data_ptr(), sums.data_ptr() if sums is not None else None, recv.data_ptr(),
-                                                       scratch.data_ptr(), scratch.numel(), stream))
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_ring_finish_phase(
+            ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), pos_out.data_ptr(), vel.data_ptr(),
+            sums.data_ptr() if sums is not None else None, recv.data_ptr(), scratch.data_ptr(), scratch.numel(), stream))
 
     def instances(self, count, pos, vel, inst) -> None:
-        import torch
-
-        stream = torch.cuda.current_stream(pos.device).cuda_stream
-        check(self.lib.nb_launch_instances(count, pos.data_ptr(), vel.data_ptr(), inst.data_ptr(), stream))
+        self._launch(pos, lambda stream: self.lib.nb_launch_instances(count, pos.data_ptr(), vel.data_ptr(), inst.data_ptr(), stream),
+                     scope=False)
 
     def boids_step(self, params, n_total, first, count, pos_in, vel_in, pos_out, vel_out) -> None:
-        import torch
-
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
-        check(self.lib.nb_launch_boids_step(ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), vel_in.data_ptr(),
-                                            pos_out.data_ptr(), vel_out.data_ptr(), stream))
-
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_boids_step(
+            ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), vel_in.data_ptr(), pos_out.data_ptr(), vel_out.data_ptr(),
+            stream), scope=False)
 
     def boids_split_scratch_bytes(self, params, n_total, count) -> int:
         return int(self.lib.nb_boids_split_scratch_bytes(ctypes.byref(params), n_total, count))
@@ -148,11 +134,9 @@ class HipBackend:
     def boids_step_split(self, params, n_total, first, count, pos_in, vel_in, pos_out, vel_out, scratch) -> None:
         """the boids step with the j range in slices (``nb_launch_boids_step_split``): the reference's neighbour sets and counts,
         reassociated sums -- the form that lets a small shard fill the chip"""
-        import torch
-
-        stream = torch.cuda.current_stream(pos_in.device).cuda_stream
-        check(self.lib.nb_launch_boids_step_split(ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), vel_in.data_ptr(),
-                                                  pos_out.data_ptr(), vel_out.data_ptr(), scratch.data_ptr(), scratch.numel(), stream))
+        self._launch(pos_in, lambda stream: self.lib.nb_launch_boids_step_split(
+            ctypes.byref(params), n_total, first, count, pos_in.data_ptr(), vel_in.data_ptr(), pos_out.data_ptr(), vel_out.data_ptr(),
+            scratch.data_ptr(), scratch.numel(), stream), scope=False)
 
 
 class ShardedScene:
