@@ -117,11 +117,12 @@ def colour(cams, inst, first, width, see_self=False, skin=None, chunk=8, stats=N
     """The rule, steps 1-11, for eyes first .. first + len(cams) - 1 over every body of `inst`; skin: (th, tw, 4) linear float32,
     row 0 first (None: 1 x 1 white).  Returns (ids, depth, rgba float32 (E, width, 4), bgra8 uint32 (E, width)).
     `stats`, a dict, collects over calls: columns won by each edge ("edge"), winning columns whose edge has unequal end w
-    ("unequal_w"), whose edge was cut where it enters ("s0>0"), and the columns that see a body ("covered") of "columns"."""
+    ("unequal_w"), whose edge was cut where it enters ("s0>0"), and the columns that see a body ("covered") of "columns"; and what
+    eyes_restatement.eyes counts."""
     cams = np.ascontiguousarray(cams, np.float32).reshape(-1, 4, 4)
     skin = WHITE if skin is None else np.ascontiguousarray(skin, np.float32)
     th, tw = skin.shape[:2]
-    ids, depth = R.eyes(cams, inst, first, width, see_self, chunk)
+    ids, depth = R.eyes(cams, inst, first, width, see_self, chunk, stats)
     E = len(cams)
     rgba = np.empty((E, width, 4), np.float32)
     rgba[:] = CLEAR                                                            # step 11

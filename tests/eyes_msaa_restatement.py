@@ -16,10 +16,10 @@ SAMPLES = 8
 OFFSETS = np.array([9, 7, 13, 5, 3, 1, 11, 15], np.float32) / F(16)
 
 
-def _sample_keys(cams, world, first, width, see_self):
+def _sample_keys(cams, world, first, width, see_self, stats=None):
     """M2: steps 3-5 with xc replaced by x_k = c + o_k.  (E, width, 8) uint64 keys, R.EMPTY where no candidate covers the sample."""
     E, n = len(cams), len(world)
-    keep, xs0, d0, xs1, d1 = R.segments(cams, world, width)
+    keep, xs0, d0, xs1, d1 = R.segments(cams, world, width, stats)
     if not see_self:
         own = first + np.arange(E)
         ok = own < n
@@ -48,7 +48,11 @@ def _sample_keys(cams, world, first, width, see_self):
         t = (x - s0) / (s1 - s0)
         d = e0 + t * (e1 - e0)
         cand = covered & (d < F(1))
+        far = covered & (d >= F(1))
         d = np.where(d > 0, d, F(0)).astype(np.float32)    # !(d > 0) -> +0
+    if stats is not None:
+        stats["rejected_far"] = stats.get("rejected_far", 0) + int(far.sum())
+        stats["widest"] = max(stats.get("widest", 0), int(np.bincount(seg[cand.any(1)], minlength=1).max()))
     key = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | j_idx[seg].astype(np.uint64)[:, None]
     slot = ((e_idx[seg] * width + col) * SAMPLES)[:, None] + np.arange(SAMPLES)[None, :]
     np.minimum.at(keys, slot[cand], key[cand])
@@ -116,8 +120,9 @@ def msaa(cams, inst, first, width, see_self=False, skin=None, chunk=8, stats=Non
     `stats`, a dict, collects over calls: "covered_hist" (9 entries: columns by their number of covered samples), "two_bodies"
     (columns whose samples name two bodies or more), "two_bodies_full" (those of them with all eight samples covered),
     "empty_centre" (columns with a covered sample whose one-sample rule at the centre finds nothing), "extrapolated" (samples whose
-    fragment is shaded outside its edge's span), "edge" (samples per winning edge), "columns"; and of the last call "edge8",
-    (E, width, 8), the winning edge per sample, -1 where empty."""
+    fragment is shaded outside its edge's span), "edge" (samples per winning edge), "columns", what eyes_restatement.segments
+    counts, "rejected_far" (covered samples of a segment whose depth is >= 1: no candidate) and "widest" (the most columns with a
+    candidate sample of one segment); and of the last call "edge8", (E, width, 8), the winning edge per sample, -1 where empty."""
     cams = np.ascontiguousarray(cams, np.float32).reshape(-1, 4, 4)
     skin = K.WHITE if skin is None else np.ascontiguousarray(skin, np.float32)
     world = R.world_vertices(inst)
@@ -129,7 +134,7 @@ def msaa(cams, inst, first, width, see_self=False, skin=None, chunk=8, stats=Non
     extrapolated = 0
     for e0 in range(0, E, chunk):
         e1 = min(E, e0 + chunk)
-        keys = _sample_keys(cams[e0:e1], world, first + e0, width, see_self)
+        keys = _sample_keys(cams[e0:e1], world, first + e0, width, see_self, stats)
         none = keys == R.EMPTY
         ids8[e0:e1] = np.where(none, np.uint32(R.NONE), (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32))
         depth8[e0:e1] = np.where(none, F(1), (keys >> np.uint64(32)).astype(np.uint32).view(np.float32))

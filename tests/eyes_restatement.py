@@ -55,8 +55,9 @@ def world_vertices(inst):
     """(n, 3, 4): w_r = ((M[r]*a.x + M[4+r]*a.y) + M[8+r]*a.z) + M[12+r]*a.w for the three model vertices."""
     m = np.ascontiguousarray(inst, np.float32).reshape(-1, 4, 4)      # m[:, k, r] = row r of column k
     out = np.empty((len(m), 3, 4), np.float32)
-    for v, a in enumerate(VERTS):
-        out[:, v, :] = ((m[:, 0, :] * a[0] + m[:, 1, :] * a[1]) + m[:, 2, :] * a[2]) + m[:, 3, :] * a[3]
+    with np.errstate(all="ignore"):                                   # (an infinite entry times zero is a NaN, silently)
+        for v, a in enumerate(VERTS):
+            out[:, v, :] = ((m[:, 0, :] * a[0] + m[:, 1, :] * a[1]) + m[:, 2, :] * a[2]) + m[:, 3, :] * a[3]
     return out
 
 
@@ -65,11 +66,14 @@ def clip_vertices(cams, world):
     c = np.ascontiguousarray(cams, np.float32).reshape(-1, 4, 4)
     cc = [c[:, k, None, None, :] for k in range(4)]                  # (E, 1, 1, 4): column k, rows r
     w = [world[None, :, :, k, None] for k in range(4)]               # (1, n, 3, 1)
-    return ((cc[0] * w[0] + cc[1] * w[1]) + cc[2] * w[2]) + cc[3] * w[3]
+    with np.errstate(all="ignore"):
+        return ((cc[0] * w[0] + cc[1] * w[1]) + cc[2] * w[2]) + cc[3] * w[3]
 
 
-def segments(cams, world, width):
-    """Clipped, projected edges: (keep, xs0, d0, xs1, d1), each (E, n, 3)."""
+def segments(cams, world, width, stats=None):
+    """Clipped, projected edges: (keep, xs0, d0, xs1, d1), each (E, n, 3).  `stats`, a dict, collects over calls: "cut" (4 entries:
+    kept edges that boundary B1 .. B4 cuts -- one end outside it, the other not) and "w_dropped" (edges that pass the clip and are
+    dropped for an end with w <= 0)."""
     P = clip_vertices(cams, world)
     P0 = P[:, :, [a for a, _ in EDGES], :]
     P1 = P[:, :, [b for _, b in EDGES], :]
@@ -82,18 +86,24 @@ def segments(cams, world, width):
             y, z, w = p[..., 1], p[..., 2], p[..., 3]
             return (z, w - z, w + y, w - y)          # near, far, y = -w, y = +w
 
+        crossed = []
         for b0, b1 in zip(bounds(P0), bounds(P1)):
             keep &= ~((b0 < 0) & (b1 < 0))
             r = b0 / (b0 - b1)
             enter = (b0 < 0) & (b1 >= 0)
             leave = (b1 < 0) & (b0 >= 0)
+            crossed.append(enter | leave)
             t_in = np.where(enter & (r > t_in), r, t_in)       # max(t_in, r); a NaN r changes nothing
             t_out = np.where(leave & (r < t_out), r, t_out)    # min(t_out, r)
         keep &= ~(t_in > t_out)
         D = P1 - P0
         Q0 = np.where((t_in > 0)[..., None], P0 + t_in[..., None] * D, P0)
         Q1 = np.where((t_out < 1)[..., None], P0 + t_out[..., None] * D, P1)
-        keep &= (Q0[..., 3] > 0) & (Q1[..., 3] > 0)
+        positive = (Q0[..., 3] > 0) & (Q1[..., 3] > 0)
+        if stats is not None:
+            stats["w_dropped"] = stats.get("w_dropped", 0) + int((keep & ~positive).sum())
+            stats["cut"] = stats.get("cut", np.zeros(4, np.int64)) + np.array([int((keep & positive & c).sum()) for c in crossed])
+        keep &= positive
         h = F(width) * F(0.5)
         xs0 = (Q0[..., 0] / Q0[..., 3]) * h + h
         xs1 = (Q1[..., 0] / Q1[..., 3]) * h + h
@@ -102,9 +112,11 @@ def segments(cams, world, width):
     return keep, xs0, d0, xs1, d1
 
 
-def eyes(cams, inst, first, width, see_self=False, chunk=8):
+def eyes(cams, inst, first, width, see_self=False, chunk=8, stats=None):
     """The rule for eyes first .. first + len(cams) - 1 (eye e is body first + e) over every body of `inst`.
-    Returns (ids uint32 (E, width), depth float32 (E, width))."""
+    Returns (ids uint32 (E, width), depth float32 (E, width)).  `stats`, a dict, collects over calls what `segments` counts and
+    "rejected_far" (covered columns of a segment whose depth is >= 1: no candidate) and "widest" (the most candidate columns of one
+    segment)."""
     cams = np.ascontiguousarray(cams, np.float32).reshape(-1, 4, 4)
     world = world_vertices(inst)
     E = len(cams)
@@ -112,16 +124,16 @@ def eyes(cams, inst, first, width, see_self=False, chunk=8):
     depth = np.empty((E, width), np.float32)
     for e0 in range(0, E, chunk):
         e1 = min(E, e0 + chunk)
-        keys = _resolve(cams[e0:e1], world, first + e0, width, see_self)
+        keys = _resolve(cams[e0:e1], world, first + e0, width, see_self, stats)
         none = keys == EMPTY
         ids[e0:e1] = np.where(none, np.uint32(NONE), (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32))
         depth[e0:e1] = np.where(none, F(1), (keys >> np.uint64(32)).astype(np.uint32).view(np.float32))
     return ids, depth
 
 
-def _resolve(cams, world, first, width, see_self):
+def _resolve(cams, world, first, width, see_self, stats=None):
     E, n = len(cams), len(world)
-    keep, xs0, d0, xs1, d1 = segments(cams, world, width)
+    keep, xs0, d0, xs1, d1 = segments(cams, world, width, stats)
     if not see_self:
         own = first + np.arange(E)
         ok = own < n
@@ -150,7 +162,11 @@ def _resolve(cams, world, first, width, see_self):
         t = (xc - s0) / (s1 - s0)
         d = e0 + t * (e1 - e0)
         cand = covered & (d < F(1))
+        far = covered & (d >= F(1))
         d = np.where(d > 0, d, F(0))                       # !(d > 0) -> +0
+    if stats is not None:
+        stats["rejected_far"] = stats.get("rejected_far", 0) + int(far.sum())
+        stats["widest"] = max(stats.get("widest", 0), int(np.bincount(seg[cand], minlength=1).max()))
     key = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | j_idx[seg].astype(np.uint64)
     slot = e_idx[seg] * width + col
     np.minimum.at(keys, slot[cand], key[cand])

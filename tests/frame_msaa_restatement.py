@@ -18,10 +18,11 @@ OX = np.array([9, 7, 13, 5, 3, 1, 11, 15], np.float32) / F(16)
 OY = np.array([5, 11, 9, 3, 13, 7, 15, 1], np.float32) / F(16)
 
 
-def _sample(e, idx, m, k, W):
+def _sample(e, idx, m, k, W, far=None):
     """FM2 for sample k of step m along the major axis of edge idx (arrays that broadcast against each other): (ok, pixel, d, t_c,
     centre) -- ok: the sample is tried, lands in a pixel and its depth is a candidate; pixel = row * W + column; d after the clamp
-    to +0; t_c: FM4's parameter of the centre of step m; centre: that centre lies inside the edge's span."""
+    to +0; t_c: FM4's parameter of the centre of step m; centre: that centre lies inside the edge's span.  far, a list, receives
+    the samples that land in a pixel with a depth >= 1: no candidate."""
     with np.errstate(all="ignore"):
         xm = e["xmajor"][idx]
         oa, ob = np.where(xm, OX[k], OY[k]), np.where(xm, OY[k], OX[k])
@@ -35,6 +36,8 @@ def _sample(e, idx, m, k, W):
         ek = o + q
         ok = ok & (ek >= 0) & (ek < e["blim"][idx])                                          # a NaN covers nothing
         d = e["d0"][idx] + t * (e["d1"][idx] - e["d0"][idx])
+        if far is not None:
+            far.append(ok & (d >= F(1)))
         ok = ok & (d < F(1))
         d = np.where(d > 0, d, F(0)).astype(F)                                               # !(d > 0) -> +0
         f = np.where(ok, np.floor(ek), 0).astype(np.int64)
@@ -70,8 +73,10 @@ def frame_msaa(cam, inst, W, H, skin=None, stats=None):
     "two_bodies" (pixels whose samples name two bodies or more), "empty_centre" (pixels with a covered sample where the one-sample
     rule F1-F6 finds nothing), "centre_only" (pixels the one-sample rule covers that have no covered sample), "extrapolated"
     (samples whose fragment is shaded at a centre outside its edge's span), "edge" (samples per winning edge), "edge8" ((H, W, 8),
-    the winning edge per sample, -1 where empty) and "one" ((H, W) bool: all eight samples covered by one (body, edge), which is
-    also the one-sample rule's winner and edge there)."""
+    the winning edge per sample, -1 where empty), "one" ((H, W) bool: all eight samples covered by one (body, edge), which is
+    also the one-sample rule's winner and edge there), "cut", "w_dropped" (as frame_restatement.frame's), "rejected_far" (samples
+    that land in a pixel with a depth >= 1) and "longest_x" / "longest_y" (the most major-axis steps with a candidate sample of one
+    x-major / y-major edge)."""
     inst = np.ascontiguousarray(inst, F).reshape(-1, 4, 4)
     skin = K.WHITE if skin is None else np.ascontiguousarray(skin, F)
     th, tw = skin.shape[:2]
@@ -79,7 +84,7 @@ def frame_msaa(cam, inst, W, H, skin=None, stats=None):
     e = FR.edges(cam, inst, W, H)
     keys = np.full(W * H * SAMPLES, R.EMPTY, np.uint64)
     ks = np.arange(SAMPLES)
-    writes = 0
+    writes = rejected_far = longest_x = longest_y = 0
     with np.errstate(all="ignore"):
         amin, amax = np.minimum(e["a0"], e["a1"]), np.maximum(e["a0"], e["a1"])              # (a NaN end: NaN, dropped next)
         live = e["keep"] & (amin <= amax)
@@ -93,7 +98,11 @@ def frame_msaa(cam, inst, W, H, skin=None, stats=None):
     if total:
         idx = np.repeat(np.arange(3 * n), span)
         m = np.arange(total) - np.repeat(np.cumsum(span) - span, span) + lo[idx]
-        ok, pixel, d, _, _ = _sample(e, idx[:, None], m[:, None], ks[None, :], W)            # FM2
+        far = []
+        ok, pixel, d, _, _ = _sample(e, idx[:, None], m[:, None], ks[None, :], W, far)       # FM2
+        rejected_far = int(far[0].sum())
+        per_edge = np.bincount(idx[ok.any(1)], minlength=3 * n)                              # steps with a candidate sample
+        longest_x, longest_y = int(per_edge[e["xmajor"]].max(initial=0)), int(per_edge[~e["xmajor"]].max(initial=0))
         key = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (idx // 3).astype(np.uint64)[:, None]
         slot = pixel * SAMPLES + ks[None, :]
         np.minimum.at(keys, slot[ok], key[ok])
@@ -162,6 +171,8 @@ def frame_msaa(cam, inst, W, H, skin=None, stats=None):
         edge1 = centre_edges(e, ids1, depth1, W)
         stats.update(writes=writes, covered_hist=np.bincount(cnt.ravel(), minlength=9), two_bodies=int(((cnt > 0) & (low != high)).sum()),
                      empty_centre=int(((ids1 == R.NONE) & (cnt > 0)).sum()), centre_only=int(((ids1 != R.NONE) & (cnt == 0)).sum()),
+                     cut=(e["cut"] & e["keep"][:, None]).sum(0).astype(np.int64), w_dropped=int(e["w_dropped"].sum()),
+                     rejected_far=rejected_far, longest_x=longest_x, longest_y=longest_y,
                      extrapolated=extrapolated, edge=np.bincount(edge8[edge8 >= 0].astype(np.int64), minlength=3), edge8=edge8,
                      one=(cnt == SAMPLES) & (low == high) & (low == ids1) & (edge8.min(-1) == edge8.max(-1)) & (edge8[..., 0] == edge1))
     return ids8, depth8, rgba.reshape(H, W, 4), K.pack_bgra8(rgba).reshape(H, W)

@@ -28,21 +28,25 @@ def ortho_camera(W, H, sx=1, sy=1):
 
 def edges(cam, inst, W, H):
     """F1-F3 for the 3n edges of n bodies, edge 3 j + k = edge k of body j: a dict of (3n,) arrays -- keep, the clip parameters and
-    the clipped ends' w (section 10 step 7 needs them), the projected ends (xs, ys, d), and `outside`: an end lies outside a plane."""
+    the clipped ends' w (section 10 step 7 needs them), the projected ends (xs, ys, d), `outside`: an end lies outside a plane,
+    `cut` ((3n, 4): boundary B1 .. B4 has one end outside it and the other not) and `w_dropped` (the edge passes the clip and is
+    dropped for an end with w <= 0)."""
     world = R.world_vertices(inst)
     P = R.clip_vertices(np.ascontiguousarray(cam, F).reshape(1, 4, 4), world)[0]            # F1: (n, 3, 4)
     P0 = P[:, [a for a, _ in R.EDGES], :].reshape(-1, 4)
     P1 = P[:, [b for _, b in R.EDGES], :].reshape(-1, 4)
     m = len(P0)
     t_in, t_out, keep, outside = np.zeros(m, F), np.ones(m, F), np.ones(m, bool), np.zeros(m, bool)
+    cut = np.zeros((m, 4), bool)
     with np.errstate(all="ignore"):
         def bounds(p):
             y, z, w = p[:, 1], p[:, 2], p[:, 3]
             return (z, w - z, w + y, w - y)                                                  # B1 .. B4
 
-        for b0, b1 in zip(bounds(P0), bounds(P1)):                                           # F2
+        for k, (b0, b1) in enumerate(zip(bounds(P0), bounds(P1))):                           # F2
             keep &= ~((b0 < 0) & (b1 < 0))
             outside |= (b0 < 0) | (b1 < 0)
+            cut[:, k] = ((b0 < 0) & (b1 >= 0)) | ((b1 < 0) & (b0 >= 0))
             r = b0 / (b0 - b1)
             t_in = np.where((b0 < 0) & (b1 >= 0) & (r > t_in), r, t_in)
             t_out = np.where((b1 < 0) & (b0 >= 0) & (r < t_out), r, t_out)
@@ -50,9 +54,11 @@ def edges(cam, inst, W, H):
         D = P1 - P0
         Q0 = np.where((t_in > 0)[:, None], P0 + t_in[:, None] * D, P0)
         Q1 = np.where((t_out < 1)[:, None], P0 + t_out[:, None] * D, P1)
-        keep &= (Q0[:, 3] > 0) & (Q1[:, 3] > 0)
+        positive = (Q0[:, 3] > 0) & (Q1[:, 3] > 0)
+        w_dropped = keep & ~positive
+        keep &= positive
         h, g = F(W) * F(0.5), F(H) * F(0.5)                                                  # F3
-        e = dict(keep=keep, outside=outside, t_in=t_in, t_out=t_out, w0=Q0[:, 3], w1=Q1[:, 3])
+        e = dict(keep=keep, outside=outside, cut=cut, w_dropped=w_dropped, t_in=t_in, t_out=t_out, w0=Q0[:, 3], w1=Q1[:, 3])
         e["xs0"] = (Q0[:, 0] / Q0[:, 3]) * h + h
         e["xs1"] = (Q1[:, 0] / Q1[:, 3]) * h + h
         e["ys0"] = g - (Q0[:, 1] / Q0[:, 3]) * g
@@ -68,9 +74,10 @@ def edges(cam, inst, W, H):
     return e
 
 
-def _steps(e, idx, m, W):
+def _steps(e, idx, m, W, far=None):
     """F4 and F5 for step m[i] along the major axis of edge idx[i]: (ok, t, pixel, d) -- ok: the step yields a pixel and its depth
-    is a candidate; pixel = row * W + column; d after the clamp to +0."""
+    is a candidate; pixel = row * W + column; d after the clamp to +0.  far, a list, receives the steps that yield a pixel whose
+    depth is >= 1: no candidate."""
     with np.errstate(all="ignore"):
         a0, a1 = e["a0"][idx], e["a1"][idx]
         amin, amax = np.where(a0 <= a1, a0, a1), np.where(a0 <= a1, a1, a0)
@@ -80,6 +87,8 @@ def _steps(e, idx, m, W):
         o = e["b0"][idx] + t * e["db"][idx]
         ok &= (o >= 0) & (o < e["blim"][idx])
         d = e["d0"][idx] + t * (e["d1"][idx] - e["d0"][idx])
+        if far is not None:
+            far.append(ok & (d >= F(1)))
         ok &= d < F(1)
         d = np.where(d > 0, d, F(0)).astype(F)                                               # !(d > 0) -> +0
         f = np.where(ok, np.floor(o), 0).astype(np.int64)
@@ -92,14 +101,18 @@ def frame(cam, inst, W, H, skin=None, stats=None):
     Returns (ids uint32 (H, W), depth float32 (H, W), rgba float32 (H, W, 4), bgra8 uint32 (H, W)); row 0 is the top.
     `stats`, a dict, receives: "kept" edges (after F2), "clipped" (kept with an end outside a plane), "xmajor" / "ymajor" (kept
     edges with a step to try), pixel "writes" (candidates), "covered" pixels, distinct "depths" among them, visible "bodies", the
-    "longest" edge in pixel writes, and "edge": how many pixels each edge index wins."""
+    "longest" edge in pixel writes ("longest_x", "longest_y": among the x-major and the y-major edges), "edge": how many pixels
+    each edge index wins, "cut" (4 entries: kept edges that boundary B1 .. B4 cuts), "w_dropped" (edges that pass the clip and are
+    dropped for an end with w <= 0) and "rejected_far" (steps that yield a pixel whose depth is >= 1)."""
     inst = np.ascontiguousarray(inst, F).reshape(-1, 4, 4)
     skin = K.WHITE if skin is None else np.ascontiguousarray(skin, F)
     th, tw = skin.shape[:2]
     n = len(inst)
     e = edges(cam, inst, W, H)
     keys = np.full(W * H, R.EMPTY, np.uint64)
-    st = dict(kept=int(e["keep"].sum()), clipped=int((e["keep"] & e["outside"]).sum()), xmajor=0, ymajor=0, writes=0, longest=0)
+    st = dict(kept=int(e["keep"].sum()), clipped=int((e["keep"] & e["outside"]).sum()), xmajor=0, ymajor=0, writes=0, longest=0,
+              longest_x=0, longest_y=0, rejected_far=0, w_dropped=int(e["w_dropped"].sum()),
+              cut=(e["cut"] & e["keep"][:, None]).sum(0).astype(np.int64))
     with np.errstate(all="ignore"):
         amin, amax = np.minimum(e["a0"], e["a1"]), np.maximum(e["a0"], e["a1"])              # (a NaN end: NaN, dropped next)
         live = e["keep"] & (amin <= amax)
@@ -114,11 +127,15 @@ def frame(cam, inst, W, H, skin=None, stats=None):
     if total:
         idx = np.repeat(np.arange(3 * n), span)
         m = np.arange(total) - np.repeat(np.cumsum(span) - span, span) + lo[idx]
-        ok, _, pixel, d = _steps(e, idx, m, W)
+        far = []
+        ok, _, pixel, d = _steps(e, idx, m, W, far)
         key = (d.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (idx // 3).astype(np.uint64)   # F5
         np.minimum.at(keys, pixel[ok], key[ok])
         st["writes"] = int(ok.sum())
-        st["longest"] = int(np.bincount(idx[ok], minlength=1).max()) if ok.any() else 0
+        per_edge = np.bincount(idx[ok], minlength=3 * n)
+        st["longest"] = int(per_edge.max()) if ok.any() else 0
+        st["longest_x"], st["longest_y"] = int(per_edge[e["xmajor"]].max(initial=0)), int(per_edge[~e["xmajor"]].max(initial=0))
+        st["rejected_far"] = int(far[0].sum())
     none = keys == R.EMPTY
     ids = np.where(none, np.uint32(R.NONE), (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32))
     depth = np.where(none, F(1), (keys >> np.uint64(32)).astype(np.uint32).view(F))

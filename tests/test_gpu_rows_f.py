@@ -57,6 +57,42 @@ def test_cameras_bit_exact(nb, oracle):
     assert np.allclose(np.einsum("nij,nkj->nik", rot, rot), np.eye(3), atol=1e-5)
 
 
+def test_cameras_over_every_binade(nb, oracle):
+    """cameras_kernel against oracle.cameras off the directions a step produces: every binade from 2^-70 to 2^63 per component, so
+    that the sum of squares inside normalize underflows to subnormals and to zero and overflows to infinity; subnormal, signed-zero
+    and infinite components; eyes of +-3e38; three `up` vectors.  The oracle runs the host's sqrtf and '/': the device must give
+    the same words, and a NaN where the oracle has a NaN (the payload and sign of a NaN are the machine's)."""
+    n = 4096
+    rng = np.random.default_rng(77)
+    e = rng.integers(-70, 64, (n, 3))
+    e[:134] = np.arange(-70, 64)[:, None]                            # each binade in all three components at once ...
+    e[134:268, 1:] = -70                                             # ... and in one component beside two tiny ones
+    e[134:268, 0] = np.arange(-70, 64)
+    e[400:900] = rng.integers(-70, -59, (500, 3))                    # the squares subnormal or zero
+    e[900:1200] = rng.integers(61, 64, (300, 3))                     # their sum at the top of the range and past it
+    dirs = (rng.uniform(1, 2, (n, 3)) * np.exp2(e) * rng.choice([-1, 1], (n, 3))).astype(np.float32)
+    sub, inf = np.float32(1e-42), np.float32(np.inf)
+    edge = [(sub, sub, sub), (sub, -sub, 0.0), (1e-30, sub, -sub), (0.0, 0.0, 1.0), (-0.0, 1.0, -0.0), (1.0, 0.0, -0.0), (-0.0, -0.0, -0.0),
+            (inf, 1.0, 1.0), (1.0, -inf, 2.0), (inf, inf, 1.0), (1.0, 1.0, inf), (3e38, 3e38, 3e38), (3e38, 1.0, -1.0), (1e-45, 0.0, 0.0),
+            (1.0, 1e-45, 0.0), (2.0 ** -63, 2.0 ** -64, 0.0), (2.0 ** 63, 2.0 ** 63, 2.0 ** 63), (2.0 ** 64, 1.0, 1.0)]
+    dirs[300:300 + len(edge)] = np.array(edge, np.float32)
+    eyes = rng.uniform(-100, 100, (n, 3)).astype(np.float32)
+    eyes[::7] = (rng.choice([-3e38, 3e38], (len(eyes[::7]), 3))).astype(np.float32)
+    eyes[3::11, 1] = np.float32(-0.0)
+    cp = perspective_cp()
+    mag2 = (dirs.astype(np.float64) ** 2).sum(1)
+    assert (mag2 < 2.0 ** -126).sum() > 100 and (mag2 > 2.0 ** 128).sum() > 50 and ((mag2 > 2.0 ** -100) & (mag2 < 2.0 ** 100)).sum() > 1000
+    with nb.Scene(eyes, dirs) as sc:
+        for up in ([0, 0, 1], [0.6, -0.8, 0], [1e-3, 2.5, -7.25]):
+            up = np.array(up, np.float32)
+            got, ref = sc.cameras(up, cp), oracle.cameras(eyes, dirs, up, cp)
+            same = (bits(got) == bits(ref)) | (np.isnan(got) & np.isnan(ref))
+            bad = np.argwhere(~same.reshape(n, 16).all(axis=1)).ravel()
+            assert len(bad) == 0, (f"up {up}: {len(bad)} of {n} cameras differ; first: direction {dirs[bad[0]]!r} eye {eyes[bad[0]]!r}: "
+                                   f"{got[bad[0]].ravel()!r} vs {ref[bad[0]].ravel()!r}")
+            assert np.isfinite(ref).all(axis=(1, 2)).sum() > 1000 and np.isnan(ref).any()
+
+
 def test_cameras_degenerate_directions_like_the_reference(nb, oracle):
     """Zero velocity -> normalize divides by zero; direction parallel to up -> zero cross product: NaNs in the same places."""
     pos = np.array([[1, 2, 3], [4, 5, 6], [7, 8, 9]], np.float32)
