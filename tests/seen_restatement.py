@@ -4,6 +4,8 @@ sees (V1-V3).
 TEST INFRASTRUCTURE.  The kernels (nenbody_amd/csrc/nb_seen.inc) and this module implement the same rule independently; the GPU
 tests compare every word.  The seen set goes through np.unique; the step is np_restatement.boids_step written out again with the
 one change the rule makes, `ne = (idx != i) & mask[:, i]` -- every operation one binary32 operation on numpy float32 arrays.
+boids_seen_step_lists is the same step over lists as a caller may hand them to nb_launch_boids_seen_step -- in slot order, duplicates
+folded again, the count clamped at the stride --; tests/test_seen_lists_cpu.py ties it to the mask form and to the C oracle.
 """
 import numpy as np
 
@@ -60,6 +62,72 @@ def mask_of_lists(count, lists, n):
         row = lists[e, :min(int(count[e]), lists.shape[1])]
         mask[e, row[row < n]] = True
     return mask
+
+
+def lists_of_mask(mask, stride=None):
+    """the ascending, duplicate-free lists of a mask (E, n): (count (E,) uint32, lists (E, stride) uint32, NONE behind count[e])"""
+    mask = np.asarray(mask, bool)
+    stride = mask.shape[1] if stride is None else stride
+    count = mask.sum(1).astype(np.uint32)
+    assert count.max(initial=0) <= stride
+    lists = np.full((len(mask), stride), NONE, np.uint32)
+    for e in range(len(mask)):
+        lists[e, :count[e]] = np.nonzero(mask[e])[0]
+    return count, lists
+
+
+def boids_seen_step_lists(pos, vel, count, lists, first=0, dt=F(0.04), r1=F(1000.0), r2=F(5.0), r3=F(500.0), s1=F(0.02), s2=F(0.05),
+                          s3=F(0.5)):
+    """V2-V3 for lists, as include/nenbody.h states nb_launch_boids_seen_step: row e of ``lists`` (E, stride) belongs to body
+    first + e of the n bodies of (pos, vel), which folds the reference's three rules over the slots k < min(count[e], stride) in slot
+    order.  An entry equal to first + e, or >= n, is skipped; a duplicate folds again; what lies behind the count is never looked at.
+    Vectorised over the bodies e, sequential over the slot index k; every operation one binary32 numpy operation, the radius tests
+    the reference's own sqrt(d2) < r.  Returns (positions, velocities), each (E, 3), of bodies first .. first + E - 1."""
+    old_p = np.ascontiguousarray(pos, np.float32)
+    old_v = np.ascontiguousarray(vel, np.float32)
+    lists = np.ascontiguousarray(lists, np.uint32)
+    n = len(old_p)
+    e, stride = lists.shape
+    me = first + np.arange(e, dtype=np.int64)
+    pn, vn = old_p[me], old_v[me]
+    length = np.minimum(np.asarray(count, np.uint32).astype(np.int64), stride)
+    c = np.zeros((e, 3), np.float32)
+    r = np.zeros((e, 3), np.float32)
+    m = np.zeros((e, 3), np.float32)
+    cnt = np.zeros(e, np.int32)
+    vcnt = np.zeros(e, np.int32)
+    with np.errstate(all="ignore"):
+        for k in range(stride):
+            i = lists[:, k].astype(np.int64)
+            live = (k < length) & (i != me) & (i < n)     # V2: inside the count, not the body itself, inside the set
+            j = np.where(live, i, 0)                      # (a skipped entry is not read: any record stands in, no rule takes it)
+            pi, vi = old_p[j], old_v[j]
+            d = pi - pn                                   # distance2: (other - self)
+            sq = d * d
+            d2 = (sq[:, 0] + sq[:, 1]) + sq[:, 2]
+            p1 = (d2 < F(r1)) & live                      # main.rs:474-475
+            c = np.where(p1[:, None], c + pi, c)
+            cnt = cnt + p1
+            p2 = (np.sqrt(d2) < F(r2)) & live             # main.rs:485-486
+            r = np.where(p2[:, None], r - (pi - pn), r)
+            dv = vi - vn
+            sv = dv * dv
+            d2v = (sv[:, 0] + sv[:, 1]) + sv[:, 2]
+            p3 = (np.sqrt(d2v) < F(r3)) & live            # main.rs:497-498
+            m = np.where(p3[:, None], m + vi, m)
+            vcnt = vcnt + p3
+        has = cnt > 0
+        c = np.where(has[:, None], c / np.maximum(cnt, 1).astype(np.float32)[:, None], c)        # main.rs:506-508
+        hasv = vcnt > 0
+        m = np.where(hasv[:, None], m / np.maximum(vcnt, 1).astype(np.float32)[:, None], m)     # main.rs:510-512
+        v = (c * F(s1) + r * F(s2)) + m * F(s3)           # main.rs:514
+        sq = v * v
+        mag = np.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2])
+        big = mag > F(1.0)                                # main.rs:516-518
+        scale = np.where(big, F(1.0) / np.where(big, mag, F(1.0)), F(1.0)).astype(np.float32)
+        v = np.where(big[:, None], v * scale[:, None], v).astype(np.float32)
+        p = (v * F(dt) + pn).astype(np.float32)           # main.rs:521
+    return p, v
 
 
 def boids_seen_step(pos, vel, mask, dt=F(0.04), r1=F(1000.0), r2=F(5.0), r3=F(500.0), s1=F(0.02), s2=F(0.05), s3=F(0.5)):

@@ -10,6 +10,7 @@ import pytest
 import eyes_restatement as R
 import seen_restatement as S
 from conftest import ROOT
+from seen_cases import PAD   # NaN records behind n_total: an out-of-set entry that were read would show as a NaN, not as a fault
 
 pytestmark = pytest.mark.gpu
 
@@ -264,8 +265,11 @@ def caller_lists(n, stride, rng):
     return count, lists
 
 
-def launch_boids_seen(n_total, first, count, pos, vel, cnt, lists):
-    """the launch on tensors with one extra record of NaNs behind n_total: (pos_out, vel_out) (n_total + 1, 4) float32"""
+def launch_boids_seen(n_total, first, count, pos, vel, cnt, lists, params=None):
+    """the launch on tensors with PAD extra records of NaNs behind n_total: (pos_out, vel_out) (n_total + PAD, 4) float32, every
+    word -7 before the launch; ``params``: an NbBoidsParams, None for the defaults"""
+    import ctypes
+
     import torch
 
     from nenbody_amd import _lib
@@ -273,20 +277,22 @@ def launch_boids_seen(n_total, first, count, pos, vel, cnt, lists):
     dev = torch.device("cuda", 0)
 
     def rec(a):
-        r = np.full((n_total + 1, 4), np.nan, F)
+        r = np.full((n_total + PAD, 4), np.nan, F)
         r[:n_total, :3] = a
         r[:n_total, 3] = 0
         return torch.from_numpy(r).to(dev)
 
     tp, tv = rec(pos), rec(vel)
-    op = torch.full((n_total + 1, 4), -7.0, dtype=torch.float32, device=dev)
-    ov = torch.full((n_total + 1, 4), -7.0, dtype=torch.float32, device=dev)
-    tc = torch.from_numpy(cnt.view(np.int32)).to(dev)
-    tl = torch.from_numpy(np.ascontiguousarray(lists).view(np.int32)).to(dev)
+    op = torch.full((n_total + PAD, 4), -7.0, dtype=torch.float32, device=dev)
+    ov = torch.full((n_total + PAD, 4), -7.0, dtype=torch.float32, device=dev)
+    tc = torch.from_numpy(np.ascontiguousarray(cnt, np.uint32).view(np.int32)).to(dev)
+    tl = torch.from_numpy(np.ascontiguousarray(lists, np.uint32).view(np.int32)).to(dev)
+    assert tc.numel() == count and tl.numel() == count * lists.shape[1]      # the kernel reads this many words, no more
     s = torch.cuda.Stream(dev)
     with torch.cuda.stream(s):
-        _lib.check(_lib.load().nb_launch_boids_seen_step(None, n_total, first, count, tp.data_ptr(), tv.data_ptr(), tc.data_ptr(),
-                                                         tl.data_ptr(), lists.shape[1], op.data_ptr(), ov.data_ptr(), s.cuda_stream))
+        _lib.check(_lib.load().nb_launch_boids_seen_step(ctypes.byref(params) if params is not None else None, n_total, first, count,
+                                                         tp.data_ptr(), tv.data_ptr(), tc.data_ptr(), tl.data_ptr(), lists.shape[1],
+                                                         op.data_ptr(), ov.data_ptr(), s.cuda_stream))
     s.synchronize()
     return op.cpu().numpy(), ov.cpu().numpy()
 
@@ -299,7 +305,7 @@ def test_caller_lists_own_index_and_entries_outside_the_set(nb, oracle):
     want_p, want_v = S.boids_seen_step(pos, vel, S.mask_of_lists(cnt, lists, n))
     gp, gv = launch_boids_seen(n, 0, n, pos, vel, cnt, lists)
     assert (bits(gp[:n, :3]) == bits(want_p)).all() and (bits(gv[:n, :3]) == bits(want_v)).all()   # a NaN would show a missing guard
-    assert (gp[:n, 3] == 0).all() and (gv[:n, 3] == 0).all() and (gp[n] == -7).all() and (gv[n] == -7).all()
+    assert (gp[:n, 3] == 0).all() and (gv[:n, 3] == 0).all() and (gp[n:] == -7).all() and (gv[n:] == -7).all()
 
 
 @pytest.mark.parametrize("first,count", [(0, 1), (5, 10), (69, 1), (13, 57)])
@@ -311,7 +317,7 @@ def test_caller_lists_subsets_write_only_their_range(nb, oracle, first, count):
     rows = slice(first, first + count)
     gp, gv = launch_boids_seen(n, first, count, pos, vel, cnt[rows].copy(), lists[rows])    # row e of the lists is body first + e
     assert (bits(gp[rows, :3]) == bits(want_p[rows])).all() and (bits(gv[rows, :3]) == bits(want_v[rows])).all()
-    rest = np.ones(n + 1, bool)
+    rest = np.ones(n + PAD, bool)
     rest[rows] = False
     assert (gp[rest] == -7).all() and (gv[rest] == -7).all()
 
