@@ -1,6 +1,10 @@
 // nb_boids.inc -- boids controller (update_instance_boids, main.rs:443-526): one-lane-per-body kernel (plain and (x, y)-packed),
 // chain-split kernel (two waves per 64 bodies) and producer/consumer kernel; nb_api.hip:boids_form picks by bodies per rank.
 // Included by nb_kernels.hip inside namespace nbk; see that file for the compilation scheme.
+// What the forms share is stated once: boids_wave_flags, BoidsOwn / boids_own (a lane's own body), boids_mask_vgprs, BoidsStage /
+// boids_stage_fetch / boids_stage_publish and BoidsTileHead / boids_tile_head (the LDS tile of the one-lane and chain-split
+// kernels; the head also serves the producer/consumer body), BOIDS_FOLD_BY_FLAGS (the form ladder), boids_finish (the epilogue,
+// also of nb_seen.inc) and BOIDS_LAUNCH (the tile and packed switches of the launchers).
 
 // ------------------------------------------------------------------------------------------------
 // Boids controller: update_instance_boids, main.rs:443-526 (SURVEY.md section 8f, rank 1).
@@ -49,6 +53,44 @@ __device__ __forceinline__ uint32_t boids_flags(const float4 p, const float4 v, 
     auto far = [vlim_bits](float c) { return (__float_as_uint(c) & 0x7fffffffu) > vlim_bits ? kBoidsVelFar : 0u; };
     return nonfinite(p.x) | nonfinite(p.y) | nonfinite(p.z) | nonfinite(v.x) | nonfinite(v.y) | nonfinite(v.z) | nonzero(p.z) |
            nonzero(v.z) | far(v.x) | far(v.y) | far(v.z);
+}
+// the three record flags of a whole wave (every lane takes part)
+__device__ __forceinline__ uint32_t boids_wave_flags(uint32_t f)
+{
+    return (__any((int)(f & kBoidsNonFinite)) ? kBoidsNonFinite : 0u) | (__any((int)(f & kBoidsNonPlanar)) ? kBoidsNonPlanar : 0u) |
+           (__any((int)(f & kBoidsVelFar)) ? kBoidsVelFar : 0u);
+}
+
+// A lane's own body, the same in every form: `bodies` (256, or 64 in the producer/consumer form) per workgroup, `within` this
+// lane's place among them.  A lane past the shard folds for the shard's last body and writes nothing.
+struct BoidsOwn {
+    uint32_t l;               // index within the shard
+    bool live;
+    uint32_t gn;              // this body's global index n
+    float4 pn, vn;
+    uint32_t self;            // the wave's own bodies' flags, the forced ones (tests) OR-ed in
+    uint32_t own_lo, own_hi;  // global index range of the workgroup's bodies: only tiles overlapping it can contain i == n
+};                            // (own_hi exclusive; past-the-shard indices never match a live body)
+__device__ __forceinline__ BoidsOwn boids_own(const BoidsArgs &a, uint32_t bodies, uint32_t within)
+{
+    BoidsOwn o;
+    o.l = blockIdx.x * bodies + within;
+    o.live = o.l < a.count;
+    o.gn = a.first + (o.live ? o.l : a.count - 1u);
+    o.pn = a.pos_in[o.gn];
+    o.vn = a.vel_in[o.gn];
+    o.self = boids_wave_flags(boids_flags(o.pn, o.vn, a.vlim_bits) | a.force_flags);
+    o.own_lo = a.first + blockIdx.x * bodies;
+    o.own_hi = o.own_lo + bodies;
+    return o;
+}
+
+// the radius-test constants in vector registers, once (boids_below)
+__device__ __forceinline__ BoidsMaskK boids_mask_vgprs(const BoidsArgs &a)
+{
+    BoidsMaskK mkv = a.mk;
+    asm("" : "+v"(mkv.k1), "+v"(mkv.tk1), "+v"(mkv.k2), "+v"(mkv.tk2), "+v"(mkv.k3), "+v"(mkv.tk3));
+    return mkv;
 }
 
 // `x < T` as 1.0f / 0.0f in ONE instruction (round 3; a compare and a select before).  k is a power of two with T * k in
@@ -252,6 +294,98 @@ __device__ __forceinline__ void boids_fold_tile(BoidsAcc &s, const float4 *tpv, 
     if (ALL3 && ROLE != 1 && ROLE != 3) s.vcnt = s.vcnt + (float)nj;  // nj ones: counts are integers below 2^24, exact in binary32 either way
 }
 
+// What the LDS-tiled kernels (one lane per body, chain split) share: a tile of TJ records is (px, py, vx, vy) in tile_pv, (pz, vz)
+// in tile_z and one flag word per staging wave in tile_flags; THREADS threads stage it, R = TJ / THREADS records each, through
+// registers (the next tile's loads are in flight while this one is folded).  A record past the end of the set is the zero record.
+template <int R>
+struct BoidsStage {
+    float4 p[R], v[R];
+};
+template <int THREADS, int R>
+__device__ __forceinline__ void boids_stage_fetch(BoidsStage<R> &st, const BoidsArgs &a, uint32_t j0, int tid)
+{
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const uint32_t j = j0 + (uint32_t)(k * THREADS + tid);
+        st.p[k] = (j < a.n_total) ? a.pos_in[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const uint32_t j = j0 + (uint32_t)(k * THREADS + tid);
+        st.v[k] = (j < a.n_total) ? a.vel_in[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+template <int THREADS, int R>
+__device__ __forceinline__ void boids_stage_publish(const BoidsStage<R> &st, const BoidsArgs &a, float4 *tile_pv, float2 *tile_z,
+                                                    uint32_t *tile_flags, int tid)
+{
+    uint32_t f = 0;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        f |= boids_flags(st.p[k], st.v[k], a.vlim_bits);
+        tile_pv[k * THREADS + tid] = make_float4(st.p[k].x, st.p[k].y, st.v[k].x, st.v[k].y);
+        tile_z[k * THREADS + tid] = make_float2(st.p[k].z, st.v[k].z);
+    }
+    f = boids_wave_flags(f);
+    if ((tid & 63) == 0) tile_flags[tid >> 6] = f;
+}
+template <int W>
+__device__ __forceinline__ uint32_t boids_or_words(const uint32_t *w)
+{
+    uint32_t f = 0;
+#pragma unroll
+    for (int i = 0; i < W; ++i) f |= w[i];
+    return f;
+}
+
+// per-tile bookkeeping of tile t of TJ records (all uniform): its first record, its length, whether it overlaps the workgroup's
+// own bodies, and its W flag words OR-ed into the own bodies' flags
+struct BoidsTileHead {
+    uint32_t j0;
+    int nj;
+    bool has_self;
+    uint32_t flags;
+};
+template <int TJ, int W>
+__device__ __forceinline__ BoidsTileHead boids_tile_head(uint32_t t, uint32_t n, const BoidsOwn &o, uint32_t self, const uint32_t *tile_flags)
+{
+    BoidsTileHead h;
+    h.j0 = t * (uint32_t)TJ;
+    const uint32_t left = n - h.j0;
+    h.nj = left < (uint32_t)TJ ? (int)left : TJ;
+    h.flags = self | boids_or_words<W>(tile_flags);
+    h.has_self = h.j0 < o.own_hi && h.j0 + (uint32_t)h.nj > o.own_lo;
+    return h;
+}
+
+// The form ladder: a tile's fold chosen from its flags (the specialisations at the top of this file), for head `h` of the tile in
+// tile_pv / tile_z and own bodies `o`.  ROLE 3 folds no rule 3 (the split form where the step's total supplies it), so
+// kBoidsVelFar, which only says whether rule 3 must be tested, chooses nothing there.  A macro with local copies of what it
+// reads, not a function: as a __forceinline__ template the same ladder leaves boids_step_kernel with 52 scalar registers where
+// the ladder written out in the kernel has 54 (DESIGN.md section 4.3, "One tile pipeline"), and the change that introduced it
+// had to leave every kernel's resources as they were.
+#define BOIDS_FOLD_BY_FLAGS(PACKED, ROLE, s, h, tile_pv, tile_z, o, a, mkv)                                                     \
+    do {                                                                                                                        \
+        constexpr bool kRule3 = (ROLE) != 3;                                                                                    \
+        constexpr uint32_t k3dFar = kBoidsNonPlanar | kBoidsVelFar;                                                             \
+        const float4 *tp = (tile_pv);                                                                                           \
+        const float2 *tv = (tile_z);                                                                                            \
+        const uint32_t f = (h).flags, j0 = (h).j0, gn = (o).gn;                                                                 \
+        const bool has_self = (h).has_self;                                                                                     \
+        const int nj = (h).nj;                                                                                                  \
+        const float4 pn = (o).pn, vn = (o).vn;                                                                                  \
+        if (has_self || (f & kBoidsNonFinite))                                                                                  \
+            boids_fold_tile<true, false, false, false, false, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, (a).r1, (a).t2, (a).t3, mkv);  \
+        else if (kRule3 && (f & k3dFar) == k3dFar)                                                                              \
+            boids_fold_tile<false, true, false, false, false, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, (a).r1, (a).t2, (a).t3, mkv);  \
+        else if (kRule3 && (f & kBoidsVelFar))                                                                                  \
+            boids_fold_tile<false, true, true, false, PACKED, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, (a).r1, (a).t2, (a).t3, mkv);  \
+        else if (f & kBoidsNonPlanar)                                                                                           \
+            boids_fold_tile<false, true, false, true, false, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, (a).r1, (a).t2, (a).t3, mkv);   \
+        else                                                                                                                    \
+            boids_fold_tile<false, true, true, true, PACKED, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, (a).r1, (a).t2, (a).t3, mkv);   \
+    } while (0)
+
 // main.rs:506-521 for one body: means, blend, speed clamp, position update
 __device__ __forceinline__ void boids_finish(const BoidsArgs &a, const BoidsAcc &s, uint32_t l, const float4 pn)
 {
@@ -344,97 +478,47 @@ __global__ __launch_bounds__(kBlock) void boids_step_kernel(BoidsArgs a)
     __shared__ uint32_t self_flags[kWaves];
 
     const int tid = threadIdx.x;
-    const int wave = tid >> 6;
-    const uint32_t l = blockIdx.x * (uint32_t)kBlock + (uint32_t)tid;
-    const bool live = l < a.count;
-    const uint32_t gn = a.first + (live ? l : a.count - 1u);  // this body's global index n
-    const float4 pn = a.pos_in[gn];
-    const float4 vn = a.vel_in[gn];
-    auto wave_flags = [](uint32_t f) {
-        return (__any((int)(f & kBoidsNonFinite)) ? kBoidsNonFinite : 0u) | (__any((int)(f & kBoidsNonPlanar)) ? kBoidsNonPlanar : 0u) |
-               (__any((int)(f & kBoidsVelFar)) ? kBoidsVelFar : 0u);
-    };
-    {
-        const uint32_t f = wave_flags(boids_flags(pn, vn, a.vlim_bits) | a.force_flags);
-        if ((tid & 63) == 0) self_flags[wave] = f;
-    }
-    // global index range of this workgroup's bodies: only tiles overlapping it can contain i == n
-    const uint32_t own_lo = a.first + blockIdx.x * (uint32_t)kBlock;
-    const uint32_t own_hi = own_lo + (uint32_t)kBlock;  // exclusive (past-the-shard indices never match a live body)
+    const BoidsOwn o = boids_own(a, (uint32_t)kBlock, (uint32_t)tid);
+    if ((tid & 63) == 0) self_flags[tid >> 6] = o.self;
 
-    TileRegs<TJ> rp, rv;
+    BoidsStage<TJ / kBlock> st;
     const uint32_t n = a.n_total;
     const uint32_t ntiles_all = (n + (uint32_t)TJ - 1u) / (uint32_t)TJ;
     const uint32_t t_lo = SLICED ? blockIdx.y * (a.j_chunk / (uint32_t)TJ) : 0u;
     const uint32_t t_end = SLICED ? t_lo + a.j_chunk / (uint32_t)TJ : ntiles_all;
     const uint32_t ntiles = t_end < ntiles_all ? t_end : ntiles_all;  // (a slice past the end of the set folds nothing)
-    tile_fetch<TJ>(rp, a.pos_in, t_lo * (uint32_t)TJ, n, tid);
-    tile_fetch<TJ>(rv, a.vel_in, t_lo * (uint32_t)TJ, n, tid);
-    auto publish = [&](int buf) {
-        uint32_t f = 0;
-#pragma unroll
-        for (int k = 0; k < TJ / kBlock; ++k) {
-            f |= boids_flags(rp.r[k], rv.r[k], a.vlim_bits);
-            tile_pv[buf][k * kBlock + tid] = make_float4(rp.r[k].x, rp.r[k].y, rv.r[k].x, rv.r[k].y);
-            tile_z[buf][k * kBlock + tid] = make_float2(rp.r[k].z, rv.r[k].z);
-        }
-        f = wave_flags(f);
-        if ((tid & 63) == 0) tile_flags[buf][wave] = f;
-    };
-    publish(0);
+    boids_stage_fetch<kBlock>(st, a, t_lo * (uint32_t)TJ, tid);
+    boids_stage_publish<kBlock>(st, a, tile_pv[0], tile_z[0], tile_flags[0], tid);
     __syncthreads();
-    const uint32_t block_self = self_flags[0] | self_flags[1] | self_flags[2] | self_flags[3];
+    const uint32_t block_self = boids_or_words<kWaves>(self_flags);
     // split form: did boids_prep_kernel find every record of the step finite and every velocity component inside the rule-3 bound?
+    // Then rule 3 holds for every pair of the step and its sum comes from the total (boids_combine_kernel).
     const bool no3 = SLICED && boids_no3(a);
 
-    // the radius-test constants in vector registers, once (boids_below)
-    BoidsMaskK mkv = a.mk;
-    asm("" : "+v"(mkv.k1), "+v"(mkv.tk1), "+v"(mkv.k2), "+v"(mkv.tk2), "+v"(mkv.k3), "+v"(mkv.tk3));
+    const BoidsMaskK mkv = boids_mask_vgprs(a);
     BoidsAcc s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int buf = 0;
     for (uint32_t t = t_lo; t < ntiles; ++t) {
         const bool more = (t + 1u) < ntiles;
-        if (more) {
-            tile_fetch<TJ>(rp, a.pos_in, (t + 1u) * (uint32_t)TJ, n, tid);
-            tile_fetch<TJ>(rv, a.vel_in, (t + 1u) * (uint32_t)TJ, n, tid);
-        }
-        const uint32_t j0 = t * (uint32_t)TJ;
-        const uint32_t left = n - j0;
-        const int nj = left < (uint32_t)TJ ? (int)left : TJ;
-        const uint32_t f = block_self | tile_flags[buf][0] | tile_flags[buf][1] | tile_flags[buf][2] | tile_flags[buf][3];
-        const bool has_self = j0 < own_hi && j0 + (uint32_t)nj > own_lo;
-        const float4 *tp = tile_pv[buf];
-        const float2 *tv = tile_z[buf];
-        if (SLICED && no3) {  // rule 3 holds for every pair of the step: its sum comes from the total (boids_combine_kernel)
-            if (has_self || (f & kBoidsNonFinite))
-                boids_fold_tile<true, false, false, false, false, 3>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-            else if (f & kBoidsNonPlanar)
-                boids_fold_tile<false, true, false, true, false, 3>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-            else
-                boids_fold_tile<false, true, true, true, false, 3>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-        } else if (has_self || (f & kBoidsNonFinite))
-            boids_fold_tile<true, false, false, false, false>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-        else if ((f & (kBoidsNonPlanar | kBoidsVelFar)) == (kBoidsNonPlanar | kBoidsVelFar))
-            boids_fold_tile<false, true, false, false, false>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-        else if (f & kBoidsVelFar)
-            boids_fold_tile<false, true, true, false, PACKED>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-        else if (f & kBoidsNonPlanar)
-            boids_fold_tile<false, true, false, true, false>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
+        if (more) boids_stage_fetch<kBlock>(st, a, (t + 1u) * (uint32_t)TJ, tid);
+        const BoidsTileHead h = boids_tile_head<TJ, kWaves>(t, n, o, block_self, tile_flags[buf]);
+        if (SLICED && no3)
+            BOIDS_FOLD_BY_FLAGS(PACKED, 3, s, h, tile_pv[buf], tile_z[buf], o, a, mkv);
         else
-            boids_fold_tile<false, true, true, true, PACKED>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-        if (more) publish(buf ^ 1);
+            BOIDS_FOLD_BY_FLAGS(PACKED, 0, s, h, tile_pv[buf], tile_z[buf], o, a, mkv);
+        if (more) boids_stage_publish<kBlock>(st, a, tile_pv[buf ^ 1], tile_z[buf ^ 1], tile_flags[buf ^ 1], tid);
         __syncthreads();
         buf ^= 1;
     }
 
-    if (!live) return;
+    if (!o.live) return;
     if (SLICED) {  // this slice's sums: three 16-byte records per body, [slice][body]
-        float4 *row = a.partial + ((size_t)blockIdx.y * a.count + l) * 3u;
+        float4 *row = a.partial + ((size_t)blockIdx.y * a.count + o.l) * 3u;
         row[0] = make_float4(s.cx, s.cy, s.cz, s.cnt);
         row[1] = make_float4(s.rx, s.ry, s.rz, s.vcnt);
         row[2] = make_float4(s.mx, s.my, s.mz, 0.f);
     } else {
-        boids_finish(a, s, l, pn);
+        boids_finish(a, s, o.l, o.pn);
     }
 }
 
@@ -506,89 +590,31 @@ __global__ __launch_bounds__(kSplitThreads) void boids_split_kernel(BoidsArgs a)
     __shared__ float handoff[7][kBlock];  // rx, ry, rz, mx, my, mz, vcnt of the rules-2-3 half
 
     const int tid = threadIdx.x;
-    const int wave = tid >> 6;
     const int role = __builtin_amdgcn_readfirstlane(tid >> 8);  // 0: rule 1; 1: rules 2 and 3
     const int btid = tid & (kBlock - 1);
-    const uint32_t l = blockIdx.x * (uint32_t)kBlock + (uint32_t)btid;
-    const bool live = l < a.count;
-    const uint32_t gn = a.first + (live ? l : a.count - 1u);
-    const float4 pn = a.pos_in[gn];
-    const float4 vn = a.vel_in[gn];
-    auto wave_flags = [](uint32_t f) {
-        return (__any((int)(f & kBoidsNonFinite)) ? kBoidsNonFinite : 0u) | (__any((int)(f & kBoidsNonPlanar)) ? kBoidsNonPlanar : 0u) |
-               (__any((int)(f & kBoidsVelFar)) ? kBoidsVelFar : 0u);
-    };
-    {
-        const uint32_t f = wave_flags(boids_flags(pn, vn, a.vlim_bits) | a.force_flags);
-        if ((tid & 63) == 0) self_flags[wave] = f;
-    }
-    const uint32_t own_lo = a.first + blockIdx.x * (uint32_t)kBlock;
-    const uint32_t own_hi = own_lo + (uint32_t)kBlock;
+    const BoidsOwn o = boids_own(a, (uint32_t)kBlock, (uint32_t)btid);
+    if ((tid & 63) == 0) self_flags[tid >> 6] = o.self;
 
-    float4 rp[R], rv[R];
+    BoidsStage<R> st;
     const uint32_t n = a.n_total;
     const uint32_t ntiles = (n + (uint32_t)TJ - 1u) / (uint32_t)TJ;
-    auto fetch = [&](uint32_t j0) {
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const uint32_t j = j0 + (uint32_t)(k * kSplitThreads + tid);
-            rp[k] = (j < n) ? a.pos_in[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-            rv[k] = (j < n) ? a.vel_in[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto publish = [&](int buf) {
-        uint32_t f = 0;
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            f |= boids_flags(rp[k], rv[k], a.vlim_bits);
-            tile_pv[buf][k * kSplitThreads + tid] = make_float4(rp[k].x, rp[k].y, rv[k].x, rv[k].y);
-            tile_z[buf][k * kSplitThreads + tid] = make_float2(rp[k].z, rv[k].z);
-        }
-        f = wave_flags(f);
-        if ((tid & 63) == 0) tile_flags[buf][wave] = f;
-    };
-    fetch(0u);
-    publish(0);
+    boids_stage_fetch<kSplitThreads>(st, a, 0u, tid);
+    boids_stage_publish<kSplitThreads>(st, a, tile_pv[0], tile_z[0], tile_flags[0], tid);
     __syncthreads();
-    uint32_t block_self = 0;
-#pragma unroll
-    for (int w = 0; w < kW; ++w) block_self |= self_flags[w];
+    const uint32_t block_self = boids_or_words<kW>(self_flags);
 
-    // the radius-test constants in vector registers, once (boids_below)
-    BoidsMaskK mkv = a.mk;
-    asm("" : "+v"(mkv.k1), "+v"(mkv.tk1), "+v"(mkv.k2), "+v"(mkv.tk2), "+v"(mkv.k3), "+v"(mkv.tk3));
+    const BoidsMaskK mkv = boids_mask_vgprs(a);
     BoidsAcc s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int buf = 0;
     for (uint32_t t = 0; t < ntiles; ++t) {
         const bool more = (t + 1u) < ntiles;
-        if (more) fetch((t + 1u) * (uint32_t)TJ);
-        const uint32_t j0 = t * (uint32_t)TJ;
-        const uint32_t left = n - j0;
-        const int nj = left < (uint32_t)TJ ? (int)left : TJ;
-        uint32_t f = block_self;
-#pragma unroll
-        for (int w = 0; w < kW; ++w) f |= tile_flags[buf][w];
-        const bool has_self = j0 < own_hi && j0 + (uint32_t)nj > own_lo;
-        const float4 *tp = tile_pv[buf];
-        const float2 *tv = tile_z[buf];
-        auto fold = [&](auto role_tag) {
-            constexpr int ROLE = decltype(role_tag)::value;
-            if (has_self || (f & kBoidsNonFinite))
-                boids_fold_tile<true, false, false, false, false, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-            else if ((f & (kBoidsNonPlanar | kBoidsVelFar)) == (kBoidsNonPlanar | kBoidsVelFar))
-                boids_fold_tile<false, true, false, false, false, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-            else if (f & kBoidsVelFar)
-                boids_fold_tile<false, true, true, false, PACKED, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-            else if (f & kBoidsNonPlanar)
-                boids_fold_tile<false, true, false, true, false, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-            else
-                boids_fold_tile<false, true, true, true, PACKED, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, a.r1, a.t2, a.t3, mkv);
-        };
+        if (more) boids_stage_fetch<kSplitThreads>(st, a, (t + 1u) * (uint32_t)TJ, tid);
+        const BoidsTileHead h = boids_tile_head<TJ, kW>(t, n, o, block_self, tile_flags[buf]);
         if (role == 0)
-            fold(std::integral_constant<int, 1>{});
+            BOIDS_FOLD_BY_FLAGS(PACKED, 1, s, h, tile_pv[buf], tile_z[buf], o, a, mkv);
         else
-            fold(std::integral_constant<int, 2>{});
-        if (more) publish(buf ^ 1);
+            BOIDS_FOLD_BY_FLAGS(PACKED, 2, s, h, tile_pv[buf], tile_z[buf], o, a, mkv);
+        if (more) boids_stage_publish<kSplitThreads>(st, a, tile_pv[buf ^ 1], tile_z[buf ^ 1], tile_flags[buf ^ 1], tid);
         __syncthreads();
         buf ^= 1;
     }
@@ -599,11 +625,11 @@ __global__ __launch_bounds__(kSplitThreads) void boids_split_kernel(BoidsArgs a)
         handoff[6][btid] = s.vcnt;
     }
     __syncthreads();
-    if (role == 0 && live) {
+    if (role == 0 && o.live) {
         s.rx = handoff[0][btid], s.ry = handoff[1][btid], s.rz = handoff[2][btid];
         s.mx = handoff[3][btid], s.my = handoff[4][btid], s.mz = handoff[5][btid];
         s.vcnt = handoff[6][btid];
-        boids_finish(a, s, l, pn);
+        boids_finish(a, s, o.l, o.pn);
     }
 }
 
@@ -810,17 +836,7 @@ __device__ __forceinline__ void boids_pc_body(const BoidsArgs &a)
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const uint32_t l = blockIdx.x * 64u + (uint32_t)lane;
-    const bool live = l < a.count;
-    const uint32_t gn = a.first + (live ? l : a.count - 1u);
-    const float4 pn = a.pos_in[gn];
-    const float4 vn = a.vel_in[gn];
-    auto wave_flags = [](uint32_t f) {
-        return (__any((int)(f & kBoidsNonFinite)) ? kBoidsNonFinite : 0u) | (__any((int)(f & kBoidsNonPlanar)) ? kBoidsNonPlanar : 0u) |
-               (__any((int)(f & kBoidsVelFar)) ? kBoidsVelFar : 0u);
-    };
-    const uint32_t self = wave_flags(boids_flags(pn, vn, a.vlim_bits) | a.force_flags);  // same 64 bodies in every wave
-    const uint32_t own_lo = a.first + blockIdx.x * 64u, own_hi = own_lo + 64u;
+    const BoidsOwn o = boids_own(a, 64u, (uint32_t)lane);  // the same 64 bodies in every wave
 
     const uint32_t n = a.n_total;
     const uint32_t ntiles = (n + (uint32_t)kBpcTile - 1u) / (uint32_t)kBpcTile;
@@ -849,7 +865,7 @@ __device__ __forceinline__ void boids_pc_body(const BoidsArgs &a)
             tile[buf].c[kSrcVx][ltid] = rec.v.x;
             tile[buf].c[kSrcVy][ltid] = rec.v.y;
             tile[buf].c[kSrcVz][ltid] = rec.v.z;
-            const uint32_t f = wave_flags(boids_flags(rec.p, rec.v, a.vlim_bits));
+            const uint32_t f = boids_wave_flags(boids_flags(rec.p, rec.v, a.vlim_bits));
             if (lane == 0) tile_flags[buf][wave - kBpcConsumers] = f;
         }
     };
@@ -866,15 +882,11 @@ __device__ __forceinline__ void boids_pc_body(const BoidsArgs &a)
         TileInfo ti;
         ti.tb = (int)(t & 1u);
         ti.stage = t + 1u < ntiles;
-        uint32_t f = self;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) f |= tile_flags[ti.tb][w];
-        ti.flags = __builtin_amdgcn_readfirstlane(f);
-        ti.j_first = t * (uint32_t)kBpcTile;
-        const uint32_t left = n - ti.j_first;
-        ti.nk = left >= (uint32_t)kBpcTile ? kBpcChunksPerTile : (int)((left + (uint32_t)kBpcChunk - 1u) / (uint32_t)kBpcChunk);
-        const uint32_t tile_n = left < (uint32_t)kBpcTile ? left : (uint32_t)kBpcTile;
-        ti.has_self = ti.j_first < own_hi && ti.j_first + tile_n > own_lo;
+        const BoidsTileHead h = boids_tile_head<kBpcTile, 8>(t, n, o, o.self, tile_flags[ti.tb]);
+        ti.flags = __builtin_amdgcn_readfirstlane(h.flags);
+        ti.j_first = h.j0;
+        ti.nk = (h.nj + kBpcChunk - 1) / kBpcChunk;
+        ti.has_self = h.has_self;
         if (ti.has_self) ti.flags |= kBoidsSelfTile;
         return ti;
     };
@@ -894,10 +906,10 @@ __device__ __forceinline__ void boids_pc_body(const BoidsArgs &a)
             pc_steps(ti.nk, [&](int k, int par) {
                 if (k == 0) {
                     if (!first_tile)
-                        bpc_fold_flags<ROLE>(prev_flags, ring[par ^ 1], tile[ti.tb ^ 1], (kBpcChunksPerTile - 1) * kBpcChunk, pn, lane,
+                        bpc_fold_flags<ROLE>(prev_flags, ring[par ^ 1], tile[ti.tb ^ 1], (kBpcChunksPerTile - 1) * kBpcChunk, o.pn, lane,
                                              kBpcChunk, sum_a, sum_b);
                 } else {
-                    bpc_fold_flags<ROLE>(ti.flags, ring[par ^ 1], tile[ti.tb], (k - 1) * kBpcChunk, pn, lane, kBpcChunk, sum_a, sum_b);
+                    bpc_fold_flags<ROLE>(ti.flags, ring[par ^ 1], tile[ti.tb], (k - 1) * kBpcChunk, o.pn, lane, kBpcChunk, sum_a, sum_b);
                 }
             }, nothing);
             prev_flags = ti.flags;
@@ -905,7 +917,7 @@ __device__ __forceinline__ void boids_pc_body(const BoidsArgs &a)
         // drain: the last chunk of the step (its tile buffer and ring slot are still intact)
         const int tb = (int)((ntiles - 1u) & 1u), k = last_nk - 1;
         const uint32_t first_j = (ntiles - 1u) * (uint32_t)kBpcTile + (uint32_t)k * (uint32_t)kBpcChunk;
-        bpc_fold_flags<ROLE>(prev_flags, ring[k & 1], tile[tb], k * kBpcChunk, pn, lane, (int)(n - first_j), sum_a, sum_b);
+        bpc_fold_flags<ROLE>(prev_flags, ring[k & 1], tile[tb], k * kBpcChunk, o.pn, lane, (int)(n - first_j), sum_a, sum_b);
         __syncthreads();  // every consumer is done with the ring: its storage now carries the sums (producers match this barrier)
         sums[ROLE][lane] = sum_a;
         if (ROLE == 2) sums[8][lane] = sum_b;   // centre z
@@ -928,7 +940,7 @@ __device__ __forceinline__ void boids_pc_body(const BoidsArgs &a)
                 pc_steps(ti.nk, [&](int k, int par) {
                     const int jt = k * kBpcChunk + j0;
                     bpc_produce<decltype(self_tag)::value, decltype(planar_tag)::value, decltype(all3_tag)::value>(
-                        tile[ti.tb], jt, ti.j_first + (uint32_t)jt, gn, pn, vn, a.r1, a.t2, a.t3, ring[par], j0, lane);
+                        tile[ti.tb], jt, ti.j_first + (uint32_t)jt, o.gn, o.pn, o.vn, a.r1, a.t2, a.t3, ring[par], j0, lane);
                 }, stage_next);
             };
             using T = std::true_type;
@@ -956,34 +968,12 @@ __device__ __forceinline__ void boids_pc_body(const BoidsArgs &a)
         default: producer(); break;
     }
     __syncthreads();
-    if (wave == 0 && live) {
-        float cx = sums[0][lane], cy = sums[1][lane], cz = sums[8][lane], mx = sums[5][lane], my = sums[6][lane], mz = sums[10][lane];
-        const float cnt = sums[2][lane], vcnt = sums[7][lane], rx = sums[3][lane], ry = sums[4][lane], rz = sums[9][lane];
-        if (cnt > 0.f) {  // main.rs:506-508
-            cx = cx / cnt;
-            cy = cy / cnt;
-            cz = cz / cnt;
-        }
-        if (vcnt > 0.f) {  // main.rs:510-512
-            mx = mx / vcnt;
-            my = my / vcnt;
-            mz = mz / vcnt;
-        }
-        const float ax = cx * a.s1, ay = cy * a.s1, az = cz * a.s1;  // main.rs:514
-        const float bx = rx * a.s2, by = ry * a.s2, bz = rz * a.s2;
-        const float gx = mx * a.s3, gy = my * a.s3, gz = mz * a.s3;
-        float vx = (ax + bx) + gx, vy = (ay + by) + gy, vz = (az + bz) + gz;
-        const float q0 = vx * vx, q1 = vy * vy, q2 = vz * vz;
-        const float mag = __builtin_sqrtf((q0 + q1) + q2);  // main.rs:516-518
-        if (mag > 1.0f) {
-            const float sc = 1.0f / mag;
-            vx = vx * sc;
-            vy = vy * sc;
-            vz = vz * sc;
-        }
-        const float sx = vx * a.dt, sy = vy * a.dt, sz = vz * a.dt;  // main.rs:521
-        a.vel_out[a.first + l] = make_float4(vx, vy, vz, 0.f);
-        a.pos_out[a.first + l] = make_float4(sx + pn.x, sy + pn.y, sz + pn.z, 0.f);
+    if (wave == 0 && o.live) {
+        const BoidsAcc s = {sums[0][lane], sums[1][lane], sums[8][lane],    // centre x, y, z
+                            sums[3][lane], sums[4][lane], sums[9][lane],    // repel
+                            sums[5][lane], sums[6][lane], sums[10][lane],   // match
+                            sums[2][lane], sums[7][lane]};                  // count, vcount
+        boids_finish(a, s, o.l, o.pn);
     }
 }
 
@@ -1004,6 +994,14 @@ hipError_t launch_boids_pc(const BoidsArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+// one launch of KERNEL<tile, packed, ...> on `grid` x `block`; every instantiation the unit holds is named below
+#define BOIDS_LAUNCH(KERNEL, ...) hipLaunchKernelGGL((KERNEL<__VA_ARGS__>), grid, block, 0, s, a)
+#define BOIDS_LAUNCH_PACKED(KERNEL, TJ)                      \
+    do {                                                     \
+        if (packed) BOIDS_LAUNCH(KERNEL, TJ, true);          \
+        else BOIDS_LAUNCH(KERNEL, TJ, false);                \
+    } while (0)
+
 // the split form: `slices` slices of a.j_chunk records (a multiple of the tile) x count / 256 workgroups, then the combine
 hipError_t launch_boids_split(const BoidsArgs &a, uint32_t tile, uint32_t slices, hipStream_t s)
 {
@@ -1014,9 +1012,9 @@ hipError_t launch_boids_split(const BoidsArgs &a, uint32_t tile, uint32_t slices
         hipLaunchKernelGGL(boids_prep_kernel, dim3(ceil_div_u(a.n_total, 1024u)), block, 0, s, a);
     }
     switch (tile) {
-        case 256: hipLaunchKernelGGL((boids_step_kernel<256, false, true>), grid, block, 0, s, a); break;
-        case 512: hipLaunchKernelGGL((boids_step_kernel<512, false, true>), grid, block, 0, s, a); break;
-        case 1024: hipLaunchKernelGGL((boids_step_kernel<1024, false, true>), grid, block, 0, s, a); break;
+        case 256: BOIDS_LAUNCH(boids_step_kernel, 256, false, true); break;
+        case 512: BOIDS_LAUNCH(boids_step_kernel, 512, false, true); break;
+        case 1024: BOIDS_LAUNCH(boids_step_kernel, 1024, false, true); break;
         default: return hipErrorInvalidValue;
     }
     hipLaunchKernelGGL(boids_combine_kernel, dim3(ceil_div_u(a.count, kBlock)), block, 0, s, a, slices);
@@ -1030,31 +1028,19 @@ hipError_t launch_boids(const BoidsArgs &a, uint32_t tile, uint32_t form, hipStr
     if (form == 3 || form == 4) {  // chain split: 512 threads stage a tile, so tiles of 512 or 1024 records
         const dim3 block(kSplitThreads);
         const bool packed = form == 4;
-        if (tile == 512) {
-            if (packed) hipLaunchKernelGGL((boids_split_kernel<512, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((boids_split_kernel<512, false>), grid, block, 0, s, a);
-        } else {
-            if (packed) hipLaunchKernelGGL((boids_split_kernel<1024, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((boids_split_kernel<1024, false>), grid, block, 0, s, a);
-        }
+        if (tile == 512) BOIDS_LAUNCH_PACKED(boids_split_kernel, 512);
+        else BOIDS_LAUNCH_PACKED(boids_split_kernel, 1024);
         return hipGetLastError();
     }
     const dim3 block(kBlock);
     const bool packed = form == 2;
     switch (tile) {
-        case 256:
-            if (packed) hipLaunchKernelGGL((boids_step_kernel<256, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((boids_step_kernel<256, false>), grid, block, 0, s, a);
-            break;
-        case 512:
-            if (packed) hipLaunchKernelGGL((boids_step_kernel<512, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((boids_step_kernel<512, false>), grid, block, 0, s, a);
-            break;
-        case 1024:
-            if (packed) hipLaunchKernelGGL((boids_step_kernel<1024, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((boids_step_kernel<1024, false>), grid, block, 0, s, a);
-            break;
+        case 256: BOIDS_LAUNCH_PACKED(boids_step_kernel, 256); break;
+        case 512: BOIDS_LAUNCH_PACKED(boids_step_kernel, 512); break;
+        case 1024: BOIDS_LAUNCH_PACKED(boids_step_kernel, 1024); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
+#undef BOIDS_LAUNCH_PACKED
+#undef BOIDS_LAUNCH

@@ -37,7 +37,7 @@
 //   nb_nbody_ring.inc    FAST pairs form on a shard ("half shell"): a second exchange carries the other GPUs' halves  (the scalar-load unit)
 //   nb_nbody_fast.inc    FAST kernels + fixed-order combine               (this unit)
 //   nb_aux.inc           model matrices, cameras, random walk, self-test  (this unit)
-//   nb_boids.inc         boids controller, one-lane and producer/consumer (SLP-off unit)
+//   nb_boids.inc         boids controller: one-lane, chain-split and producer/consumer kernels over one tile stage, form ladder and epilogue (SLP-off unit)
 //   nb_raster.inc        what the four files below share: vertices, clip, depth, fragment, sRGB bytes (SLP-off unit; device functions only)
 //   nb_eyes.inc          every entity's eye view: depth + entity id per column (SLP-off unit; its own launcher, nb_eyes.h)
 //   nb_frame.inc         the scene camera's frame: ids, depth and colour per pixel (SLP-off unit; its own launcher, nb_frame.h)

@@ -85,23 +85,33 @@ def test_boids_planar_state_every_form(nb, oracle, force, n):
     assert_bits_equal(v, v_ref)
 
 
-def test_boids_mixed_tiles(nb, oracle):
-    """Some tiles planar, some not, one with a non-finite record: every tile picks its own form."""
-    n = 2600
-    pos, vel = oracle.init_state(n, seed=99)
+def mixed_tiles(oracle, n, seed, z_run, vz_run, bad):
+    """a planar state with positions off the plane in [z_run), velocities off it in [vz_run) and a non-finite record at `bad`"""
+    pos, vel = oracle.init_state(n, seed=seed)
     pos *= np.float32(0.2)
-    pos[300:500, 2] = np.linspace(-3, 3, 200, dtype=np.float32)
-    vel[1500:1600, 2] = np.float32(0.05)
-    pos[2000, 0] = np.inf
-    with nb.Scene(pos, vel) as sc:
-        sc.step_boids_n(2)
-        p, v = sc.state()
-    p_ref, v_ref = oracle.boids_run(pos, vel, 2)
+    pos[z_run[0]:z_run[1], 2] = np.linspace(-3, 3, z_run[1] - z_run[0], dtype=np.float32)
+    vel[vz_run[0]:vz_run[1], 2] = np.float32(0.05)
+    pos[bad, 0] = np.inf
+    return pos, vel
+
+
+def assert_bits_equal_nan_alike(p, v, p_ref, v_ref):
+    """the oracle's bits wherever it has a number, a NaN (any payload) wherever it has one"""
     assert (np.isnan(p) == np.isnan(p_ref)).all() and (np.isnan(v) == np.isnan(v_ref)).all()
     ok = ~np.isnan(p_ref)
     assert (bits(p)[ok] == bits(p_ref)[ok]).all()
     okv = ~np.isnan(v_ref)
     assert (bits(v)[okv] == bits(v_ref)[okv]).all()
+
+
+def test_boids_mixed_tiles(nb, oracle):
+    """Some tiles planar, some not, one with a non-finite record: every tile picks its own form."""
+    pos, vel = mixed_tiles(oracle, 2600, 99, (300, 500), (1500, 1600), 2000)
+    with nb.Scene(pos, vel) as sc:
+        sc.step_boids_n(2)
+        p, v = sc.state()
+    p_ref, v_ref = oracle.boids_run(pos, vel, 2)
+    assert_bits_equal_nan_alike(p, v, p_ref, v_ref)
 
 
 def test_boids_reference_initial_state_long_run(nb, oracle):
