@@ -235,6 +235,42 @@ int nb_eyes_seen(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xy
 int nb_step_boids_seen(nb_ctx *ctx, uint32_t k, const nb_boids_params *params, const float *up_xyz, const float *cp16, uint32_t width,
                        uint32_t batch);
 
+/* WHERE an eye sees what it sees.  A resolved row holds a bearing (the column) and a range (the depth): the
+ * LOCATED seen set of eye e gives, per member of its seen set, the column at which the member is nearest and the seen point relative
+ * to the eye in world axes -- formed from the eye's own row, its own heading (its velocity record), `up` and the eyes' camera constant,
+ * from no body's position, not even its own.  Every step one binary32 operation, round to nearest, in the order written:
+ *   L1  seen_col[e*width + k], k < count: the least column c with ids[c] == seen_ids[k] and bits(depth[c]) == bits(seen_depth[k]);
+ *       no such column (a list that is not of this row): NB_EYES_NONE, and seen_rel[k] = four +0 words
+ *   L2  h = width*0.5; xc = c + 0.5; xn = (xc - h)/h; r = cp16[14] / (d + cp16[10]), d = seen_depth[k]; xv = (xn*r) / cp16[0]
+ *   L3  f = normalize(dir), s = normalize(f x up) as nb_cameras forms them (products first, one subtraction per component;
+ *       normalize(x) = x * (1 / sqrt((x0*x0 + x1*x1) + x2*x2)))
+ *   L4  seen_rel[(e*width + k)*4 ..] = (r*f0 + xv*s0, r*f1 + xv*s1, r*f2 + xv*s2, r): two products and one sum per component
+ *   L5  the slots k >= count: seen_col = NB_EYES_NONE, seen_rel = (+0, +0, +0, +0)
+ *   L6  L2 inverts cp16 * view only for a perspective constant of the shape nb_camera_constant produces: cp16[11] == -1,
+ *       cp16[1,2,3,4,6,7,8,9,12,13,15] all zero, cp16[0] != 0, cp16[14] != 0; any other constant is NB_ERR_INVALID (the eye rows
+ *       themselves accept any matrix: only the located entries refuse)
+ * A row is one pixel high: the estimate lies in the plane through the eye spanned by f and s -- on planar data the data's plane, where
+ * it is a point of the seen body's outline (within sqrt(2) of its centre, plus the depth buffer's resolution at that range).  A
+ * function of the row and the list: the same bits from run to run.
+ * nb_eyes_located: rows, seen sets and located sets of the eyes of bodies [first, first+count) of the context's current state, checks
+ * and staging as nb_eyes_seen.  Host outputs: seen_count count words; seen_ids, seen_depth, seen_cols, seen_col count*width words;
+ * seen_rel count*width*4 floats; any may be NULL, not all.  count = 0 is a no-op. */
+int nb_eyes_located(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width, uint32_t flags,
+                    uint32_t *seen_count, uint32_t *seen_ids, float *seen_depth, uint32_t *seen_cols, uint32_t *seen_col, float *seen_rel);
+
+/* k applications of update_instance_nbody (src/main.rs:404-441) from VISION ALONE, device-resident and asynchronous on the context's
+ * stream; may be mixed freely with the other steps.  One application to the state (P, V), with the context's nb_params (dt, G, bias):
+ *   G1  cameras, model matrices, eye rows with flags = 0 (ids and depth), seen sets with depth and located sets of every body, as
+ *       nb_eyes_located forms them from (P, V)
+ *   G2  body n starts sum = (0, 0, 0) and walks its slots in slot order: vec = seen_rel[k].xyz;
+ *       dist = ((vec.x*vec.x + vec.y*vec.y) + vec.z*vec.z) + bias; sum = sum + (vec*G)/dist per component -- the operations and
+ *       operand order of main.rs:428-430 with vec supplied by the row instead of p_i - p_n
+ *   G3  v = v + sum*dt; p = v + p (main.rs:434-436)
+ * A body that sees nobody coasts.  Eyes are processed `batch` at a time; every batch size gives the same bits.  batch = 0: the
+ * library's choice, the most eyes whose id and depth rows, list ids and depths, seen_rel and count (32 bytes a column, 4 bytes an eye)
+ * stay together at or below 64 MiB -- 2 047 at width 1024.  1 <= width <= NB_EYES_MAX_WIDTH; cp16 as L6 asks. */
+int nb_step_nbody_located(nb_ctx *ctx, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width, uint32_t batch);
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which
@@ -464,6 +500,27 @@ int nb_launch_seen(uint32_t count, uint32_t width, const void *ids_rows, const v
 int nb_launch_boids_seen_step(const nb_boids_params *params, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
                               const void *vel_in, const void *seen_count, const void *seen_ids, uint32_t stride, void *pos_out,
                               void *vel_out, void *stream);
+
+/* The located seen sets of `count` rows of `width` columns (nb_eyes_located's rule L1-L6), stateless, on caller-owned device memory:
+ * ids_rows (uint32) / depth_rows (float): count*width each, as nb_launch_eyes leaves them; seen_count, seen_ids, seen_depth: as
+ * nb_launch_seen leaves them for those rows (ascending, no duplicates; a count above width is taken as width); eyes / dirs: count
+ * 16-byte records as nb_launch_cameras takes them (the rule reads dirs alone: the estimate is relative to the eye); up_xyz / cp16:
+ * host pointers; seen_col (uint32, may be NULL): count*width; seen_rel: count*width records of 4 floats.  The rows, the lists and
+ * seen_col 4-byte aligned, eyes, dirs and seen_rel 16-byte aligned; no output may overlap the other output or an input.
+ * 1 <= width <= NB_EYES_MAX_WIDTH.  count = 0 is a no-op.  One kernel on `stream`.  (A stateless launch entry like the nb_launch_* ones;
+ * `launch` stands behind its name and that of the fold below.) */
+int nb_seen_located_launch(uint32_t count, uint32_t width, const void *ids_rows, const void *depth_rows, const void *seen_count,
+                           const void *seen_ids, const void *seen_depth, const void *eyes, const void *dirs, const float *up_xyz,
+                           const float *cp16, void *seen_col, void *seen_rel, void *stream);
+
+/* One gravity step over located lists (nb_step_nbody_located's G2-G3) for bodies [first, first+count) of a set of n_total: body
+ * first+e folds over the first seen_count[e] records (at most `stride`) of seen_rel[(e*stride + k)*4 ..] in slot order; what lies
+ * behind is never read.  pos_in, vel_in, pos_out, vel_out: n_total records each, only [first, first+count) is read and written;
+ * params == NULL -> defaults (dt, G and bias are used).  seen_count 4-byte aligned, the records and seen_rel 16-byte aligned,
+ * stride >= 1; the outputs must not alias the inputs or the lists. */
+int nb_nbody_located_step_launch(const nb_params *params, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
+                                 const void *vel_in, const void *seen_count, const void *seen_rel, uint32_t stride, void *pos_out,
+                                 void *vel_out, void *stream);
 
 /* nb_eyes_colour's rule, stateless, on caller-owned device memory: as nb_launch_eyes, plus skin = tw x th linear RGBA texels (row 0
  * first, 16-byte aligned, 1 <= tw, th <= NB_EYES_MAX_SKIN), or NULL for the 1 x 1 white skin (tw, th ignored); rgba: count*width*4

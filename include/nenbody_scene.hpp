@@ -158,6 +158,53 @@ public:
     {
         check(nb_step_boids_seen(ctx_, k, params, up.data(), cp[0].data(), width, batch), ctx_);
     }
+    // Where every eye sees the members of its seen set (nb_eyes_located): seen()'s lists (same arguments) plus, per member, the
+    // column at which it is nearest (col) and the seen point relative to the eye in world axes with its range (rel: x, y, z, r),
+    // formed from the eye's row, its heading, `up` and `cp` alone.  cp must be a perspective constant as nb_camera_constant forms
+    // it.  Behind the count[e] used slots col reads NB_EYES_NONE and rel four +0.
+    struct Located {
+        uint32_t width = 0;
+        std::vector<uint32_t> count, ids;
+        std::vector<float> depth;
+        std::vector<uint32_t> cols, col;
+        std::vector<std::array<float, 4>> rel;
+    };
+    Located located(const Mat4 &cp, uint32_t width = 1024, uint32_t first = 0, uint32_t count = UINT32_MAX, bool see_self = false,
+                    const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (count == UINT32_MAX) count = first <= positions.size() ? (uint32_t)positions.size() - first : 0;
+        Located s;
+        s.width = width;
+        const size_t cells = (size_t)count * width;
+        s.count.resize(count ? count : 1);    // (pointers the library can check even where count = 0)
+        s.ids.resize(cells ? cells : 1);
+        s.depth.resize(cells ? cells : 1);
+        s.cols.resize(cells ? cells : 1);
+        s.col.resize(cells ? cells : 1);
+        s.rel.resize(cells ? cells : 1);
+        check(nb_eyes_located(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, s.count.data(),
+                              s.ids.data(), s.depth.data(), s.cols.data(), s.col.data(), s.rel[0].data()),
+              ctx_);
+        s.count.resize(count);
+        s.ids.resize(cells);
+        s.depth.resize(cells);
+        s.cols.resize(cells);
+        s.col.resize(cells);
+        s.rel.resize(cells);
+        return s;
+    }
+    // one update_instance_nbody from vision alone (nb_step_nbody_located: body n folds the reference's law over the relative positions
+    // of located() instead of over p_i - p_n; one that sees nobody coasts); host mirrors refreshed.  batch: eyes processed at a time,
+    // 0 = the library's choice.
+    void step_nbody_located(const Mat4 &cp, uint32_t width = 1024, uint32_t batch = 0, const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        step_nbody_located_n(1, cp, width, batch, up);
+        check(nb_download(ctx_, positions[0].data(), velocities[0].data(), instances[0][0].data()), ctx_);
+    }
+    void step_nbody_located_n(uint32_t k, const Mat4 &cp, uint32_t width = 1024, uint32_t batch = 0, const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        check(nb_step_nbody_located(ctx_, k, up.data(), cp[0].data(), width, batch), ctx_);
+    }
     // The skin the colour rows sample: tw x th linear RGBA texels, row 0 first; an empty vector: the 1 x 1 white skin.
     void set_skin(const std::vector<std::array<float, 4>> &rgba_linear, uint32_t tw, uint32_t th)
     {

@@ -86,6 +86,9 @@ extern "C" {
     // what a controller makes of the eye rows: the seen set of every eye, and the boids step over it (null params = reference constants)
     fn nb_eyes_seen(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, seen_count: *mut u32, seen_ids: *mut u32, seen_depth: *mut f32, seen_cols: *mut u32) -> c_int;
     fn nb_step_boids_seen(ctx: *mut NbCtx, k: u32, params: *const NbBoidsParams, up_xyz: *const f32, cp16: *const f32, width: u32, batch: u32) -> c_int;
+    // where each eye sees the members of its seen set, and the gravity step over those relative positions alone (the context's nb_params)
+    fn nb_eyes_located(ctx: *mut NbCtx, first: u32, count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, flags: u32, seen_count: *mut u32, seen_ids: *mut u32, seen_depth: *mut f32, seen_cols: *mut u32, seen_col: *mut u32, seen_rel: *mut f32) -> c_int;
+    fn nb_step_nbody_located(ctx: *mut NbCtx, k: u32, up_xyz: *const f32, cp16: *const f32, width: u32, batch: u32) -> c_int;
     fn nb_srgb_decode_table(out256: *mut f32) -> c_int;
     fn nb_srgb_encode(linear: *const f32, n: usize, out: *mut u8) -> c_int;
     // the scene camera's frame (the reference's display pass, src/main.rs:948-960)
@@ -193,6 +196,17 @@ pub struct Seen {
     pub ids: Vec<u32>,   // NB_EYES_NONE behind the used slots
     pub depth: Vec<f32>, // the nearest depth at which the eye sees the entity, 1.0 behind the used slots
     pub cols: Vec<u32>,  // the number of columns the entity holds, 0 behind the used slots
+}
+
+/// What `Scene::located` returns: `Seen`'s lists plus, per member, where the eye sees it.
+pub struct Located {
+    pub width: u32,
+    pub count: Vec<u32>,
+    pub ids: Vec<u32>,
+    pub depth: Vec<f32>,
+    pub cols: Vec<u32>,
+    pub col: Vec<u32>,      // the column at which the entity is nearest, NB_EYES_NONE behind the used slots
+    pub rel: Vec<[f32; 4]>, // the seen point relative to the eye in world axes and its range (x, y, z, r), +0 behind the used slots
 }
 
 /// What `Scene::eyes_colour` returns: the same plus the colour attachment.
@@ -379,6 +393,60 @@ impl Scene {
     pub fn step_boids_seen(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32) -> Result<(), SceneError> {
         let up = [up.x, up.y, up.z];
         check(unsafe { nb_step_boids_seen(self.ctx, 1, std::ptr::null(), up.as_ptr(), cp.as_ptr() as *const f32, width, 0) }, self.ctx)?;
+        check(
+            unsafe {
+                nb_download(
+                    self.ctx,
+                    self.positions.as_mut_ptr() as *mut f32,
+                    self.velocities.as_mut_ptr() as *mut f32,
+                    self.instances.as_mut_ptr() as *mut f32,
+                )
+            },
+            self.ctx,
+        )
+    }
+
+    /// Where every eye sees the members of its seen set (nb_eyes_located) for bodies [first, first + count): `seen`'s lists plus the
+    /// column and the relative position of each member, formed from the eye's row, its heading, `up` and `cp` alone.  `cp` must be
+    /// a perspective constant as `camera_constant` forms it.
+    pub fn located(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32, first: u32, count: u32, see_self: bool) -> Result<Located, SceneError> {
+        let cells = count as usize * width as usize;
+        let mut s = Located {
+            width,
+            count: vec![0; (count as usize).max(1)],
+            ids: vec![0; cells.max(1)],
+            depth: vec![0.0; cells.max(1)],
+            cols: vec![0; cells.max(1)],
+            col: vec![0; cells.max(1)],
+            rel: vec![[0.0; 4]; cells.max(1)],
+        };
+        let up = [up.x, up.y, up.z];
+        let flags = if see_self { NB_EYES_SEE_SELF } else { 0 };
+        check(
+            unsafe {
+                nb_eyes_located(
+                    self.ctx, first, count, up.as_ptr(), cp.as_ptr() as *const f32, width, flags,
+                    s.count.as_mut_ptr(), s.ids.as_mut_ptr(), s.depth.as_mut_ptr(), s.cols.as_mut_ptr(), s.col.as_mut_ptr(),
+                    s.rel.as_mut_ptr() as *mut f32,
+                )
+            },
+            self.ctx,
+        )?;
+        s.count.truncate(count as usize);
+        s.ids.truncate(cells);
+        s.depth.truncate(cells);
+        s.cols.truncate(cells);
+        s.col.truncate(cells);
+        s.rel.truncate(cells);
+        Ok(s)
+    }
+
+    /// One update_instance_nbody from vision alone (nb_step_nbody_located): entity n folds the reference's law over the relative
+    /// positions of `located` instead of over p_i - p_n; one that sees nobody coasts.  Replaces the call at src/main.rs:925; mirrors
+    /// refreshed.
+    pub fn step_nbody_located(&mut self, cp: &[[f32; 4]; 4], up: Vector3<f32>, width: u32) -> Result<(), SceneError> {
+        let up = [up.x, up.y, up.z];
+        check(unsafe { nb_step_nbody_located(self.ctx, 1, up.as_ptr(), cp.as_ptr() as *const f32, width, 0) }, self.ctx)?;
         check(
             unsafe {
                 nb_download(

@@ -124,6 +124,16 @@ PROTOTYPES = {
     "nb_launch_boids_seen_step": (
         c_int, [POINTER(NbBoidsParams), c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
                 c_void_p]),
+    "nb_eyes_located": (
+        c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_void_p]),
+    "nb_seen_located_launch": (
+        c_int, [c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_void_p, c_void_p]),
+    "nb_step_nbody_located": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32]),
+    "nb_nbody_located_step_launch": (
+        c_int, [POINTER(NbParams), c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
+                c_void_p]),
     "nb_srgb_decode_table": (c_int, [c_void_p]),
     "nb_srgb_encode": (c_int, [c_void_p, c_size_t, c_void_p]),
     "nb_camera_at": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

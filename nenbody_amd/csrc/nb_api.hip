@@ -23,6 +23,7 @@
 #include "nb_eyes.h"
 #include "nb_frame.h"
 #include "nb_seen.h"
+#include "nb_located.h"
 #define NB_SRGB_TABLE static const
 #define NB_SRGB_WANT_DECODE
 #include "nb_srgb_tables.h"
@@ -930,6 +931,9 @@ struct nb_ctx {
     float *seen_depth = nullptr;
     uint32_t *seen_cols = nullptr;
     size_t seen_count_cap = 0, seen_ids_cap = 0, seen_depth_cap = 0, seen_cols_cap = 0;
+    uint32_t *loc_col = nullptr;     // nb_eyes_located's and nb_step_nbody_located's located rows, likewise: loc_*_cap slots (one word / one record each)
+    float4 *loc_rel = nullptr;
+    size_t loc_col_cap = 0, loc_rel_cap = 0;
     float *skin = nullptr;        // nb_eyes_skin's texels (skin_w x skin_h x 4 floats); null: the 1 x 1 white skin
     uint32_t skin_w = 0, skin_h = 0;
     uint64_t *frame_keys = nullptr;  // nb_frame's and nb_frame_msaa's key plane, grown on demand: frame_keys_cap keys (their rows are the eye rows above)
@@ -1023,6 +1027,8 @@ NB_EXPORT void nb_destroy(nb_ctx *ctx)
     if (ctx->seen_ids) (void)hipFree(ctx->seen_ids);
     if (ctx->seen_depth) (void)hipFree(ctx->seen_depth);
     if (ctx->seen_cols) (void)hipFree(ctx->seen_cols);
+    if (ctx->loc_col) (void)hipFree(ctx->loc_col);
+    if (ctx->loc_rel) (void)hipFree(ctx->loc_rel);
     if (ctx->skin) (void)hipFree(ctx->skin);
     if (ctx->frame_keys) (void)hipFree(ctx->frame_keys);
     if (ctx->frame_cam) (void)hipFree(ctx->frame_cam);
@@ -2356,5 +2362,6 @@ NB_EXPORT int nb_launch_unpack(uint32_t count, const void *rec4, void *xyz, void
 }
 
 #include "nb_seen_api.inc"
+#include "nb_located_api.inc"
 #include "nb_peers.inc"
 #include "nb_shard.inc"

@@ -44,6 +44,7 @@
 //   nb_eyes_msaa.inc     the eye view through 8 samples per column, resolved (SLP-off unit; launcher in nb_eyes.h)
 //   nb_frame_msaa.inc    the scene camera's frame through 8 samples per pixel, resolved (SLP-off unit; launcher in nb_frame.h)
 //   nb_seen.inc          the seen set of every eye row; the boids step over what each body sees (SLP-off unit; launchers in nb_seen.h)
+//   nb_located.inc       where each eye sees the members of its seen set; the gravity step over those relative positions (SLP-off unit; launchers in nb_located.h)
 //   nb_launch.inc        host-side launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +58,7 @@
 #include "nb_eyes.h"
 #include "nb_frame.h"
 #include "nb_seen.h"
+#include "nb_located.h"
 #endif
 
 namespace nbk {
@@ -81,6 +83,7 @@ static_assert(kMsaaOffsets16 == sample_nibbles(kEyeSampleX16) && kFrameMsaaOffse
 #include "nb_eyes_msaa.inc"   // the eye view through 8 samples per column: likewise; uses nb_eyes.inc's edge
 #include "nb_frame_msaa.inc"  // the frame through 8 samples per pixel: likewise; uses nb_frame.inc's edge and clear
 #include "nb_seen.inc"        // the seen set of every eye row and the boids step over it: likewise; uses nb_boids.inc's accumulators and epilogue
+#include "nb_located.inc"     // the located seen sets and the gravity step over them: likewise; uses nb_seen.inc's constants and nb_nbody_strict.inc's integrate
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

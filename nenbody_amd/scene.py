@@ -238,6 +238,42 @@ class Scene:
         check(self._lib.nb_step_boids_seen(self._ctx, int(k), ctypes.byref(params) if params is not None else None, upv.ctypes.data,
                                            cpm.ctypes.data, width, int(batch)), self._ctx)
 
+    def located(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, first: int = 0, count: Optional[int] = None,
+                see_self: bool = False):
+        """Where every eye sees the members of its seen set (nb_eyes_located) for bodies [first, first + count)
+        of the current state: per member of :meth:`seen` (same arguments) the column at which it is nearest and the seen point relative
+        to the eye in world axes, formed from the eye's row, its heading, ``up`` and ``cp`` alone.  ``cp`` must be a perspective
+        constant as :func:`camera_constant` forms it.  Returns (count, ids, depth, cols as :meth:`seen`, col uint32 (count, width) --
+        NB_EYES_NONE behind the first count[e] slots --, rel float32 (count, width, 4) -- (x, y, z, range), +0 there)."""
+        if count is None:
+            count = self.n - first
+        if first < 0 or count < 0:
+            raise ValueError("first and count must be >= 0")
+        upv, cpm = self._eye_setup(width, up, cp)
+        w = max(int(width), 0)
+        cnt = np.empty(count, np.uint32)
+        ids = np.empty((count, w), np.uint32)
+        depth = np.empty((count, w), np.float32)
+        cols = np.empty((count, w), np.uint32)
+        col = np.empty((count, w), np.uint32)
+        rel = np.empty((count, w, 4), np.float32)
+        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
+        check(self._lib.nb_eyes_located(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, cnt.ctypes.data,
+                                        ids.ctypes.data, depth.ctypes.data, cols.ctypes.data, col.ctypes.data, rel.ctypes.data), self._ctx)
+        return cnt, ids, depth, cols, col, rel
+
+    def step_nbody_located(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, batch: int = 0) -> None:
+        """One update_instance_nbody from vision alone (nb_step_nbody_located): body n folds the reference's
+        law over the relative positions of :meth:`located` instead of over p_i - p_n; one that sees nobody coasts.  Then refresh the
+        host mirrors.  ``batch``: eyes processed at a time (0: the library's choice); every value gives the same bits."""
+        self.step_nbody_located_n(1, width, up, cp, batch)
+        self._refresh(True)
+
+    def step_nbody_located_n(self, k: int, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, batch: int = 0) -> None:
+        """k such updates, device-resident and asynchronous; host mirrors are NOT refreshed."""
+        upv, cpm = self._eye_setup(width, up, cp)
+        check(self._lib.nb_step_nbody_located(self._ctx, int(k), upv.ctypes.data, cpm.ctypes.data, width, int(batch)), self._ctx)
+
     def set_skin(self, rgba=None) -> None:
         """The skin the colour rows sample (nb_eyes_skin): an array (th, tw, 4), row 0 first as the image file stores it -- floats
         are linear RGBA, uint8 is an sRGB image (Rgba8UnormSrgb: colour through :func:`srgb_decode`, alpha / 255).  None: the 1 x 1
