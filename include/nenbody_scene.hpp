@@ -107,12 +107,9 @@ public:
         Eyes e;
         e.width = width;
         const size_t cells = (size_t)count * width;
-        e.ids.resize(cells ? cells : 1);      // (a pointer the library can check even where count = 0)
-        e.depth.resize(cells ? cells : 1);
-        check(nb_eyes(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids.data(), e.depth.data()),
-              ctx_);
-        e.ids.resize(cells);
-        e.depth.resize(cells);
+        sized(cells, [&] {
+            return nb_eyes(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids.data(), e.depth.data());
+        }, e.ids, e.depth);
         return e;
     }
     // The seen set of every eye (nb_eyes_seen): which entities occur in the eye's row of eyes() (same arguments), ascending, with
@@ -131,17 +128,12 @@ public:
         Seen s;
         s.width = width;
         const size_t cells = (size_t)count * width;
-        s.count.resize(count ? count : 1);    // (pointers the library can check even where count = 0)
-        s.ids.resize(cells ? cells : 1);
-        s.depth.resize(cells ? cells : 1);
-        s.cols.resize(cells ? cells : 1);
-        check(nb_eyes_seen(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, s.count.data(),
-                           s.ids.data(), s.depth.data(), s.cols.data()),
-              ctx_);
+        s.count.resize(count ? count : 1);
+        sized(cells, [&] {
+            return nb_eyes_seen(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, s.count.data(),
+                                s.ids.data(), s.depth.data(), s.cols.data());
+        }, s.ids, s.depth, s.cols);
         s.count.resize(count);
-        s.ids.resize(cells);
-        s.depth.resize(cells);
-        s.cols.resize(cells);
         return s;
     }
     // one update_instance_boids restricted to what each entity sees (nb_step_boids_seen: body n folds over the entities of its own
@@ -176,21 +168,12 @@ public:
         Located s;
         s.width = width;
         const size_t cells = (size_t)count * width;
-        s.count.resize(count ? count : 1);    // (pointers the library can check even where count = 0)
-        s.ids.resize(cells ? cells : 1);
-        s.depth.resize(cells ? cells : 1);
-        s.cols.resize(cells ? cells : 1);
-        s.col.resize(cells ? cells : 1);
-        s.rel.resize(cells ? cells : 1);
-        check(nb_eyes_located(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, s.count.data(),
-                              s.ids.data(), s.depth.data(), s.cols.data(), s.col.data(), s.rel[0].data()),
-              ctx_);
+        s.count.resize(count ? count : 1);
+        sized(cells, [&] {
+            return nb_eyes_located(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, s.count.data(),
+                                   s.ids.data(), s.depth.data(), s.cols.data(), s.col.data(), s.rel[0].data());
+        }, s.ids, s.depth, s.cols, s.col, s.rel);
         s.count.resize(count);
-        s.ids.resize(cells);
-        s.depth.resize(cells);
-        s.cols.resize(cells);
-        s.col.resize(cells);
-        s.rel.resize(cells);
         return s;
     }
     // one update_instance_nbody from vision alone (nb_step_nbody_located: body n folds the reference's law over the relative positions
@@ -228,17 +211,10 @@ public:
         EyesColour e;
         e.width = width;
         const size_t cells = (size_t)count * width;
-        e.ids.resize(cells ? cells : 1);
-        e.depth.resize(cells ? cells : 1);
-        e.rgba.resize(cells ? cells : 1);
-        e.bgra8.resize(cells ? cells : 1);
-        check(nb_eyes_colour(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids.data(),
-                             e.depth.data(), e.rgba[0].data(), e.bgra8.data()),
-              ctx_);
-        e.ids.resize(cells);
-        e.depth.resize(cells);
-        e.rgba.resize(cells);
-        e.bgra8.resize(cells);
+        sized(cells, [&] {
+            return nb_eyes_colour(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids.data(),
+                                  e.depth.data(), e.rgba[0].data(), e.bgra8.data());
+        }, e.ids, e.depth, e.rgba, e.bgra8);
         return e;
     }
 
@@ -259,17 +235,10 @@ public:
         EyesMsaa e;
         e.width = width;
         const size_t cells = (size_t)count * width;
-        e.ids8.resize(cells ? cells : 1);
-        e.depth8.resize(cells ? cells : 1);
-        e.rgba.resize(cells ? cells : 1);
-        e.bgra8.resize(cells ? cells : 1);
-        check(nb_eyes_msaa(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids8[0].data(),
-                           e.depth8[0].data(), e.rgba[0].data(), e.bgra8.data()),
-              ctx_);
-        e.ids8.resize(cells);
-        e.depth8.resize(cells);
-        e.rgba.resize(cells);
-        e.bgra8.resize(cells);
+        sized(cells, [&] {
+            return nb_eyes_msaa(ctx_, first, count, up.data(), cp[0].data(), width, see_self ? NB_EYES_SEE_SELF : 0u, e.ids8[0].data(),
+                                e.depth8[0].data(), e.rgba[0].data(), e.bgra8.data());
+        }, e.ids8, e.depth8, e.rgba, e.bgra8);
         return e;
     }
 
@@ -332,6 +301,14 @@ public:
     }
 
 private:
+    // `rows` at least one element long for `call` (pointers the library can check even where count = 0), `cells` behind it
+    template <typename Call, typename... Rows>
+    void sized(size_t cells, Call call, Rows &...rows)
+    {
+        (rows.resize(cells ? cells : 1), ...);
+        check(call(), ctx_);
+        (rows.resize(cells), ...);
+    }
     void create(const nb_params &params)
     {
         check_abi();

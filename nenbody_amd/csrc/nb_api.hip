@@ -962,6 +962,13 @@ struct nb_ctx {
         }                                                                                          \
     } while (0)
 
+// one of the context's buffers of a fixed size (vel_alt, cams, inst, frame_cam): allocated on first use, kept until nb_destroy
+template <typename T>
+static hipError_t first_use(T **buf, size_t bytes)
+{
+    return *buf ? hipSuccess : hipMalloc((void **)buf, bytes);
+}
+
 NB_EXPORT int nb_abi_version(void) { return NB_ABI_VERSION; }
 
 NB_EXPORT void nb_default_params(nb_params *p)
@@ -1288,7 +1295,7 @@ NB_EXPORT int nb_step_boids(nb_ctx *ctx, uint32_t k, const nb_boids_params *para
     uint32_t tile = 0;
     int rc = make_boids_args(p, ctx->n, 0, ctx->n, &a, &tile, &ctx->err);
     if (rc != NB_OK) return rc;
-    if (!ctx->vel_alt) NB_HIP(ctx, hipMalloc((void **)&ctx->vel_alt, (size_t)ctx->n * sizeof(float4)));
+    NB_HIP(ctx, first_use(&ctx->vel_alt, (size_t)ctx->n * sizeof(float4)));
     RoctxRange range("nb_step_boids");
     for (uint32_t s = 0; s < k; ++s) {
         a.pos_in = ctx->pos[ctx->cur];
@@ -1331,7 +1338,7 @@ NB_EXPORT int nb_device_state(nb_ctx *ctx, const void **pos_rec, const void **ve
         return NB_ERR_STATE;
     }
     if (inst_16n) {
-        if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+        NB_HIP(ctx, first_use(&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
         NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
         *inst_16n = ctx->inst;
     }
@@ -1387,7 +1394,7 @@ NB_EXPORT int nb_cameras(nb_ctx *ctx, const float *up_xyz, const float *cp16, fl
         ctx->err = "nb_cameras: no state uploaded";
         return NB_ERR_STATE;
     }
-    if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, first_use(&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
     NB_HIP(ctx, nbk::launch_cameras(ctx->n, ctx->pos[ctx->cur], ctx->vel, up_xyz, cp16, ctx->cams, ctx->stream));
     NB_HIP(ctx, hipMemcpyAsync(out_16n, ctx->cams, (size_t)ctx->n * 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1451,14 +1458,16 @@ static int frame_extent_check(const char *fn, uint32_t width, uint32_t height, b
     return NB_OK;
 }
 
-// The outputs ids, depth, rgba, bgra8 (NULL: not wanted): one of those in `need` (bit a: out[a]) at least, or none_msg; 4-byte
-// aligned where aligned4 asks for it; no two may overlap, and none may overlap one of the inputs `in` (a frame's scratch among them).
-static int outputs_check(const char *fn, const ByteRange (&out)[4], uint32_t need, const char *none_msg, bool aligned4, const ByteRange *in,
+// The outputs of an entry (ids, depth, rgba, bgra8; the lists of a seen or located set; NULL: not wanted): one of those in `need`
+// (bit a: out[a]) at least, or none_msg; 4-byte aligned where aligned4 asks for it; no two may overlap, and none may overlap one of
+// the inputs `in` (a frame's scratch among them).
+template <int N>
+static int outputs_check(const char *fn, const ByteRange (&out)[N], uint32_t need, const char *none_msg, bool aligned4, const ByteRange *in,
                          int n_in, const char *alias_msg, std::string *err)
 {
     uintptr_t bits = 0;
     bool any = false;
-    for (int a = 0; a < 4; ++a) {
+    for (int a = 0; a < N; ++a) {
         bits |= (uintptr_t)out[a].p;
         any = any || ((need >> a & 1u) && out[a].p);
     }
@@ -1470,9 +1479,9 @@ static int outputs_check(const char *fn, const ByteRange (&out)[4], uint32_t nee
         *err = std::string(fn) + ": the outputs must be 4-byte aligned";
         return NB_ERR_INVALID;
     }
-    for (int a = 0; a < 4; ++a) {
+    for (int a = 0; a < N; ++a) {
         bool alias = false;
-        for (int b = a + 1; b < 4; ++b)
+        for (int b = a + 1; b < N; ++b)
             alias = alias || (out[a].p && out[a].p == out[b].p) || ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes);
         for (int b = 0; b < n_in; ++b) alias = alias || ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes);
         if (alias) {
@@ -1515,10 +1524,10 @@ static int grow_rows(nb_ctx *ctx, const void *ids, const void *depth, const void
 static int stage_matrices(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16)
 {
     if (up_xyz) {
-        if (!ctx->cams) NB_HIP(ctx, hipMalloc((void **)&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
+        NB_HIP(ctx, first_use(&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
         NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
     }
-    if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, first_use(&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
     NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
     return NB_OK;
 }
@@ -1690,7 +1699,7 @@ NB_EXPORT int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_x
         ctx->err = "nb_camera_at: null argument";
         return NB_ERR_INVALID;
     }
-    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
+    NB_HIP(ctx, first_use(&ctx->frame_cam, 6 * sizeof(float4)));
     // the eye and the direction as the 16-byte records the camera kernel reads, behind the camera's own four
     const float rec[8] = {eye_xyz[0], eye_xyz[1], eye_xyz[2], 0.0f, dir_xyz[0], dir_xyz[1], dir_xyz[2], 0.0f};
     NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam + 4, rec, sizeof(rec), hipMemcpyHostToDevice, ctx->stream));
@@ -1705,7 +1714,7 @@ NB_EXPORT int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_x
 static int stage_frame(nb_ctx *ctx, const float *cam16, size_t keys)
 {
     NB_HIP(ctx, grow_row(&ctx->frame_keys, &ctx->frame_keys_cap, keys, sizeof(uint64_t)));
-    if (!ctx->frame_cam) NB_HIP(ctx, hipMalloc((void **)&ctx->frame_cam, 6 * sizeof(float4)));
+    NB_HIP(ctx, first_use(&ctx->frame_cam, 6 * sizeof(float4)));
     NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     return NB_OK;
 }
@@ -1845,7 +1854,7 @@ NB_EXPORT int nb_download(nb_ctx *ctx, float *pos_xyz, float *vel_xyz, float *in
         NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (inst_16n) {
-        if (!ctx->inst) NB_HIP(ctx, hipMalloc((void **)&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+        NB_HIP(ctx, first_use(&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
         NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
         NB_HIP(ctx, hipMemcpyAsync(inst_16n, ctx->inst, (size_t)ctx->n * 16 * sizeof(float), hipMemcpyDeviceToHost,
                                    ctx->stream));
@@ -2361,7 +2370,6 @@ NB_EXPORT int nb_launch_unpack(uint32_t count, const void *rec4, void *xyz, void
     NB_LAUNCH_TLS(nbk::launch_unpack(count, (const float4 *)rec4, (float *)xyz, (hipStream_t)stream));
 }
 
-#include "nb_seen_api.inc"
-#include "nb_located_api.inc"
+#include "nb_vision_api.inc"   // the seen and located sets and the steps over them (DESIGN.md sections 12 and 13)
 #include "nb_peers.inc"
 #include "nb_shard.inc"

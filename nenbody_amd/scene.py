@@ -103,6 +103,10 @@ def init_state(n: int, seed: int = 1234):
     return pos, vel
 
 
+# the arrays an eye-row entry fills (Scene._eye_rows): (dtype, shape behind (count, width)), None for one word an eye
+_PER_EYE, _U32, _F32, _RGBA = (np.uint32, None), (np.uint32, ()), (np.float32, ()), (np.float32, (4,))
+
+
 class Scene:
     """Device-resident n-body state with the update of src/main.rs:404-441 as :meth:`step`.
 
@@ -182,25 +186,26 @@ class Scene:
         reference's depth attachment holds after its eye pass, one row of ``width`` pixels per entity, and which entity wrote each
         pixel.  ``cp`` is the eyes' camera constant, (4, 4) with [k] = column k; None: the reference's, :func:`eye_constant`.
         Returns (ids uint32 (count, width) -- NB_EYES_NONE where nothing covers the column --, depth float32 (count, width))."""
+        return self._eye_rows(self._lib.nb_eyes, (_U32, _F32), width, up, cp, first, count, see_self)
+
+    def _eye_setup(self, width, up, cp, max_width=_lib.NB_EYES_MAX_WIDTH):
+        if cp is None:   # (an invalid width is the library's to refuse)
+            cp = eye_constant(width) if 0 < width <= max_width else np.zeros((4, 4), np.float32)
+        return np.ascontiguousarray(up, np.float32).reshape(3), np.ascontiguousarray(cp, np.float32).reshape(16)
+
+    def _eye_rows(self, entry, outputs, width, up, cp, first, count, see_self, max_width=_lib.NB_EYES_MAX_WIDTH):
+        """What the eye-row methods share: the defaults of ``count`` and ``cp``, the arrays ``entry`` fills -- one per (dtype, tail)
+        of ``outputs``, shaped (count, width) + tail, or (count,) where tail is None -- and the call.  Returns those arrays."""
         if count is None:
             count = self.n - first
         if first < 0 or count < 0:
             raise ValueError("first and count must be >= 0")
-        if cp is None:   # (an invalid width is the library's to refuse)
-            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MAX_WIDTH else np.zeros((4, 4), np.float32)
-        upv = np.ascontiguousarray(up, np.float32).reshape(3)
-        cpm = np.ascontiguousarray(cp, np.float32).reshape(16)
-        ids = np.empty((count, max(int(width), 0)), np.uint32)
-        depth = np.empty((count, max(int(width), 0)), np.float32)
+        upv, cpm = self._eye_setup(width, up, cp, max_width)
+        w = max(int(width), 0)
+        out = tuple(np.empty((count,) if tail is None else (count, w) + tail, dtype) for dtype, tail in outputs)
         flags = _lib.NB_EYES_SEE_SELF if see_self else 0
-        check(self._lib.nb_eyes(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, ids.ctypes.data,
-                                depth.ctypes.data), self._ctx)
-        return ids, depth
-
-    def _eye_setup(self, width, up, cp):
-        if cp is None:   # (an invalid width is the library's to refuse)
-            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MAX_WIDTH else np.zeros((4, 4), np.float32)
-        return np.ascontiguousarray(up, np.float32).reshape(3), np.ascontiguousarray(cp, np.float32).reshape(16)
+        check(entry(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, *(a.ctypes.data for a in out)), self._ctx)
+        return out
 
     def seen(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, first: int = 0, count: Optional[int] = None,
              see_self: bool = False):
@@ -208,20 +213,7 @@ class Scene:
         entities occur in the eye's row of :meth:`eyes` (same arguments), in ascending order, with the nearest depth and the number of
         columns of each.  Returns (count uint32 (count,), ids uint32 (count, width) -- NB_EYES_NONE behind the first count[e] slots --,
         depth float32 (count, width) -- 1.0 there --, cols uint32 (count, width) -- 0 there)."""
-        if count is None:
-            count = self.n - first
-        if first < 0 or count < 0:
-            raise ValueError("first and count must be >= 0")
-        upv, cpm = self._eye_setup(width, up, cp)
-        w = max(int(width), 0)
-        cnt = np.empty(count, np.uint32)
-        ids = np.empty((count, w), np.uint32)
-        depth = np.empty((count, w), np.float32)
-        cols = np.empty((count, w), np.uint32)
-        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
-        check(self._lib.nb_eyes_seen(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, cnt.ctypes.data,
-                                     ids.ctypes.data, depth.ctypes.data, cols.ctypes.data), self._ctx)
-        return cnt, ids, depth, cols
+        return self._eye_rows(self._lib.nb_eyes_seen, (_PER_EYE, _U32, _F32, _U32), width, up, cp, first, count, see_self)
 
     def step_boids_seen(self, params: Optional[NbBoidsParams] = None, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None,
                         batch: int = 0) -> None:
@@ -245,22 +237,7 @@ class Scene:
         to the eye in world axes, formed from the eye's row, its heading, ``up`` and ``cp`` alone.  ``cp`` must be a perspective
         constant as :func:`camera_constant` forms it.  Returns (count, ids, depth, cols as :meth:`seen`, col uint32 (count, width) --
         NB_EYES_NONE behind the first count[e] slots --, rel float32 (count, width, 4) -- (x, y, z, range), +0 there)."""
-        if count is None:
-            count = self.n - first
-        if first < 0 or count < 0:
-            raise ValueError("first and count must be >= 0")
-        upv, cpm = self._eye_setup(width, up, cp)
-        w = max(int(width), 0)
-        cnt = np.empty(count, np.uint32)
-        ids = np.empty((count, w), np.uint32)
-        depth = np.empty((count, w), np.float32)
-        cols = np.empty((count, w), np.uint32)
-        col = np.empty((count, w), np.uint32)
-        rel = np.empty((count, w, 4), np.float32)
-        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
-        check(self._lib.nb_eyes_located(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, cnt.ctypes.data,
-                                        ids.ctypes.data, depth.ctypes.data, cols.ctypes.data, col.ctypes.data, rel.ctypes.data), self._ctx)
-        return cnt, ids, depth, cols, col, rel
+        return self._eye_rows(self._lib.nb_eyes_located, (_PER_EYE, _U32, _F32, _U32, _U32, _RGBA), width, up, cp, first, count, see_self)
 
     def step_nbody_located(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, batch: int = 0) -> None:
         """One update_instance_nbody from vision alone (nb_step_nbody_located): body n folds the reference's
@@ -298,23 +275,7 @@ class Scene:
         winning fragment's texel of the skin (:meth:`set_skin`) under the vignette, or the clear colour.
         Returns (ids, depth, rgba float32 (count, width, 4) linear, bgra8 uint32 (count, width) whose bytes are B, G, R, A: the
         texel of the reference's Bgra8UnormSrgb target)."""
-        if count is None:
-            count = self.n - first
-        if first < 0 or count < 0:
-            raise ValueError("first and count must be >= 0")
-        if cp is None:   # (an invalid width is the library's to refuse)
-            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MAX_WIDTH else np.zeros((4, 4), np.float32)
-        upv = np.ascontiguousarray(up, np.float32).reshape(3)
-        cpm = np.ascontiguousarray(cp, np.float32).reshape(16)
-        w = max(int(width), 0)
-        ids = np.empty((count, w), np.uint32)
-        depth = np.empty((count, w), np.float32)
-        rgba = np.empty((count, w, 4), np.float32)
-        bgra8 = np.empty((count, w), np.uint32)
-        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
-        check(self._lib.nb_eyes_colour(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, ids.ctypes.data,
-                                       depth.ctypes.data, rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
-        return ids, depth, rgba, bgra8
+        return self._eye_rows(self._lib.nb_eyes_colour, (_U32, _F32, _RGBA, _U32), width, up, cp, first, count, see_self)
 
     def eyes_msaa(self, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None, first: int = 0, count: Optional[int] = None,
                   see_self: bool = False):
@@ -324,23 +285,9 @@ class Scene:
         empty.  ``width`` is at most NB_EYES_MSAA_MAX_WIDTH.
         Returns (ids8 uint32 (count, width, 8), depth8 float32 (count, width, 8), rgba float32 (count, width, 4) linear, bgra8
         uint32 (count, width) whose bytes are B, G, R, A)."""
-        if count is None:
-            count = self.n - first
-        if first < 0 or count < 0:
-            raise ValueError("first and count must be >= 0")
-        if cp is None:   # (an invalid width is the library's to refuse)
-            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MSAA_MAX_WIDTH else np.zeros((4, 4), np.float32)
-        upv = np.ascontiguousarray(up, np.float32).reshape(3)
-        cpm = np.ascontiguousarray(cp, np.float32).reshape(16)
-        w = max(int(width), 0)
-        ids8 = np.empty((count, w, _lib.NB_EYES_SAMPLES), np.uint32)
-        depth8 = np.empty((count, w, _lib.NB_EYES_SAMPLES), np.float32)
-        rgba = np.empty((count, w, 4), np.float32)
-        bgra8 = np.empty((count, w), np.uint32)
-        flags = _lib.NB_EYES_SEE_SELF if see_self else 0
-        check(self._lib.nb_eyes_msaa(self._ctx, first, count, upv.ctypes.data, cpm.ctypes.data, width, flags, ids8.ctypes.data,
-                                     depth8.ctypes.data, rgba.ctypes.data, bgra8.ctypes.data), self._ctx)
-        return ids8, depth8, rgba, bgra8
+        samples = (_lib.NB_EYES_SAMPLES,)
+        return self._eye_rows(self._lib.nb_eyes_msaa, ((np.uint32, samples), (np.float32, samples), _RGBA, _U32), width, up, cp, first,
+                              count, see_self, _lib.NB_EYES_MSAA_MAX_WIDTH)
 
     def viewport(self, camera: int, scale: float = 0.1, extent=(1024, 768), width: int = 1024, up=(0.0, 0.0, 1.0), cp=None,
                  see_self: bool = False, msaa: bool = False) -> np.ndarray:
