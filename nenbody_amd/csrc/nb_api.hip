@@ -20,6 +20,7 @@
 #include "../../include/nenbody.h"
 #include "../../include/nenbody_diag.h"
 #include "nb_kernels.h"
+#include "nb_plan.h"
 #include "nb_eyes.h"
 #include "nb_frame.h"
 #include "nb_seen.h"
@@ -36,12 +37,13 @@ namespace {
 
 thread_local std::string g_tls_error = "";
 
-// MI355X: 256 CUs x 4 SIMDs.  FAST launches aim at 16 waves per SIMD's worth of work items: four times what is resident at
-// once (4 bodies per lane: 120 registers, 4 waves per SIMD).  Measured at N = 131 072 (profiles/r02/fast_forms.log): with
-// exactly one resident round (512 workgroups of 8 waves) the step takes 2.80 ms, with two rounds 2.62, with four 2.53 --
-// workgroups that all start together finish when the slowest CU does, later rounds go to whoever is free.
-constexpr uint32_t kTargetWaves = 16384;
-constexpr uint32_t kMaxSlices = 64;
+using nbp::DebugOverrides;
+using nbp::floor_log2f;
+using nbp::Form;
+using nbp::Knob;
+using nbp::PhasePlan;
+using nbp::Plan;
+using nbp::valid_tile;
 
 // ---- diagnostic overrides -----------------------------------------------------------------------------------
 // The parity tests pin every kernel form and the sweeps in tools/ time them; both do it through NB_* environment
@@ -50,19 +52,6 @@ constexpr uint32_t kMaxSlices = 64;
 // library is steered by nothing its environment happens to export (round 4; VERDICT r03 item 11: until then an inherited
 // NB_TILE or NB_FAST_SL changed which kernels ran).  The one exception is NB_ROCTX, which is a feature for the host (tracing),
 // not a kernel form.  No launch path calls getenv.
-struct Knob {
-    bool set = false;
-    uint32_t v = 0;
-    // the override if present, else the default
-    uint32_t or_else(uint32_t dflt) const { return set ? v : dflt; }
-    bool on() const { return set && v != 0; }
-};
-struct DebugOverrides {
-    Knob tile, fast_pairs_w, fast_pairs_np, fast_pairs_chunk, fast_ib, fast_groups, fast_waves, fast_slices, fast_no_share, strict_force_ieee, force_3d, strict_no_packed, strict_lanes, strict_unroll,
-        strict_pc, strict_bc, strict_sl, fast_sl, fast_pairs, ring, ring_np, ring_ga, ring_wpb, ring_c4_own, ring_c4_rest, ring_cap, inst_device_libm, boids_slices, bc_spin_budget, bc_prio, boids_pc, boids_tile, boids_force, selftest_control, roctx, dropin_zero_copy, dropin_poll, dropin_poll_budget_us;
-    uint32_t generation = 0;  // bumped by every reload: invalidates cached plans
-};
-
 Knob read_knob(const char *name)
 {
     Knob k;
@@ -87,43 +76,7 @@ const DebugOverrides *parse_overrides(uint32_t generation)
     d->generation = generation;
     d->roctx = read_knob("NB_ROCTX");
     if (!g_env_enabled.load(std::memory_order_relaxed)) return d;  // a bare load of the library: no kernel-form override is read
-    d->tile = read_knob("NB_TILE");
-    d->fast_ib = read_knob("NB_FAST_IB");
-    d->fast_groups = read_knob("NB_FAST_GROUPS");
-    d->fast_waves = read_knob("NB_FAST_WAVES");
-    d->fast_slices = read_knob("NB_FAST_SLICES");
-    d->fast_no_share = read_knob("NB_FAST_NO_SHARE");
-    d->strict_force_ieee = read_knob("NB_STRICT_FORCE_IEEE");
-    d->force_3d = read_knob("NB_FORCE_3D");
-    d->strict_no_packed = read_knob("NB_STRICT_NO_PACKED");
-    d->strict_lanes = read_knob("NB_STRICT_LANES");
-    d->strict_unroll = read_knob("NB_STRICT_UNROLL");
-    d->strict_pc = read_knob("NB_STRICT_PC");
-    d->strict_bc = read_knob("NB_STRICT_BC");
-    d->strict_sl = read_knob("NB_STRICT_SL");
-    d->fast_sl = read_knob("NB_FAST_SL");
-    d->fast_pairs = read_knob("NB_FAST_PAIRS");
-    d->fast_pairs_w = read_knob("NB_FAST_PAIRS_W");
-    d->fast_pairs_chunk = read_knob("NB_FAST_PAIRS_CHUNK");
-    d->fast_pairs_np = read_knob("NB_FAST_PAIRS_NP");
-    d->inst_device_libm = read_knob("NB_INST_DEVICE_LIBM");
-    d->ring = read_knob("NB_RING");
-    d->ring_np = read_knob("NB_RING_NP");
-    d->ring_ga = read_knob("NB_RING_GA");
-    d->ring_wpb = read_knob("NB_RING_WPB");
-    d->ring_c4_own = read_knob("NB_RING_C4_OWN");
-    d->ring_c4_rest = read_knob("NB_RING_C4_REST");
-    d->ring_cap = read_knob("NB_RING_CAP");
-    d->bc_spin_budget = read_knob("NB_BC_SPIN_BUDGET");
-    d->bc_prio = read_knob("NB_BC_PRIO");
-    d->boids_pc = read_knob("NB_BOIDS_PC");
-    d->boids_tile = read_knob("NB_BOIDS_TILE");
-    d->boids_force = read_knob("NB_BOIDS_FORCE");
-    d->boids_slices = read_knob("NB_BOIDS_SLICES");
-    d->dropin_zero_copy = read_knob("NB_DROPIN_ZERO_COPY");
-    d->dropin_poll = read_knob("NB_DROPIN_POLL");
-    d->dropin_poll_budget_us = read_knob("NB_DROPIN_POLL_BUDGET_US");
-    d->selftest_control = read_knob("NB_SELFTEST_CONTROL");
+    for (const nbp::KnobName &k : nbp::kKnobNames) d->*k.knob = read_knob(k.name);
     return d;
 }
 
@@ -140,256 +93,19 @@ const DebugOverrides &overrides()
     return *d;
 }
 
-bool valid_tile(uint32_t t) { return t == 256 || t == 512 || t == 1024; }
-
-struct Plan {
-    uint32_t tile;
-    uint32_t ib;      // FAST: bodies per thread
-    uint32_t waves;   // FAST: 0 = workgroup-tile form; else the barrier-free form with this many waves per workgroup (= groups)
-    uint32_t groups;  // FAST: 256-lane groups per workgroup, each folding its own j chunk (combined in LDS)
-    uint32_t slices;  // FAST: blockIdx.y slices of the j range (combined through memory)
-    uint32_t j_chunk; // FAST: records per chunk (groups * slices chunks cover the set)
-    uint32_t lo_bits, hi_bits, force_ieee;  // STRICT guard
-    int guard_a, guard_b, guard_g, guard_c; // its exponents: coordinates in {0} U [2^a, 2^b], |G| in [2^g, 2^(g+1)), bias in [2^c, 2^(c+1))
-    uint32_t force_3d;                      // 2 = never take the planar shortcut (NB_FORCE_3D=1: tests, measurements)
-    uint32_t unroll;                        // STRICT: pairs in flight per lane (2, 4 or 8)
-    uint32_t lanes;                         // STRICT: lanes per body (1 = plain; 2..16 = j-parallel, same summation order)
-    uint32_t pc;                            // STRICT: 0 = off, else producers per workgroup of the producer/consumer form (8 or 14)
-    uint32_t no_packed;                     // STRICT, one lane per body: 1 = do not use the j-packed planar fold (NB_STRICT_NO_PACKED=1)
-    uint32_t bc;                            // STRICT: 1 = block-chain form (nb_nbody_bc.inc) instead of producer/consumer; needs scratch
-    uint32_t pairs;                         // FAST: the pairs form (nb_nbody_sym.inc: every unordered pair once; whole sets, n a multiple of 256; needs scratch) with this many waves per workgroup (8, 4, 2, 1); 0 = another form
-    uint32_t pairs_np;                      // pairs form: packed pairs of bodies per lane, 2 or 4 (blocks of 256 or 512 bodies)
-    uint32_t pairs_chunk;                   // pairs form: bodies per chunk of the two-level walk (0: the default -- one tile up to 262 144 bodies, chunks of 131 072 beyond)
-    uint32_t fsl;                           // FAST: 1 = scalar-load form (step_fast_sl_kernel, nb_nbody_sl.inc): whole-set launches, eight waves per workgroup; needs scratch
-    uint32_t sl;                            // STRICT: 1 = scalar-load form (nb_nbody_sl.inc) instead of the LDS-tiled one-lane kernel; needs scratch
-    uint32_t spin_budget;                   // block chain: polls per wait, 0 = kernel default (NB_BC_SPIN_BUDGET: the give-up test)
-    uint32_t bc_prio;                       // block chain: raised wave priority around the chain turns (NB_BC_PRIO=0 switches it off)
-    uint32_t n_total;                       // the set size the plan was made for
-};
-
-int floor_log2f(float x)
-{
-    int e;
-    std::frexp(x, &e);  // x = m * 2^e, m in [0.5, 1)
-    return e - 1;
-}
-
-// FAST: bodies per thread; two or four also let the thread's pairs share reciprocals
-uint32_t fast_bodies_per_lane(uint32_t n_total, uint32_t count)
-{
-    // by the size of the launch, in pairs (measured, profiles/r02/fast_forms.log): 16 384 of 131 072 bodies: 4 (0.340 ms
-    // against 0.360 with 2); standalone sets of 32 768 and 16 384: 2 (0.184 against 0.207 with 4); 8 192 and below: 1
-    const uint64_t pairs = (uint64_t)n_total * count;
-    uint32_t ib = overrides().fast_ib.or_else(pairs >= (1ull << 31) ? 4u : pairs >= (1ull << 27) ? 2u : 1u);
-    return (ib == 1 || ib == 2 || ib == 4) ? ib : 1u;
-}
-
-// FAST: 0 = the workgroup-tile form (step_fast_kernel), else waves per workgroup of the barrier-free form (1, 4, 8 or 16)
-uint32_t fast_wave_form()
-{
-    const uint32_t w = overrides().fast_waves.or_else(8u);  // NB_FAST_WAVES=0: the workgroup-tile form
-    return (w == 1 || w == 4 || w == 8 || w == 16) ? w : 0u;
-}
-
-// FAST: how a fold over `n_fold` records is split for `count` bodies at `ib` bodies per lane: `groups` chunks inside a
-// workgroup (combined in LDS) times `slices` across workgroups (combined through memory by integrate_partials_kernel),
-// `chunk` records each (a multiple of the tile).  The split aims at kTargetWaves waves in all.
-// `waves` != 0 selects the barrier-free form (step_fast_wave_kernel): a workgroup is `waves` waves that share 64*ib bodies
-// and fold one chunk each; then *groups = waves.
-void fast_split(uint32_t n_fold, uint32_t count, uint32_t ib, uint32_t waves, uint32_t *tile, uint32_t *groups, uint32_t *slices,
-                uint32_t *chunk)
-{
-    const DebugOverrides &dbg = overrides();
-    if (waves && *tile == 1024u) *tile = 512u;  // the wave form stages a whole tile per wave: 256 or 512 records
-    if (waves && *tile == 512u && (ib == 1 || waves == 1)) *tile = 256u;  // built 512-record shapes: 4, 8, 16 waves at 2 / 4 bodies per lane
-    const uint32_t bodies = waves ? 64u * ib : 256u * ib, chunk_waves = waves ? 1u : 4u;
-    const uint32_t blocks = (count + bodies - 1u) / bodies;
-    const uint32_t max_by_tiles = std::max(1u, (n_fold + *tile - 1u) / *tile);
-    uint32_t split = (kTargetWaves + blocks * chunk_waves - 1u) / (blocks * chunk_waves);
-    if (split > max_by_tiles) split = max_by_tiles;
-    if (split < 1) split = 1;
-    uint32_t g = waves ? waves : dbg.fast_groups.or_else(split >= 4u ? 4u : split >= 2u ? 2u : 1u);
-    if (!waves && g != 1 && g != 2 && g != 4) g = 1;
-    if (!waves && *tile == 1024u) g = 1;  // groups are built for tiles of 256 and 512 records (4 x 2 x 1024 records = 128 KB of LDS)
-    uint32_t sl = dbg.fast_slices.or_else((split + g - 1u) / g);
-    if (sl > kMaxSlices) sl = kMaxSlices;
-    if (sl < 1) sl = 1;
-    uint32_t chunks = sl * g;
-    if (chunks > max_by_tiles) chunks = max_by_tiles;
-    uint32_t c = (std::max(n_fold, 1u) + chunks - 1u) / chunks;
-    c = ((c + *tile - 1u) / *tile) * *tile;
-    chunks = (std::max(n_fold, 1u) + c - 1u) / c;   // drop empty chunks ...
-    sl = (chunks + g - 1u) / g;                     // ... and the slices made of them
-    *groups = g;
-    *slices = sl;
-    *chunk = c;
-}
-
-// Launch shape + STRICT guard range for (params, n_total, count).  Pure host arithmetic.
+// The planner itself is nb_plan.h (pure host arithmetic); here it meets the process's overrides and the kernels' own sizes.
 int make_plan(const nb_params &p, uint32_t n_total, uint32_t count, Plan *out, std::string *err)
 {
-    if (n_total == 0 || count == 0 || count > n_total) {
-        *err = "nb: need 0 < count <= n_total";
-        return NB_ERR_INVALID;
-    }
-    if (p.mode != NB_MODE_STRICT && p.mode != NB_MODE_FAST) {
-        *err = "nb: params.mode must be NB_MODE_STRICT or NB_MODE_FAST";
-        return NB_ERR_INVALID;
-    }
-    if (n_total > 0x80000000u) {  // the kernels index records and tiles in 32 bits with headroom for padding
-        *err = "nb: sets of more than 2^31 bodies are not supported";
-        return NB_ERR_UNSUPPORTED;
-    }
-    const DebugOverrides &dbg = overrides();
-    Plan pl{};
-    pl.tile = p.tile;
-    // FAST: the barrier-free form stages a whole tile per wave (256 records: 4 per lane, 120 registers at 4 bodies per lane;
-    // 512 would take 142 and cost a wave per SIMD); the workgroup-tile form shares tiles of 512
-    if (pl.tile == 0) pl.tile = dbg.tile.or_else((p.mode == NB_MODE_STRICT) ? 1024u : fast_wave_form() ? 256u : 512u);
-    if (!valid_tile(pl.tile)) {
-        *err = "nb: params.tile must be 0, 256, 512 or 1024";
-        return NB_ERR_INVALID;
-    }
-    pl.ib = 1;
-    pl.groups = 1;
-    pl.slices = 1;
-    pl.j_chunk = n_total;
-    if (p.mode == NB_MODE_FAST) {
-        pl.ib = fast_bodies_per_lane(n_total, count);
-        pl.waves = fast_wave_form();
-        fast_split(n_total, count, pl.ib, pl.waves, &pl.tile, &pl.groups, &pl.slices, &pl.j_chunk);
-    }
-    // FAST through scalar loads (nb_nbody_sl.inc) for sets of 4 096 bodies and more (below, its second launch -- the planes --
-    // costs more than it saves): the same split of the j range over eight waves per workgroup and grid.y slices.  Naming a
-    // tile, a wave count or groups asks for one of the LDS forms; NB_FAST_SL=0/1 decides outright.
-    if (p.mode == NB_MODE_FAST) {
-        const bool no_form_named = p.tile == 0 && !dbg.tile.set && !dbg.fast_waves.set && !dbg.fast_groups.set;
-        pl.fsl = dbg.fast_sl.or_else((pl.waves == 8u && n_total >= 4096u && no_form_named) ? 1u : 0u);
-        // The pairs form (nb_nbody_sym.inc): every UNORDERED pair once.  Whole sets only (both bodies of a pair on this GPU), n a
-        // multiple of its 256-body blocks.  One workgroup of W waves per pair of superblocks of 256 W bodies; measured by size and W
-        // (profiles/r03/pairs_sizes.log): it wins from 32 768 bodies on (0.95 of the ordered fold's time there, 0.82 at 65 536,
-        // 0.76-0.78 from 114 688 on), with W = 4 below 131 072 (eight-wave workgroups are too few and too long there: 1.12 ms
-        // against 1.02 at 98 304) and W = 8 from there on (the same time as W = 4 and half the rows).  The rows of partial sums
-        // take n x superblocks x 12 B -- 100 MB at n = 131 072 --, so sets of more than 262 144 bodies are walked in chunks of
-        // 131 072 (tiles of one or two chunks, each tile's rows added to running sums before the next: 0.2 GB of rows + 12 B per
-        // body, whatever the size; up to 4 194 304 bodies).
-        // NB_FAST_PAIRS=0/1 decides outright where it can run, NB_FAST_PAIRS_W names W (8, 4, 2, 1), NB_FAST_PAIRS_CHUNK the chunk.
-        constexpr uint32_t kPairsMinN = 32768u;
-        const bool pairs_ok = count == n_total && n_total % 256u == 0 && n_total <= 4194304u;
-        // From 98 304 bodies on a lane holds EIGHT bodies (four packed pairs, blocks of 512) where the size allows: the step's fixed
-        // costs -- the rotating sums' four instructions, the LDS read, the hazard nops -- are shared by twice the pairs: 1.68 against
-        // 1.78 ms at 131 072 (W = 4), 6.61 against 7.19 at 262 144, 106 against 114 at 2^20 (profiles/r03/pairs_sizes_np.log); below,
-        // four bodies per lane (142 registers leave three waves per SIMD, too few where the workgroups are few as well).
-        uint32_t pnp = (n_total >= 98304u && n_total % 512u == 0) ? 4u : 2u;
-        if (dbg.fast_pairs_np.set && (dbg.fast_pairs_np.v == 2 || (dbg.fast_pairs_np.v == 4 && n_total % 512u == 0))) pnp = dbg.fast_pairs_np.v;
-        uint32_t pw = pnp == 4u ? (n_total >= 131072u ? 4u : 2u) : (n_total >= 131072u ? 8u : 4u);
-        if (dbg.fast_pairs_w.set && (dbg.fast_pairs_w.v == 1 || dbg.fast_pairs_w.v == 2 || dbg.fast_pairs_w.v == 4 || (dbg.fast_pairs_w.v == 8 && pnp == 2u)))
-            pw = dbg.fast_pairs_w.v;
-        pl.pairs = (pairs_ok && dbg.fast_pairs.or_else((n_total >= kPairsMinN && no_form_named && !dbg.fast_sl.set && !dbg.fast_ib.set &&
-                                                        !dbg.fast_slices.set) ? 1u : 0u)) ? pw : 0u;
-        pl.pairs_np = pnp;
-        pl.pairs_chunk = 0;
-        if (pl.pairs && dbg.fast_pairs_chunk.on()) {  // whole superblocks per chunk
-            const uint32_t super = 128u * pnp * pw;
-            pl.pairs_chunk = std::max(super, dbg.fast_pairs_chunk.v / super * super);
-        }
-        if (pl.pairs) pl.fsl = 0;
-        if (pl.fsl) {  // its own split: 8 waves per workgroup, chunks of whole 256-record tiles (16-record requests stay aligned)
-            uint32_t tile = 256u;
-            pl.waves = 8u;
-            fast_split(n_total, count, pl.ib, pl.waves, &tile, &pl.groups, &pl.slices, &pl.j_chunk);
-            pl.tile = tile;
-        }
-    }
-    // STRICT: magnitude range {0} U [2^a, 2^b] of coordinates for which d, n = dx*G, q = n/d and the
-    // ladder's residuals are all normal binary32 with headroom, so that v_div_scale/v_div_fixup would be
-    // the identity and the shared-reciprocal ladder equals the IEEE divide bit for bit.
-    //   nonzero |dx| >= 2^(a-23), |dx| <= 2^(b+1);  d in [bias, 3*2^(2b+2)+bias];  |n| >= 2^(a-23+g)
-    pl.force_ieee = 1;
-    pl.lo_bits = 0x3f800000u;
-    pl.hi_bits = 0x3f800000u;
-    const float G = std::fabs(p.G);
-    if (std::isfinite(p.G) && std::isfinite(p.bias) && G > 0.f && p.bias > 0.f) {
-        const int g = floor_log2f(G), c = floor_log2f(p.bias);
-        const int b = 20;
-        const int dmax = std::max(2 * b + 4, c + 2);
-        int a = std::max(-100 + 23 - g, -120 + 23 - g + dmax);
-        const bool ok = g >= -100 && g <= 100 && c >= -100 && dmax <= 100 && (b + 2 + g - c) <= 120 && a <= b - 1;
-        if (ok) {
-            if (a < -120) a = -120;
-            pl.lo_bits = (uint32_t)(a + 127) << 23;
-            pl.hi_bits = (uint32_t)(b + 127) << 23;
-            pl.force_ieee = 0;
-            pl.guard_a = a;
-            pl.guard_b = b;
-            pl.guard_g = g;
-            pl.guard_c = c;
-        }
-    }
-    if (dbg.strict_force_ieee.on()) pl.force_ieee = 1;
-    if (p.mode == NB_MODE_FAST) {
-        // FAST reuses the field: 1 = never share a reciprocal between two pairs (the product of two r^2 must stay normal:
-        // bias in [2^-60, 2^60]; coordinates are checked per tile on the device).  NB_FAST_NO_SHARE=1: tests, measurements.
-        const bool bias_ok = std::isfinite(p.bias) && p.bias >= 0x1p-60f && p.bias <= 0x1p60f;
-        pl.force_ieee = (!bias_ok || dbg.fast_no_share.on()) ? 1u : 0u;
-    }
-    pl.force_3d = dbg.force_3d.on() ? 2u : 0u;
-    pl.no_packed = dbg.strict_no_packed.on() ? 1u : 0u;
-    // STRICT cannot split the fold over j (the sum is sequential), so a small shard would leave SIMDs idle:
-    // below 65 536 bodies give each body S lanes until the shard supplies 2 waves per SIMD (256 CUs x 4 SIMDs x 2 =
-    // 2048 waves).  The DPP adds of the j-parallel form cost about twice a plain add, so S = 1 stays ahead down to
-    // one wave per SIMD (measured: profiles/r01_jp/sweep_lanes.log).
-    // (Round 3: the line is 57 344 bodies, not 65 536 -- above it the scalar-load kernel, one wave per SIMD and nothing to wait
-    // for, beats every chained form: a 65 536-body shard of 131 072 takes 2.95 ms against the block chain's 3.35,
-    // profiles/r03/shard_strict_forms.log; the block chain costs 0.84 ms per 16 384 bodies, so the two meet at 57 500.)
-    constexpr uint32_t kChainMax = 57344u;
-    pl.lanes = 1;
-    if (count <= kChainMax)
-        while (pl.lanes < 16 && (uint64_t)count * pl.lanes < 2048ull * 64ull) pl.lanes *= 2;
-    pl.lanes = dbg.strict_lanes.or_else(pl.lanes);
-    if (pl.lanes != 1 && pl.lanes != 2 && pl.lanes != 4 && pl.lanes != 8 && pl.lanes != 16) pl.lanes = 1;
-    pl.unroll = dbg.strict_unroll.or_else(pl.lanes == 1 ? 8 : (pl.lanes == 16 ? 2 : 4));
-    if (pl.lanes == 1 && pl.unroll != 4 && pl.unroll != 8 && pl.unroll != 16) pl.unroll = 8;
-    if (pl.lanes > 1 && pl.unroll != 2 && pl.unroll != 4) pl.unroll = 4;
-    if (pl.lanes == 16) pl.unroll = 2;
-    if (p.mode == NB_MODE_STRICT && pl.lanes > 1 && pl.tile == 512) pl.tile = 1024;  // built j-parallel shapes: 256, 1024
-    if (p.mode == NB_MODE_STRICT && pl.lanes > 1 && pl.tile == 1024 && pl.unroll == 2 && pl.lanes < 8) pl.unroll = 4;
-    // Shards of up to 57 344 bodies (round 1-2: 65 536) cannot fill the chip with one lane per body (the running sum is a serial chain per
-    // body).  Default there: the block-chain form (nb_nbody_bc.inc).  Against all 131 072 bodies: 16 384 bodies 0.85 ms
-    // (producer/consumer, 14 producers + 2 consumers per 64 bodies: 1.15; j-parallel S = 8: 2.1), 32 768: 1.67 (2.28),
-    // 65 536: 3.30 (one lane per body 3.52); the whole set: 6.57 against 6.19 for one lane per body, which therefore keeps
-    // everything above (profiles/r01_final/pc_sweep.log).  It needs scratch memory (nb_scratch_bytes).
-    // Small SETS (tools/small_forms.py, profiles/r02/small_forms.log; microseconds per step, j-parallel / producer-consumer /
-    // block chain): N = 100: 3.7 / 4.3 / 6.9, 1 024: 11.6 / 12.8 / 12.4, 2 048: 20.2 / 21.5 / 19.9, 3 072: 28.9 / 30.0 / 25.8,
-    // 4 096: 37.8 / 39.5 / 32.9 -- below 1 536 bodies the j-parallel form (the block chain's second launch costs more than
-    // the form gains), from there on the block chain (round 1's four launches had put that line at 4 096).
-    // Naming another shape (NB_STRICT_PC / NB_STRICT_LANES) turns the block chain off; NB_STRICT_BC=0/1 decides outright.
-    constexpr uint32_t kSmallSet = 1536u;
-    pl.pc = dbg.strict_pc.or_else((count <= kChainMax && n_total >= kSmallSet) ? 14u : 0u);
-    if (pl.pc == 1) pl.pc = 8;
-    if (pl.pc != 0 && pl.pc != 8 && pl.pc != 14) pl.pc = 8;
-    pl.n_total = n_total;
-    pl.bc = dbg.strict_bc.or_else((count <= kChainMax && n_total >= kSmallSet && !dbg.strict_pc.set && !dbg.strict_lanes.set) ? 1u : 0u);
-    pl.bc = (pl.bc && p.mode == NB_MODE_STRICT) ? 1u : 0u;
-    pl.spin_budget = dbg.bc_spin_budget.or_else(0u);
-    pl.bc_prio = dbg.bc_prio.or_else(1u) ? 1u : 0u;
-    // Above the block chain's range (whole sets, shards of more than 57 344 bodies) one lane per body fills the chip, and the
-    // records reach the lanes through scalar loads instead of LDS tiles: no barrier, no ds_read (nb_nbody_sl.inc).  Naming a
-    // tile (params.tile / NB_TILE), a lane count or the producer/consumer form asks for the LDS-tiled kernel; NB_STRICT_SL=0/1 decides outright.
-    pl.sl = dbg.strict_sl.or_else((!pl.bc && !pl.pc && pl.lanes == 1 && p.tile == 0 && !dbg.tile.set && !dbg.strict_lanes.set &&
-                                   !dbg.strict_pc.set && !dbg.strict_unroll.set && !dbg.strict_no_packed.set && n_total >= kSmallSet) ? 1u : 0u);
-    pl.sl = (pl.sl && p.mode == NB_MODE_STRICT && !pl.bc) ? std::min(pl.sl, 3u) : 0u;  // NB_STRICT_SL = 1 + launch shape (nb_nbody_sl.inc)
-    *out = pl;
-    return NB_OK;
+    return nbp::make_plan(p, n_total, count, overrides(), out, err);
 }
 
-size_t plan_scratch_bytes(const Plan &pl, uint32_t count)
-{
-    if (pl.bc || pl.sl) return nbk::strict_bc_scratch_bytes(pl.n_total);
-    if (pl.pairs) return nbk::strict_bc_scratch_bytes(pl.n_total) + nbk::fast_pairs_scratch_floats(pl.n_total, pl.pairs, pl.pairs_np, pl.pairs_chunk) * sizeof(float);
-    if (pl.fsl) return nbk::strict_bc_scratch_bytes(pl.n_total) + (pl.slices > 1 ? (size_t)pl.slices * count * sizeof(float4) : 0);
-    return pl.slices > 1 ? (size_t)pl.slices * count * sizeof(float4) : 0;
-}
+struct KernelSizes {
+    size_t planes_bytes(uint32_t n) const { return nbk::strict_bc_scratch_bytes(n); }
+    uint32_t pairs_chunk(uint32_t n, uint32_t chunk) const { return nbk::fast_pairs_chunk(n, chunk); }
+    uint32_t pairs_rows(uint32_t n, uint32_t w, uint32_t np) const { return nbk::fast_pairs_rows(n, w, np); }
+    size_t pairs_scratch_floats(uint32_t n, uint32_t w, uint32_t np, uint32_t chunk) const { return nbk::fast_pairs_scratch_floats(n, w, np, chunk); }
+};
+size_t plan_scratch_bytes(const Plan &pl, uint32_t count) { return nbp::plan_scratch_bytes(pl, count, KernelSizes{}); }
 
 // The launch API is stateless; a rank calls it with the same shape every step.  A few planned shapes per thread are kept (no lock:
 // one thread drives one GPU), keyed by everything the planners read: the parameters, the shape words and the overrides'
@@ -579,24 +295,47 @@ int check_status(StatusWord *sw, std::string *err)
     return check_status_word(sw->w, err);
 }
 
-// What every step launch fills alike: the buffers, the shape, the constants and the plan's two verdicts.  The fields only some forms
-// read (the guard bits, j_chunk, the j range and its hole, partial rows, the block chain's knobs) stay with the caller.
+// What every step launch fills alike: the buffers, the shape, the constants, every plan-derived word (nb_plan.h: plan_step_args), and a
+// whole-set fold -- partial rows in `partial`, the whole set as the j range, no hole.  The phases name their own rows, range and hole;
+// the ring launches read none of the three.
 nbk::StepArgs step_args(const nb_params &p, const Plan &pl, uint32_t n_total, uint32_t first, uint32_t count, const void *pos_in,
-                        void *pos_out, void *vel)
+                        void *pos_out, void *vel, void *partial = nullptr)
 {
     nbk::StepArgs a{};
     a.pos_in = (const float4 *)pos_in;
     a.pos_out = (float4 *)pos_out;
     a.vel = (float4 *)vel;
+    a.partial = (float4 *)partial;
     a.n_total = n_total;
     a.first = first;
     a.count = count;
     a.dt = p.dt;
     a.G = p.G;
     a.bias = p.bias;
-    a.force_ieee = pl.force_ieee;
-    a.force_3d = pl.force_3d;
+    a.j_count = n_total;
+    a.hole_lo = 0xffffffffu;
+    nbp::plan_step_args(pl, &a);
     return a;
+}
+
+// The one dispatch: nb_plan.h's visit_launch() names the launcher and its scalar arguments, this calls it.
+struct Launchers {
+    const nbk::StepArgs &a;
+    void *scratch;
+    uint32_t *status;
+    hipStream_t s;
+    hipError_t strict(uint32_t tile, uint32_t unroll, uint32_t lanes) const { return nbk::launch_strict(a, tile, unroll, lanes, s); }
+    hipError_t strict_pc(uint32_t producers) const { return nbk::launch_strict_pc(a, producers, s); }
+    hipError_t strict_bc() const { return nbk::launch_strict_bc(a, scratch, status, s); }
+    hipError_t strict_sl(uint32_t shape) const { return nbk::launch_strict_sl(a, shape, scratch, s); }
+    hipError_t fast(uint32_t tile, uint32_t ib, uint32_t groups, uint32_t slices) const { return nbk::launch_fast(a, tile, ib, groups, slices, s); }
+    hipError_t fast_wave(uint32_t tile, uint32_t ib, uint32_t waves, uint32_t slices) const { return nbk::launch_fast_wave(a, tile, ib, waves, slices, s); }
+    hipError_t fast_sl(uint32_t ib, uint32_t slices) const { return nbk::launch_fast_sl(a, ib, slices, scratch, s); }
+    hipError_t fast_pairs(uint32_t w, uint32_t np, uint32_t chunk) const { return nbk::launch_fast_pairs(a, w, np, chunk, scratch, s); }
+};
+hipError_t launch_planned(const Plan &pl, const nbk::StepArgs &a, void *scratch, uint32_t *status, hipStream_t stream)
+{
+    return nbp::visit_launch(pl, Launchers{a, scratch, status, stream});
 }
 
 // A launcher's answer as a status: NB_ERR_HIP with `what` (the caller's own text, up to and including ": ") and the runtime's words.
@@ -612,32 +351,14 @@ int launch_step_planned(const nb_params &p, const Plan &pl, uint32_t n_total, ui
                         const void *pos_in, void *pos_out, void *vel, void *scratch, hipStream_t stream, std::string *err,
                         StatusWord *sw = nullptr)
 {
-    nbk::StepArgs a = step_args(p, pl, n_total, first, count, pos_in, pos_out, vel);
-    a.partial = (float4 *)scratch;
-    a.lo_bits = pl.lo_bits;
-    a.hi_bits = pl.hi_bits;
-    a.j_chunk = pl.j_chunk;
-    a.no_packed = pl.no_packed;
-    a.spin_budget = pl.spin_budget;
-    a.bc_prio = pl.bc_prio;
-    a.j_count = n_total;  // the whole set: no base, no hole
-    a.j_base = 0;
-    a.hole_lo = 0xffffffffu;
-    a.hole_len = 0;
+    const nbk::StepArgs a = step_args(p, pl, n_total, first, count, pos_in, pos_out, vel, scratch);
     uint32_t *status = nullptr;
-    if (p.mode == NB_MODE_STRICT && pl.bc) {
+    if (nbp::form_info(pl.form).status_word) {
         int rc = sw ? status_word_for_launch(sw, err) : device_status_word(&status, err);
         if (rc != NB_OK) return rc;
         if (sw) status = sw->w;
     }
-    hipError_t e = (p.mode == NB_MODE_STRICT) ? (pl.bc   ? nbk::launch_strict_bc(a, scratch, status, stream)
-                                                 : pl.sl ? nbk::launch_strict_sl(a, pl.sl - 1u, scratch, stream)
-                                                 : pl.pc ? nbk::launch_strict_pc(a, pl.pc, stream)
-                                                       : nbk::launch_strict(a, pl.tile, pl.unroll, pl.lanes, stream))
-                                              : pl.pairs ? nbk::launch_fast_pairs(a, pl.pairs, pl.pairs_np, pl.pairs_chunk, scratch, stream)
-                                              : pl.fsl   ? nbk::launch_fast_sl(a, pl.ib, pl.slices, scratch, stream)
-                                              : pl.waves ? nbk::launch_fast_wave(a, pl.tile, pl.ib, pl.waves, pl.slices, stream)
-                                                         : nbk::launch_fast(a, pl.tile, pl.ib, pl.groups, pl.slices, stream);
+    hipError_t e = launch_planned(pl, a, scratch, status, stream);
     if (e == hipErrorNotSupported) {  // a launch shape only the diagnostic knobs can name, in a build without -DNB_LEGACY_FORMS
         *err = "nb: this launch shape is one of the legacy forms (NB_STRICT_PC / NB_STRICT_LANES / NB_STRICT_UNROLL / NB_STRICT_SL=2,3 / "
                "NB_FAST_WAVES / NB_FAST_GROUPS / NB_FAST_PAIRS_W): this library was built without them (make -C nenbody_amd/csrc legacy "
@@ -1932,43 +1653,13 @@ NB_EXPORT int nb_launch_status(void *stream)
 
 // ---- a FAST step in two phases ("Overlap") -------------------------------------------------
 namespace {
-struct PhasePlan {
-    Plan base;                 // tile, ib, the sharing verdict, force_3d ...
-    uint32_t len[2];           // records folded by phase 0 (the range) and phase 1 (the rest)
-    uint32_t groups[2], slices[2], chunk[2];
-    uint32_t fsl;              // 1 = the phases fold through scalar loads (step_fast_sl_kernel; the planes area in front of the rows), 0 = LDS forms
-};
-
+// the two-phase planner is nb_plan.h's too
 int make_phase_plan(const nb_params &p, uint32_t n_total, uint32_t count, uint32_t j_lo, uint32_t j_hi, PhasePlan *out, std::string *err)
 {
-    if (p.mode != NB_MODE_FAST) {
-        *err = "nb: a step in phases is FAST only: the reference's sum runs j = 0..N-1 in order, and STRICT keeps that order";
-        return NB_ERR_UNSUPPORTED;
-    }
-    if (j_lo > j_hi || j_hi > n_total) {
-        *err = "nb: need j_lo <= j_hi <= n_total";
-        return NB_ERR_INVALID;
-    }
-    int rc = make_plan(p, n_total, count, &out->base, err);
-    if (rc != NB_OK) return rc;
-    out->len[0] = j_hi - j_lo;
-    out->len[1] = n_total - out->len[0];
-    // Through scalar loads where a shard's one-call step would go that way (the plan's own choice, never the pairs form: a phase
-    // folds a range of j's, not pairs): eight waves per workgroup, chunks of whole 256-record tiles; else the LDS forms.
-    out->fsl = (out->base.fsl || out->base.pairs) ? 1u : 0u;
-    for (int ph = 0; ph < 2; ++ph) {
-        uint32_t tile = out->fsl ? 256u : out->base.tile;
-        fast_split(out->len[ph], count, out->base.ib, out->fsl ? 8u : out->base.waves, &tile, &out->groups[ph], &out->slices[ph], &out->chunk[ph]);
-    }
-    return NB_OK;
+    return nbp::make_phase_plan(p, n_total, count, j_lo, j_hi, overrides(), out, err);
 }
-size_t phase_scratch_bytes(const PhasePlan &pp, uint32_t count)
-{
-    return (pp.fsl ? nbk::strict_bc_scratch_bytes(pp.base.n_total) : 0) + (size_t)(pp.slices[0] + pp.slices[1]) * count * sizeof(float4);
-}
-}  // namespace
+size_t phase_scratch_bytes(const PhasePlan &pp, uint32_t count) { return nbp::phase_scratch_bytes(pp, count, KernelSizes{}); }
 
-namespace {
 // as cached_plan: a rank asks for the same two phases every step
 int cached_phase_plan(const nb_params &p, uint32_t n_total, uint32_t count, uint32_t j_lo, uint32_t j_hi, const PhasePlan **out,
                       std::string *err)
@@ -1993,38 +1684,30 @@ namespace {
 int launch_phase_planned(const nb_params &p, const PhasePlan &pp, uint32_t n_total, uint32_t first, uint32_t count, uint32_t j_lo,
                          int phase, const void *pos_in, void *pos_out, void *vel, void *scratch, hipStream_t stream, std::string *err)
 {
-    const Plan &pl = pp.base;
-    nbk::StepArgs a = step_args(p, pl, n_total, first, count, pos_in, pos_out, vel);
-    char *const rows = pp.fsl ? nbk::plane_scratch(scratch, n_total).behind : (char *)scratch;  // the partial rows: behind the planes area
+    nbk::StepArgs a = step_args(p, pp.base, n_total, first, count, pos_in, pos_out, vel);
+    char *const rows = nbp::phase_sl(pp) ? nbk::plane_scratch(scratch, n_total).behind : (char *)scratch;  // the partial rows: behind the planes area
     a.partial = (float4 *)rows;
     a.always_partial = 1;
+    // an ordered FAST fold of this plan with phase ph's slices / groups / chunk into its rows, or those rows zeroed where it folds nothing
+    auto fold = [&](int ph, bool range, uint32_t r0, uint32_t r1) {
+        a.j_count = pp.len[ph];
+        a.j_chunk = pp.chunk[ph];
+        a.partial_row0 = ph ? pp.slices[0] : 0u;
+        if (!pp.len[ph]) return hipMemsetAsync(rows + (size_t)a.partial_row0 * count * sizeof(float4), 0, (size_t)pp.slices[ph] * count * sizeof(float4), stream);
+        if (nbp::phase_sl(pp)) return nbk::launch_fast_sl_phase(a, pp.base.ib, pp.slices[ph], range, r0, r1, scratch, stream);
+        Plan lds = pp.base;  // the tile or wave form, split as this phase is
+        lds.groups = pp.groups[ph];
+        lds.slices = pp.slices[ph];
+        return launch_planned(lds, a, scratch, nullptr, stream);
+    };
     hipError_t e = hipSuccess;
     if (phase == NB_PHASE_RANGE) {  // records [j_lo, j_lo + len[0]) -> partial rows [0, slices[0])
-        a.j_count = pp.len[0];
         a.j_base = j_lo;
-        a.hole_lo = 0xffffffffu;
-        a.hole_len = 0;
-        a.j_chunk = pp.chunk[0];
-        a.partial_row0 = 0;
-        if (pp.len[0])
-            e = pp.fsl   ? nbk::launch_fast_sl_phase(a, pl.ib, pp.slices[0], true, j_lo, j_lo + pp.len[0], scratch, stream)
-                : pl.waves ? nbk::launch_fast_wave(a, pl.tile, pl.ib, pl.waves, pp.slices[0], stream)
-                           : nbk::launch_fast(a, pl.tile, pl.ib, pp.groups[0], pp.slices[0], stream);
-        else
-            e = hipMemsetAsync(rows, 0, (size_t)pp.slices[0] * count * sizeof(float4), stream);
+        e = fold(0, true, j_lo, j_lo + pp.len[0]);
     } else {  // the set without that range -> rows [slices[0], slices[0] + slices[1]), then every row in order + integrate
-        a.j_count = pp.len[1];
-        a.j_base = 0;
         a.hole_lo = j_lo;
         a.hole_len = pp.len[0];
-        a.j_chunk = pp.chunk[1];
-        a.partial_row0 = pp.slices[0];
-        if (pp.len[1])
-            e = pp.fsl   ? nbk::launch_fast_sl_phase(a, pl.ib, pp.slices[1], false, 0, 0, scratch, stream)
-                : pl.waves ? nbk::launch_fast_wave(a, pl.tile, pl.ib, pl.waves, pp.slices[1], stream)
-                           : nbk::launch_fast(a, pl.tile, pl.ib, pp.groups[1], pp.slices[1], stream);
-        else
-            e = hipMemsetAsync(rows + (size_t)pp.slices[0] * count * sizeof(float4), 0, (size_t)pp.slices[1] * count * sizeof(float4), stream);
+        e = fold(1, false, 0, 0);
         if (e == hipSuccess) e = nbk::launch_integrate_partials(a, pp.slices[0] + pp.slices[1], stream);
     }
     return launch_status(e, "nb: kernel launch failed (step phase): ", err);
@@ -2090,16 +1773,7 @@ NB_EXPORT int nb_diag_plan(const nb_params *params, uint32_t n_total, uint32_t c
     Plan pl;
     int rc = make_plan(p, n_total, count, &pl, &g_tls_error);
     if (rc != NB_OK) return rc;
-    std::string k;
-    if (p.mode == NB_MODE_STRICT)
-        k = pl.bc ? "step_strict_bc_kernel,planes_kernel" : pl.sl ? "step_strict_sl_kernel,planes_kernel" : pl.pc ? "step_strict_pc_kernel" : "step_strict_kernel";
-    else if (pl.pairs)
-        k = nbk::fast_pairs_chunk(pl.n_total, pl.pairs_chunk) >= pl.n_total ? "step_fast_pairs_kernel,planes_kernel,pairs_diag_kernel,pairs_integrate_kernel"
-                                                                             : "step_fast_pairs_kernel,planes_kernel,pairs_diag_kernel,pairs_accumulate_kernel,pairs_finish_kernel";
-    else if (pl.fsl)
-        k = std::string("step_fast_sl_kernel,planes_kernel") + (pl.slices > 1 ? ",integrate_partials_kernel" : "");
-    else
-        k = std::string(pl.waves ? "step_fast_wave_kernel" : "step_fast_kernel") + (pl.slices > 1 ? ",integrate_partials_kernel" : "");
+    const std::string k = nbp::plan_kernels(pl, KernelSizes{});
     if (k.size() + 1 > out_bytes) {
         g_tls_error = "nb_diag_plan: out too small";
         return NB_ERR_INVALID;
@@ -2108,23 +1782,18 @@ NB_EXPORT int nb_diag_plan(const nb_params *params, uint32_t n_total, uint32_t c
     return NB_OK;
 }
 
-NB_EXPORT int nb_diag_enable_env(int on)
+namespace {
+int reread_overrides(bool enable)
 {
     std::lock_guard<std::mutex> lock(g_overrides_mu);
-    g_env_enabled.store(on != 0, std::memory_order_relaxed);
+    g_env_enabled.store(enable, std::memory_order_relaxed);
     const DebugOverrides *old = g_overrides.load(std::memory_order_acquire);
     g_overrides.store(parse_overrides(old ? old->generation + 1u : 1u), std::memory_order_release);
     return NB_OK;
 }
-
-NB_EXPORT int nb_debug_reload_env(void)
-{
-    std::lock_guard<std::mutex> lock(g_overrides_mu);
-    g_env_enabled.store(true, std::memory_order_relaxed);  // asking for a re-read is asking for the knobs
-    const DebugOverrides *old = g_overrides.load(std::memory_order_acquire);
-    g_overrides.store(parse_overrides(old ? old->generation + 1u : 1u), std::memory_order_release);
-    return NB_OK;
-}
+}  // namespace
+NB_EXPORT int nb_diag_enable_env(int on) { return reread_overrides(on != 0); }
+NB_EXPORT int nb_debug_reload_env(void) { return reread_overrides(true); }  // asking for a re-read is asking for the knobs
 
 NB_EXPORT int nb_launch_boids_step(const nb_boids_params *params, uint32_t n_total, uint32_t first, uint32_t count,
                                    const void *pos_in, const void *vel_in, void *pos_out, void *vel_out, void *stream)

@@ -13,11 +13,11 @@ NB_EXPORT int nb_selftest_divide(const nb_params *params, uint64_t pairs, uint64
     Plan pl;
     int rc = make_plan(p, 1024, 1024, &pl, &g_tls_error);
     if (rc != NB_OK) return rc;
-    if (pl.force_ieee && !overrides().strict_force_ieee.on()) {
+    if (pl.guard.force_ieee && !overrides().strict_force_ieee.on()) {
         g_tls_error = "nb_selftest_divide: these parameters have no guarded range (STRICT always divides with '/')";
         return NB_ERR_UNSUPPORTED;
     }
-    if (pl.force_ieee) {  // forced by the environment only: recompute the range without the override is not possible here
+    if (pl.guard.force_ieee) {  // forced by the environment only: recompute the range without the override is not possible here
         g_tls_error = "nb_selftest_divide: unset NB_STRICT_FORCE_IEEE";
         return NB_ERR_UNSUPPORTED;
     }
@@ -25,8 +25,8 @@ NB_EXPORT int nb_selftest_divide(const nb_params *params, uint64_t pairs, uint64
     if (rc != NB_OK) return rc;
     // what the kernels can meet inside the guard (see make_plan):
     //   d = |dp|^2 + bias  in [2^c, 2^max(2b+4, c+2)),   n = dx*G, nonzero dx in [2^(a-23), 2^(b+1)]  ->  |n| in [2^(a-23+g), 2^(b+g+2))
-    const int d_lo = pl.guard_c, d_hi = std::max(2 * pl.guard_b + 4, pl.guard_c + 2) - 1;
-    const int n_lo = pl.guard_a - 23 + pl.guard_g, n_hi = pl.guard_b + pl.guard_g + 1;
+    const int d_lo = pl.guard.c, d_hi = std::max(2 * pl.guard.b + 4, pl.guard.c + 2) - 1;
+    const int n_lo = pl.guard.a - 23 + pl.guard.g, n_hi = pl.guard.b + pl.guard.g + 1;
     unsigned long long *d_bad = nullptr;
     float *d_pair = nullptr;
     hipError_t e = hipMalloc((void **)&d_bad, sizeof(unsigned long long));
@@ -254,15 +254,19 @@ namespace {
 // The clock a kernel ran at, from the (s_memtime, s_memrealtime) stamps its workgroups' first waves left at entry and exit
 // (4 words per workgroup): median over workgroups of d(s_memtime) / d(s_memrealtime) x 100 MHz -- s_memrealtime ticks at a
 // constant 100 MHz, s_memtime at the shader clock (MI355X_MICROARCH.md, "DVFS give-back" (6)).  Also the median lifetime of
-// those waves in shader cycles.  Workgroups too short to time (< 20 us) are left out.
+// those waves in shader cycles.  Workgroups too short to time well (< 20 us: 2 000 ticks) are left out where any ran longer; a step
+// so small that none did (a few thousand bodies) is timed from every workgroup the counter saw run, at that coarser resolution.
 bool clock_from_stamps(const std::vector<unsigned long long> &st, double *mhz, double *cycles)
 {
     std::vector<double> f, c;
-    for (size_t i = 0; i + 3 < st.size(); i += 4) {
-        const unsigned long long t0 = st[i], r0 = st[i + 1], t1 = st[i + 2], r1 = st[i + 3];
-        if (r1 <= r0 + 2000ull || t1 <= t0) continue;
-        f.push_back((double)(t1 - t0) / (double)(r1 - r0) * 100.0);
-        c.push_back((double)(t1 - t0));
+    for (unsigned long long min_ticks : {2000ull, 0ull}) {
+        for (size_t i = 0; i + 3 < st.size(); i += 4) {
+            const unsigned long long t0 = st[i], r0 = st[i + 1], t1 = st[i + 2], r1 = st[i + 3];
+            if (r1 <= r0 + min_ticks || t1 <= t0) continue;
+            f.push_back((double)(t1 - t0) / (double)(r1 - r0) * 100.0);
+            c.push_back((double)(t1 - t0));
+        }
+        if (!f.empty()) break;
     }
     if (f.empty()) return false;
     std::sort(f.begin(), f.end());
@@ -340,7 +344,7 @@ NB_EXPORT int nb_diag_step_clock(const nb_params *params, uint32_t n, double sec
     Plan pl;
     int rc = make_plan(p, n, n, &pl, &g_tls_error);
     if (rc != NB_OK) return rc;
-    if ((p.mode == NB_MODE_STRICT && (pl.bc || pl.pc || pl.lanes != 1)) || (p.mode == NB_MODE_FAST && !pl.waves && !pl.pairs)) {
+    if (!pl.stamped) {
         g_tls_error = "nb_diag_step_clock: only the whole-set kernels carry stamps (STRICT one lane per body, FAST wave and pairs forms)";
         return NB_ERR_UNSUPPORTED;
     }
@@ -350,12 +354,7 @@ NB_EXPORT int nb_diag_step_clock(const nb_params *params, uint32_t n, double sec
     std::vector<float> pos((size_t)n * 3), vel((size_t)n * 3);
     nb_init_state(1234, n, pos.data(), vel.data());
     rc = nb_upload(c, pos.data(), vel.data());
-    const uint32_t bodies = p.mode == NB_MODE_STRICT ? (pl.sl == 3u ? 64u : 256u) : 64u * pl.ib;
-    size_t groups = (size_t)((n + bodies - 1u) / bodies) * (p.mode == NB_MODE_FAST ? pl.slices : 1u);
-    if (p.mode == NB_MODE_FAST && pl.pairs) {  // one workgroup per superblock pair
-        const size_t ns = nbk::fast_pairs_rows(n, pl.pairs, pl.pairs_np);
-        groups = std::max<size_t>(1, ns * (ns - 1) / 2);
-    }
+    const size_t groups = nbp::stamp_groups(pl, n, KernelSizes{});
     unsigned long long *stamps = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipSuccess;
@@ -378,20 +377,9 @@ NB_EXPORT int nb_diag_step_clock(const nb_params *params, uint32_t n, double sec
             // the stamped step: the same launch with StepArgs::stamps set
             if (rc == NB_OK) e = hipEventRecord(e0, c->stream);
             if (rc == NB_OK && e == hipSuccess) {
-                nbk::StepArgs a = step_args(p, pl, n, 0, n, c->pos[c->cur], c->pos[c->cur ^ 1], c->vel);
-                a.partial = (float4 *)c->scratch;
-                a.j_count = n;
-                a.lo_bits = pl.lo_bits;
-                a.hi_bits = pl.hi_bits;
-                a.j_chunk = pl.j_chunk;
-                a.no_packed = pl.no_packed;
-                a.hole_lo = 0xffffffffu;
+                nbk::StepArgs a = step_args(p, pl, n, 0, n, c->pos[c->cur], c->pos[c->cur ^ 1], c->vel, c->scratch);
                 a.stamps = stamps;
-                e = p.mode == NB_MODE_STRICT ? (pl.sl ? nbk::launch_strict_sl(a, pl.sl - 1u, c->scratch, c->stream)
-                                                      : nbk::launch_strict(a, pl.tile, pl.unroll, pl.lanes, c->stream))
-                                             : pl.pairs ? nbk::launch_fast_pairs(a, pl.pairs, pl.pairs_np, pl.pairs_chunk, c->scratch, c->stream)
-                                             : pl.fsl ? nbk::launch_fast_sl(a, pl.ib, pl.slices, c->scratch, c->stream)
-                                                      : nbk::launch_fast_wave(a, pl.tile, pl.ib, pl.waves, pl.slices, c->stream);
+                e = launch_planned(pl, a, c->scratch, nullptr, c->stream);  // (no stamped form reports through the status word)
             }
             if (rc == NB_OK && e == hipSuccess) e = hipEventRecord(e1, c->stream);
             if (rc == NB_OK && e == hipSuccess) e = hipEventSynchronize(e1);

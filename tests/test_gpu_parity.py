@@ -1671,6 +1671,35 @@ def test_step_clock_of_the_headline_kernels(nb):
         assert cyc.value / (mhz.value * 1e3) <= ms.value * 1.02
 
 
+@pytest.mark.parametrize("mode_fast,tile,n,kernel", [(True, 0, 1024, "step_fast_wave_kernel"), (True, 0, 4096, "step_fast_sl_kernel"),
+                                                    (True, 0, 32768, "step_fast_pairs_kernel"), (False, 256, 57408, "step_strict_kernel"),
+                                                    (False, 0, 1536, "step_strict_bc_kernel")])
+def test_step_clock_of_the_other_stamped_forms(nb, mode_fast, tile, n, kernel):
+    """nb_diag_step_clock on the smallest shape that reaches each stamped form the headline test does not: its stamped launch is the
+    plan's own dispatch with the stamps set (nb_plan.h: visit_launch).  No clock or time bound at these sizes: the part does not ramp
+    on microsecond kernels.  The block chain (n = 1 536, STRICT) carries no stamps and is still refused.
+
+    No workgroup of the two smallest steps runs for the 20 us (2 000 ticks of the 100 MHz counter) that clock_from_stamps asks of a
+    workgroup where it has the choice; those steps are timed from every workgroup the counter saw run.  Before that rule the call
+    answered NB_ERR_STATE, "no workgroup ran long enough to time", for FAST sets of 1 024, 4 096 and 8 192 bodies, with the planner in
+    nb_api.hip as with it in nb_plan.h; the shapes that were timed then give what they gave (measured on one MI355X, before / after
+    the planner moved: 32 768 FAST, pairs: 2 330.4 / 2 329.8 MHz, 161 784 / 161 920 cycles, 0.150 ms; 57 408 STRICT tiled: 2 383.1 /
+    2 383.2 MHz, 4 185 744 / 4 185 776 cycles, 1.774 ms)."""
+    lib = nb.load()
+    p = nb.default_params(mode=nb.NB_MODE_FAST if mode_fast else nb.NB_MODE_STRICT, tile=tile)
+    assert nb._lib.planned_kernels(p, n, n)[0] == kernel
+    mhz, cyc, ms = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    rc = lib.nb_diag_step_clock(ctypes.byref(p), n, 0.05, ctypes.byref(mhz), ctypes.byref(cyc), ctypes.byref(ms))
+    if kernel == "step_strict_bc_kernel":
+        assert rc == nb._lib.NB_ERR_UNSUPPORTED
+        assert nb._lib.last_error() == ("nb_diag_step_clock: only the whole-set kernels carry stamps (STRICT one lane per body, FAST wave and pairs "
+                                        "forms)")
+        return
+    assert rc == 0, nb._lib.last_error()
+    for v in (mhz.value, cyc.value, ms.value):
+        assert np.isfinite(v) and v > 0, (kernel, mhz.value, cyc.value, ms.value)
+
+
 def test_perf_floor_of_the_whole_set_kernels(nb, capsys):
     """What the headline rests on, as a TIME (the ISA side is tests/test_isa_guard.py): N = 131 072, each
     controller stepped for >= 100 ms first (the part ramps its clock after an idle gap), then 40 steps against the wall clock
