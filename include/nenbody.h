@@ -271,6 +271,44 @@ int nb_eyes_located(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up
  * stay together at or below 64 MiB -- 2 047 at width 1024.  1 <= width <= NB_EYES_MAX_WIDTH; cp16 as L6 asks. */
 int nb_step_nbody_located(nb_ctx *ctx, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width, uint32_t batch);
 
+/* ---- scene batches ------------------------------------------------------------------------------------
+ * A scene batch is `scenes` >= 1 independent scenes of n bodies each, 1 <= n <= NB_SCENES_MAX_BODIES; body i of scene s is record
+ * s*n + i of the 16-byte position and velocity records (and of the 16-float model matrices).  scenes*n <= 2^27, more is
+ * NB_ERR_UNSUPPORTED.  One launch steps every scene k times, one workgroup per scene, the scene's state on chip between the steps:
+ *   B1  gravity: scene s gets exactly the records nb_step(ctx, k) gives a context of n bodies created with the same nb_params and
+ *       uploaded with scene s's records -- every bit.  STRICT only: NB_MODE_FAST is NB_ERR_UNSUPPORTED.  params.tile is validated
+ *       and otherwise unused.
+ *   B2  boids: the same against nb_step_boids(ctx, k, params) (the radius thresholds are those of a set of n bodies)
+ *   B3  no scene's result depends on another scene's records, on `scenes`, or on whether k steps come as one launch or as k
+ *   B4  the stateless entries update pos and vel in place */
+#define NB_SCENES_MAX_BODIES 2048u
+
+/* k steps of a batch on caller-owned device memory, in place, one kernel on `stream`: pos, vel: scenes*n records each, 16-byte
+ * aligned, not overlapping.  params == NULL -> defaults.  k = 0 is a checked no-op. */
+int nb_scenes_nbody_step_launch(const nb_params *params, uint32_t scenes, uint32_t n, uint32_t k, void *pos, void *vel, void *stream);
+int nb_scenes_boids_step_launch(const nb_boids_params *params, uint32_t scenes, uint32_t n, uint32_t k, void *pos, void *vel, void *stream);
+
+typedef struct nb_scenes nb_scenes; /* opaque; owns a batch's device buffers and its stream */
+
+/* params == NULL -> defaults; checked as B1 asks.  Errors from a NULL context or from nb_scenes_create are read with
+ * nb_scenes_last_error(NULL), a context's own with nb_scenes_last_error(ctx). */
+int nb_scenes_create(uint32_t scenes, uint32_t n, const nb_params *params, nb_scenes **out);
+void nb_scenes_destroy(nb_scenes *ctx);
+/* pos_xyz, vel_xyz: stride-3 host arrays of 3*scenes*n floats, scene after scene, as nb_upload takes one set's */
+int nb_scenes_upload(nb_scenes *ctx, const float *pos_xyz, const float *vel_xyz);
+/* k steps of every scene, asynchronous on the context's stream; the two may be mixed freely.  NB_ERR_STATE before an upload. */
+int nb_scenes_step(nb_scenes *ctx, uint32_t k);
+int nb_scenes_step_boids(nb_scenes *ctx, uint32_t k, const nb_boids_params *params);
+/* any output may be NULL, but not all three; inst_16: 16*scenes*n floats, the model matrices of every body (nb_download's) */
+int nb_scenes_download(nb_scenes *ctx, float *pos_xyz, float *vel_xyz, float *inst_16);
+/* the batch's device records, as nb_device_state hands out a set's (valid until the next step or upload; work on another stream
+ * orders itself behind nb_scenes_sync): scene s starts s*n records (s*n matrices) behind each pointer, so nb_launch_cameras /
+ * nb_launch_eyes run on one scene with n_total = n and offset pointers.  Any of the three may be NULL. */
+int nb_scenes_device_state(nb_scenes *ctx, const void **pos_rec, const void **vel_rec, const void **inst_16);
+int nb_scenes_sync(nb_scenes *ctx);
+uint64_t nb_scenes_steps(const nb_scenes *ctx); /* steps applied since the last upload */
+const char *nb_scenes_last_error(const nb_scenes *ctx);
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which

@@ -325,6 +325,76 @@ private:
     nb_ctx *ctx_ = nullptr;
 };
 
+// B independent scenes of n <= NB_SCENES_MAX_BODIES bodies, device-resident (nb_scenes_* of nenbody.h): one launch steps every scene
+// k times, one workgroup per scene, and every scene gets the bits a Scene of its n bodies gets.  Body i of scene s is element
+// s * n + i of every array.  Steps are asynchronous on the batch's stream; download() waits.
+class SceneBatch {
+public:
+    // scene s starts from the reference's initial distributions drawn with seed + s
+    SceneBatch(uint32_t scenes, uint32_t n, uint64_t seed, const nb_params &params) : scenes_(scenes), n_(n)
+    {
+        check_abi();
+        std::vector<Vec3> pos((size_t)scenes * n + 1), vel((size_t)scenes * n + 1);
+        for (uint32_t s = 0; s < scenes; ++s)
+            check(nb_init_state(seed + s, n, pos[(size_t)s * n].data(), vel[(size_t)s * n].data()), nullptr);
+        create(pos, vel, params);
+    }
+    SceneBatch(uint32_t scenes, uint32_t n, const std::vector<Vec3> &pos, const std::vector<Vec3> &vel, const nb_params &params)
+        : scenes_(scenes), n_(n)
+    {
+        check_abi();
+        if (pos.size() != (size_t)scenes * n || vel.size() != pos.size() || pos.empty())
+            throw std::invalid_argument("positions and velocities must hold scenes * n bodies");
+        create(pos, vel, params);
+    }
+    SceneBatch(const SceneBatch &) = delete;
+    SceneBatch &operator=(const SceneBatch &) = delete;
+    ~SceneBatch() { nb_scenes_destroy(ctx_); }
+
+    uint32_t scenes() const { return scenes_; }
+    uint32_t n() const { return n_; }
+    void step(uint32_t k = 1) { check_sc(nb_scenes_step(ctx_, k)); }
+    void step_boids(uint32_t k = 1, const nb_boids_params *params = nullptr) { check_sc(nb_scenes_step_boids(ctx_, k, params)); }
+    void sync() { check_sc(nb_scenes_sync(ctx_)); }
+    uint64_t steps_done() const { return nb_scenes_steps(ctx_); }
+    void download(std::vector<Vec3> &positions, std::vector<Vec3> &velocities, std::vector<Mat4> &instances)
+    {
+        const size_t total = (size_t)scenes_ * n_;
+        positions.resize(total), velocities.resize(total), instances.resize(total);
+        check_sc(nb_scenes_download(ctx_, positions[0].data(), velocities[0].data(), instances[0][0].data()));
+    }
+    // the batch's device records (nb_scenes_device_state): scene s starts s * n records behind each pointer
+    struct DeviceState {
+        const void *pos, *vel, *inst;
+    };
+    DeviceState device_state()
+    {
+        DeviceState d{};
+        check_sc(nb_scenes_device_state(ctx_, &d.pos, &d.vel, &d.inst));
+        return d;
+    }
+
+private:
+    void check_sc(int rc)
+    {
+        if (rc != NB_OK) throw Error(rc, nb_scenes_last_error(ctx_));
+    }
+    void create(const std::vector<Vec3> &pos, const std::vector<Vec3> &vel, const nb_params &params)
+    {
+        const int rc = nb_scenes_create(scenes_, n_, &params, &ctx_);
+        if (rc != NB_OK) throw Error(rc, nb_scenes_last_error(nullptr));
+        const int up = nb_scenes_upload(ctx_, pos[0].data(), vel[0].data());
+        if (up != NB_OK) {
+            const std::string msg = nb_scenes_last_error(ctx_);
+            nb_scenes_destroy(ctx_);
+            ctx_ = nullptr;
+            throw Error(up, msg);
+        }
+    }
+    nb_scenes *ctx_ = nullptr;
+    uint32_t scenes_ = 0, n_ = 0;
+};
+
 // One rank's share of a scene on a multi-GPU host (one process or thread per GPU): nb_shard_* of nenbody.h.  Every rank
 // passes the same full state; the rank keeps its index range and a replica of all positions, and each step ends with
 // one exchange (RCCL when constructed with a comm id from Shard::comm_id(), else the host's nb_gather_fn).

@@ -8,7 +8,7 @@
 //! NOT COMPILED in the build environment (no cargo/rustc there): a mechanical binding of the C ABI.
 use cgmath::{Point3, Vector3};
 use std::ffi::CStr;
-use std::os::raw::{c_char, c_int};
+use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -99,7 +99,28 @@ extern "C" {
     fn nb_frame_sample_offsets(out16: *mut f32) -> c_int;
     fn nb_frame_msaa(ctx: *mut NbCtx, cam16: *const f32, width: u32, height: u32, flags: u32, ids8: *mut u32, depth8: *mut f32, rgba: *mut f32, bgra8: *mut u32) -> c_int;
     fn nb_frame_msaa_scratch_bytes(width: u32, height: u32) -> usize;
+    // scene batches (include/nenbody.h, "scene batches"): B scenes of n <= NB_SCENES_MAX_BODIES bodies, k steps per launch
+    fn nb_scenes_create(scenes: u32, n: u32, params: *const NbParams, out: *mut *mut NbScenes) -> c_int;
+    fn nb_scenes_destroy(ctx: *mut NbScenes);
+    fn nb_scenes_upload(ctx: *mut NbScenes, pos_xyz: *const f32, vel_xyz: *const f32) -> c_int;
+    fn nb_scenes_step(ctx: *mut NbScenes, k: u32) -> c_int;
+    fn nb_scenes_step_boids(ctx: *mut NbScenes, k: u32, params: *const NbBoidsParams) -> c_int; // null = reference constants
+    fn nb_scenes_download(ctx: *mut NbScenes, pos_xyz: *mut f32, vel_xyz: *mut f32, inst_16: *mut f32) -> c_int;
+    fn nb_scenes_device_state(ctx: *mut NbScenes, pos_rec: *mut *const c_void, vel_rec: *mut *const c_void, inst_16: *mut *const c_void) -> c_int;
+    fn nb_scenes_sync(ctx: *mut NbScenes) -> c_int;
+    fn nb_scenes_steps(ctx: *const NbScenes) -> u64;
+    fn nb_scenes_last_error(ctx: *const NbScenes) -> *const c_char;
+    // the same on caller-owned device memory, in place
+    fn nb_scenes_nbody_step_launch(params: *const NbParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_boids_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
 }
+
+#[repr(C)]
+pub struct NbScenes {
+    _private: [u8; 0],
+}
+
+pub const NB_SCENES_MAX_BODIES: u32 = 2048;
 
 pub const NB_FRAME_MAX_DIM: u32 = 4096;
 pub const NB_FRAME_MSAA_MAX_DIM: u32 = 2048;
@@ -697,4 +718,94 @@ pub fn update_instance_random_seeded(
 /// Seed of `update_instance_random`'s stream; restarts its call counter.
 pub fn update_random_seed(seed: u64) {
     unsafe { nb_update_random_seed(seed) }
+}
+
+fn check_scenes(rc: c_int, ctx: *const NbScenes) -> Result<(), SceneError> {
+    if rc == 0 {
+        return Ok(());
+    }
+    let msg = unsafe { CStr::from_ptr(nb_scenes_last_error(ctx)) }.to_string_lossy().into_owned();
+    Err(SceneError(rc, msg))
+}
+
+/// B independent scenes of n <= `NB_SCENES_MAX_BODIES` bodies, device-resident; one launch steps every scene k times, one
+/// workgroup per scene, and every scene gets the bits a `Scene` of its n bodies gets.  Body i of scene s is element `s * n + i`.
+pub struct SceneBatch {
+    ctx: *mut NbScenes,
+    pub scenes: usize,
+    pub n: usize,
+}
+
+unsafe impl Send for SceneBatch {}
+
+impl SceneBatch {
+    /// scene s starts from the reference's initial distributions drawn with `seed + s`
+    pub fn new(scenes: usize, n: usize, seed: u64, params: NbParams) -> Result<SceneBatch, SceneError> {
+        check_abi();
+        let mut positions = vec![Point3::new(0.0f32, 0.0, 0.0); scenes * n];
+        let mut velocities = vec![Vector3::new(0.0f32, 0.0, 0.0); scenes * n];
+        for s in 0..scenes {
+            check(
+                unsafe {
+                    nb_init_state(seed + s as u64, n as u32, positions[s * n..].as_mut_ptr() as *mut f32, velocities[s * n..].as_mut_ptr() as *mut f32)
+                },
+                std::ptr::null(),
+            )?;
+        }
+        SceneBatch::from_state(scenes, n, &positions, &velocities, params)
+    }
+
+    pub fn from_state(scenes: usize, n: usize, positions: &[Point3<f32>], velocities: &[Vector3<f32>], params: NbParams) -> Result<SceneBatch, SceneError> {
+        check_abi();
+        assert!(positions.len() == scenes * n && velocities.len() == scenes * n, "positions and velocities must hold scenes * n bodies");
+        let mut ctx: *mut NbScenes = std::ptr::null_mut();
+        check_scenes(unsafe { nb_scenes_create(scenes as u32, n as u32, &params, &mut ctx) }, std::ptr::null())?;
+        let batch = SceneBatch { ctx, scenes, n };
+        check_scenes(unsafe { nb_scenes_upload(batch.ctx, positions.as_ptr() as *const f32, velocities.as_ptr() as *const f32) }, batch.ctx)?;
+        Ok(batch)
+    }
+
+    /// k `update_instance_nbody` of every scene (STRICT), asynchronous
+    pub fn step(&mut self, k: u32) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_step(self.ctx, k) }, self.ctx)
+    }
+
+    /// k `update_instance_boids` of every scene with the reference's constants, asynchronous
+    pub fn step_boids(&mut self, k: u32) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_step_boids(self.ctx, k, std::ptr::null()) }, self.ctx)
+    }
+
+    /// positions, velocities and model matrices of every body, scene after scene
+    pub fn download(&mut self) -> Result<(Vec<Point3<f32>>, Vec<Vector3<f32>>, Vec<[[f32; 4]; 4]>), SceneError> {
+        let total = self.scenes * self.n;
+        let mut p = vec![Point3::new(0.0f32, 0.0, 0.0); total];
+        let mut v = vec![Vector3::new(0.0f32, 0.0, 0.0); total];
+        let mut m = vec![[[0.0f32; 4]; 4]; total];
+        check_scenes(
+            unsafe { nb_scenes_download(self.ctx, p.as_mut_ptr() as *mut f32, v.as_mut_ptr() as *mut f32, m.as_mut_ptr() as *mut f32) },
+            self.ctx,
+        )?;
+        Ok((p, v, m))
+    }
+
+    /// device addresses of the position records, velocity records and model matrices (scene s: `s * n` records behind each)
+    pub fn device_state(&mut self) -> Result<(*const c_void, *const c_void, *const c_void), SceneError> {
+        let (mut p, mut v, mut m) = (std::ptr::null(), std::ptr::null(), std::ptr::null());
+        check_scenes(unsafe { nb_scenes_device_state(self.ctx, &mut p, &mut v, &mut m) }, self.ctx)?;
+        Ok((p, v, m))
+    }
+
+    pub fn sync(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_sync(self.ctx) }, self.ctx)
+    }
+
+    pub fn steps_done(&self) -> u64 {
+        unsafe { nb_scenes_steps(self.ctx) }
+    }
+}
+
+impl Drop for SceneBatch {
+    fn drop(&mut self) {
+        unsafe { nb_scenes_destroy(self.ctx) };
+    }
 }

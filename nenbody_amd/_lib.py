@@ -31,6 +31,7 @@ NB_PHASE_REST = 1
 # phases of the pairs form on shards (nb_launch_ring_fold_phase)
 NB_RING_OWN, NB_RING_REST, NB_RING_SUMS, NB_RING_OWN_READY = 1, 2, 3, 4
 # every entity's eye view (nb_eyes / nb_launch_eyes)
+NB_SCENES_MAX_BODIES = 2048
 NB_EYES_NONE = 0xFFFFFFFF
 NB_EYES_SEE_SELF = 1
 NB_EYES_MAX_WIDTH = 4096
@@ -134,6 +135,18 @@ PROTOTYPES = {
     "nb_nbody_located_step_launch": (
         c_int, [POINTER(NbParams), c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
                 c_void_p]),
+    "nb_scenes_nbody_step_launch": (c_int, [POINTER(NbParams), c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_boids_step_launch": (c_int, [POINTER(NbBoidsParams), c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_create": (c_int, [c_uint32, c_uint32, POINTER(NbParams), POINTER(c_void_p)]),
+    "nb_scenes_destroy": (None, [c_void_p]),
+    "nb_scenes_upload": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_step": (c_int, [c_void_p, c_uint32]),
+    "nb_scenes_step_boids": (c_int, [c_void_p, c_uint32, POINTER(NbBoidsParams)]),
+    "nb_scenes_download": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_device_state": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
+    "nb_scenes_sync": (c_int, [c_void_p]),
+    "nb_scenes_steps": (c_uint64, [c_void_p]),
+    "nb_scenes_last_error": (c_char_p, [c_void_p]),
     "nb_srgb_decode_table": (c_int, [c_void_p]),
     "nb_srgb_encode": (c_int, [c_void_p, c_size_t, c_void_p]),
     "nb_camera_at": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -25,6 +25,7 @@
 #include "nb_frame.h"
 #include "nb_seen.h"
 #include "nb_located.h"
+#include "nb_scenes.h"
 #define NB_SRGB_TABLE static const
 #define NB_SRGB_WANT_DECODE
 #include "nb_srgb_tables.h"
@@ -2040,5 +2041,6 @@ NB_EXPORT int nb_launch_unpack(uint32_t count, const void *rec4, void *xyz, void
 }
 
 #include "nb_vision_api.inc"   // the seen and located sets and the steps over them (DESIGN.md sections 12 and 13)
+#include "nb_scenes_api.inc"   // scene batches: B small scenes, k steps, one launch
 #include "nb_peers.inc"
 #include "nb_shard.inc"

@@ -386,8 +386,9 @@ __device__ __forceinline__ BoidsTileHead boids_tile_head(uint32_t t, uint32_t n,
             boids_fold_tile<false, true, true, true, PACKED, ROLE>(s, tp, tv, nj, j0, gn, pn, vn, (a).r1, (a).t2, (a).t3, mkv);   \
     } while (0)
 
-// main.rs:506-521 for one body: means, blend, speed clamp, position update
-__device__ __forceinline__ void boids_finish(const BoidsArgs &a, const BoidsAcc &s, uint32_t l, const float4 pn)
+// main.rs:506-521 for one body: means, blend, speed clamp, position update -- the arithmetic, stated once; boids_finish stores its
+// records, the scene-batch kernel (nb_scenes.inc) keeps them on chip
+__device__ __forceinline__ void boids_finish_records(const BoidsArgs &a, const BoidsAcc &s, const float4 pn, float4 &p_new, float4 &v_new)
 {
     float cx = s.cx, cy = s.cy, cz = s.cz, mx = s.mx, my = s.my, mz = s.mz;
     if (s.cnt > 0.f) {  // main.rs:506-508  (count as f32)
@@ -417,8 +418,15 @@ __device__ __forceinline__ void boids_finish(const BoidsArgs &a, const BoidsAcc 
     }
     // main.rs:521  pos = vel * dt + pos
     const float sx = vx * a.dt, sy = vy * a.dt, sz = vz * a.dt;
-    a.vel_out[a.first + l] = make_float4(vx, vy, vz, 0.f);
-    a.pos_out[a.first + l] = make_float4(sx + pn.x, sy + pn.y, sz + pn.z, 0.f);
+    v_new = make_float4(vx, vy, vz, 0.f);
+    p_new = make_float4(sx + pn.x, sy + pn.y, sz + pn.z, 0.f);
+}
+__device__ __forceinline__ void boids_finish(const BoidsArgs &a, const BoidsAcc &s, uint32_t l, const float4 pn)
+{
+    float4 p, v;
+    boids_finish_records(a, s, pn, p, v);
+    a.vel_out[a.first + l] = v;
+    a.pos_out[a.first + l] = p;
 }
 
 // Split form, first launch: the step's global flags (a non-finite record, a velocity component above the rule-3 bound -- OR-ed

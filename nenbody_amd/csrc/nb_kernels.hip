@@ -45,6 +45,7 @@
 //   nb_frame_msaa.inc    the scene camera's frame through 8 samples per pixel, resolved (SLP-off unit; launcher in nb_frame.h)
 //   nb_seen.inc          the seen set of every eye row; the boids step over what each body sees (SLP-off unit; launchers in nb_seen.h)
 //   nb_located.inc       where each eye sees the members of its seen set; the gravity step over those relative positions (SLP-off unit; launchers in nb_located.h)
+//   nb_scenes.inc        scene batches: B scenes of up to 2 048 bodies, k steps, one workgroup per scene (SLP-off unit; launchers in nb_scenes.h)
 //   nb_launch.inc        host-side launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,6 +60,7 @@
 #include "nb_frame.h"
 #include "nb_seen.h"
 #include "nb_located.h"
+#include "nb_scenes.h"
 #endif
 
 namespace nbk {
@@ -84,6 +86,7 @@ static_assert(kMsaaOffsets16 == sample_nibbles(kEyeSampleX16) && kFrameMsaaOffse
 #include "nb_frame_msaa.inc"  // the frame through 8 samples per pixel: likewise; uses nb_frame.inc's edge and clear
 #include "nb_seen.inc"        // the seen set of every eye row and the boids step over it: likewise; uses nb_boids.inc's accumulators and epilogue
 #include "nb_located.inc"     // the located seen sets and the gravity step over them: likewise; uses nb_seen.inc's constants and nb_nbody_strict.inc's integrate
+#include "nb_scenes.inc"      // scene batches, one workgroup per scene: likewise; uses nb_nbody_strict.inc's folds and nb_boids.inc's pair and epilogue
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

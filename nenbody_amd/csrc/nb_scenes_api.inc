@@ -1,0 +1,312 @@
+// nb_scenes_api.inc -- the C ABI of DESIGN.md section 14: scene batches.  The two stateless entries (nb_scenes_nbody_step_launch,
+// nb_scenes_boids_step_launch) step caller-owned records in place; the context nb_scenes owns a batch and a stream.  Included by
+// nb_api.hip behind nb_vision_api.inc.  Every check runs before anything touches the device and has its own message naming the entry.
+
+static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
+constexpr uint64_t kScenesMaxRecords = 1ull << 27;   // scenes * n
+
+// the shape of a batch: scenes >= 1, 1 <= n <= NB_SCENES_MAX_BODIES, scenes * n <= 2^27
+static int scenes_shape_check(const char *fn, uint32_t scenes, uint32_t n, std::string *err)
+{
+    if (scenes == 0) {
+        *err = std::string(fn) + ": scenes must be at least 1";
+        return NB_ERR_INVALID;
+    }
+    if (n == 0 || n > NB_SCENES_MAX_BODIES) {
+        *err = std::string(fn) + ": n must be 1 .. NB_SCENES_MAX_BODIES (2048)";
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)scenes * n > kScenesMaxRecords) {
+        *err = std::string(fn) + ": scenes * n must be at most 2^27";
+        return NB_ERR_UNSUPPORTED;
+    }
+    return NB_OK;
+}
+
+// gravity: STRICT only; the tile is validated as elsewhere and otherwise unused
+static int scenes_params_check(const char *fn, const nb_params &p, std::string *err)
+{
+    if (p.mode != NB_MODE_STRICT && p.mode != NB_MODE_FAST) {
+        *err = std::string(fn) + ": params.mode must be NB_MODE_STRICT or NB_MODE_FAST";
+        return NB_ERR_INVALID;
+    }
+    if (p.mode != NB_MODE_STRICT) {
+        *err = std::string(fn) + ": a scene batch steps STRICT only (params.mode is NB_MODE_FAST)";
+        return NB_ERR_UNSUPPORTED;
+    }
+    if (p.tile != 0 && !valid_tile(p.tile)) {
+        *err = std::string(fn) + ": params.tile must be 0, 256, 512 or 1024";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+static int scenes_boids_params_check(const char *fn, const nb_boids_params &p, std::string *err)
+{
+    if (p.tile != 0 && !valid_tile(p.tile)) {
+        *err = std::string(fn) + ": params.tile must be 0, 256, 512 or 1024";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// the records of a stateless entry: there, 16-byte aligned, not overlapping
+static int scenes_records_check(const char *fn, uint32_t scenes, uint32_t n, const void *pos, const void *vel, std::string *err)
+{
+    if (((uintptr_t)pos | (uintptr_t)vel) & 15u) {
+        *err = std::string(fn) + ": pos and vel must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t bytes = (size_t)scenes * n * sizeof(float4);
+    if (ranges_overlap(pos, bytes, vel, bytes)) {
+        *err = std::string(fn) + ": pos and vel must not overlap";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// the launch arguments of k gravity steps: the guard and the forced paths as the planner gives them to a set of n bodies
+static int scenes_nbody_args(const nb_params &p, uint32_t scenes, uint32_t n, uint32_t k, void *pos, void *vel, nbk::ScenesNbodyArgs *out,
+                             std::string *err)
+{
+    Plan plan;
+    const int rc = make_plan(p, n, n, &plan, err);
+    if (rc != NB_OK) return rc;
+    const nbk::StepArgs sa = step_args(p, plan, n, 0, n, pos, pos, vel);
+    nbk::ScenesNbodyArgs a{};
+    a.pos = (float4 *)pos, a.vel = (float4 *)vel;
+    a.scenes = scenes, a.n = n, a.k = k;
+    a.dt = sa.dt, a.G = sa.G, a.bias = sa.bias;
+    a.lo_bits = sa.lo_bits, a.hi_bits = sa.hi_bits, a.force_ieee = sa.force_ieee, a.force_3d = sa.force_3d;
+    *out = a;
+    return NB_OK;
+}
+
+// ---- the stateless entries ----------------------------------------------------------------------------------------------------------------
+NB_EXPORT int nb_scenes_nbody_step_launch(const nb_params *params, uint32_t scenes, uint32_t n, uint32_t k, void *pos, void *vel, void *stream)
+{
+    static const char fn[] = "nb_scenes_nbody_step_launch";
+    if (!pos || !vel) {
+        g_tls_error = std::string(fn) + ": pos and vel must be non-null";
+        return NB_ERR_INVALID;
+    }
+    const nb_params p = params_or_default(params);
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_params_check(fn, p, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_records_check(fn, scenes, n, pos, vel, &g_tls_error);
+    nbk::ScenesNbodyArgs a;
+    if (rc == NB_OK) rc = scenes_nbody_args(p, scenes, n, k, pos, vel, &a, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (k == 0) return NB_OK;
+    rc = device_for_launch(pos, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    return launch_status(nbk::launch_scenes_nbody(a, (hipStream_t)stream), "nb: gravity kernel launch failed (scene batch): ", &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_boids_step_launch(const nb_boids_params *params, uint32_t scenes, uint32_t n, uint32_t k, void *pos, void *vel,
+                                          void *stream)
+{
+    static const char fn[] = "nb_scenes_boids_step_launch";
+    if (!pos || !vel) {
+        g_tls_error = std::string(fn) + ": pos and vel must be non-null";
+        return NB_ERR_INVALID;
+    }
+    const nb_boids_params p = boids_params_or_default(params);
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_boids_params_check(fn, p, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_records_check(fn, scenes, n, pos, vel, &g_tls_error);
+    nbk::BoidsArgs c;
+    uint32_t tile = 0;
+    if (rc == NB_OK) rc = make_boids_args(p, n, 0, n, &c, &tile, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (k == 0) return NB_OK;
+    rc = device_for_launch(pos, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    return launch_status(nbk::launch_scenes_boids(c, (float4 *)pos, (float4 *)vel, scenes, k, (hipStream_t)stream),
+                         "nb: boids kernel launch failed (scene batch): ", &g_tls_error);
+}
+
+// ---- the context --------------------------------------------------------------------------------------------------------------------------
+struct nb_scenes {
+    uint32_t scenes = 0, n = 0;
+    nb_params p{};
+    hipStream_t stream = nullptr;
+    float4 *pos = nullptr, *vel = nullptr;   // scenes * n records each, stepped in place
+    float *stage = nullptr;                  // 6 * scenes * n floats: the stride-3 arrays of an upload or a download
+    float4 *inst = nullptr;                  // 4 * scenes * n records, allocated on first use
+    bool uploaded = false;
+    uint64_t steps = 0;
+    std::string err;
+};
+
+NB_EXPORT const char *nb_scenes_last_error(const nb_scenes *ctx) { return ctx ? ctx->err.c_str() : g_tls_error.c_str(); }
+
+NB_EXPORT void nb_scenes_destroy(nb_scenes *ctx)
+{
+    if (!ctx) return;
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->pos) (void)hipFree(ctx->pos);
+    if (ctx->vel) (void)hipFree(ctx->vel);
+    if (ctx->stage) (void)hipFree(ctx->stage);
+    if (ctx->inst) (void)hipFree(ctx->inst);
+    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    delete ctx;
+}
+
+static int scenes_create_impl(nb_scenes *c)
+{
+    const size_t records = (size_t)c->scenes * c->n;
+    NB_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    NB_HIP(c, hipMalloc((void **)&c->pos, records * sizeof(float4)));
+    NB_HIP(c, hipMalloc((void **)&c->vel, records * sizeof(float4)));
+    NB_HIP(c, hipMalloc((void **)&c->stage, records * 6 * sizeof(float)));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_create(uint32_t scenes, uint32_t n, const nb_params *params, nb_scenes **out)
+{
+    static const char fn[] = "nb_scenes_create";
+    if (!out) {
+        g_tls_error = std::string(fn) + ": out is null";
+        return NB_ERR_INVALID;
+    }
+    *out = nullptr;
+    const nb_params p = params_or_default(params);
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_params_check(fn, p, &g_tls_error);
+    if (rc == NB_OK) rc = check_device(&g_tls_error);
+    if (rc != NB_OK) return rc;
+    nb_scenes *c = new (std::nothrow) nb_scenes();
+    if (!c) {
+        g_tls_error = std::string(fn) + ": out of host memory";
+        return NB_ERR_ALLOC;
+    }
+    c->scenes = scenes, c->n = n, c->p = p;
+    rc = scenes_create_impl(c);
+    if (rc != NB_OK) {
+        g_tls_error = c->err;
+        nb_scenes_destroy(c);
+        return rc;
+    }
+    *out = c;
+    return NB_OK;
+}
+
+// a context entry's first two checks: the context is there, and (where `state`) it holds a state
+static int scenes_ctx_check(nb_scenes *ctx, const char *fn, bool state)
+{
+    if (!ctx) {
+        g_tls_error = std::string(fn) + ": ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (state && !ctx->uploaded) {
+        ctx->err = std::string(fn) + ": no state uploaded (call nb_scenes_upload first)";
+        return NB_ERR_STATE;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_upload(nb_scenes *ctx, const float *pos_xyz, const float *vel_xyz)
+{
+    int rc = scenes_ctx_check(ctx, "nb_scenes_upload", false);
+    if (rc != NB_OK) return rc;
+    if (!pos_xyz || !vel_xyz) {
+        ctx->err = "nb_scenes_upload: null array";
+        return NB_ERR_INVALID;
+    }
+    const size_t records = (size_t)ctx->scenes * ctx->n, bytes = records * 3 * sizeof(float);
+    NB_HIP(ctx, hipMemcpyAsync(ctx->stage, pos_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->stage + 3 * records, vel_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, nbk::launch_import((uint32_t)records, ctx->stage, ctx->stage + 3 * records, ctx->pos, ctx->vel, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host arrays are not retained
+    ctx->uploaded = true;
+    ctx->steps = 0;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_step(nb_scenes *ctx, uint32_t k)
+{
+    int rc = scenes_ctx_check(ctx, "nb_scenes_step", true);
+    if (rc != NB_OK) return rc;
+    nbk::ScenesNbodyArgs a;
+    rc = scenes_nbody_args(ctx->p, ctx->scenes, ctx->n, k, ctx->pos, ctx->vel, &a, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (k == 0) return NB_OK;
+    RoctxRange range("nb_scenes_step");
+    NB_HIP(ctx, nbk::launch_scenes_nbody(a, ctx->stream));
+    ctx->steps += k;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_step_boids(nb_scenes *ctx, uint32_t k, const nb_boids_params *params)
+{
+    static const char fn[] = "nb_scenes_step_boids";
+    int rc = scenes_ctx_check(ctx, fn, false);
+    if (rc != NB_OK) return rc;
+    const nb_boids_params p = boids_params_or_default(params);
+    rc = scenes_boids_params_check(fn, p, &ctx->err);
+    if (rc == NB_OK) rc = scenes_ctx_check(ctx, fn, true);
+    nbk::BoidsArgs c;
+    uint32_t tile = 0;
+    if (rc == NB_OK) rc = make_boids_args(p, ctx->n, 0, ctx->n, &c, &tile, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (k == 0) return NB_OK;
+    RoctxRange range(fn);
+    NB_HIP(ctx, nbk::launch_scenes_boids(c, ctx->pos, ctx->vel, ctx->scenes, k, ctx->stream));
+    ctx->steps += k;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_device_state(nb_scenes *ctx, const void **pos_rec, const void **vel_rec, const void **inst_16n)
+{
+    int rc = scenes_ctx_check(ctx, "nb_scenes_device_state", true);
+    if (rc != NB_OK) return rc;
+    const size_t records = (size_t)ctx->scenes * ctx->n;
+    if (inst_16n) {
+        NB_HIP(ctx, first_use(&ctx->inst, records * 16 * sizeof(float)));
+        NB_HIP(ctx, nbk::launch_instances((uint32_t)records, ctx->pos, ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+        *inst_16n = ctx->inst;
+    }
+    if (pos_rec) *pos_rec = ctx->pos;
+    if (vel_rec) *vel_rec = ctx->vel;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_sync(nb_scenes *ctx)
+{
+    int rc = scenes_ctx_check(ctx, "nb_scenes_sync", false);
+    if (rc != NB_OK) return rc;
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT uint64_t nb_scenes_steps(const nb_scenes *ctx) { return ctx ? ctx->steps : 0; }
+
+NB_EXPORT int nb_scenes_download(nb_scenes *ctx, float *pos_xyz, float *vel_xyz, float *inst_16)
+{
+    static const char fn[] = "nb_scenes_download";
+    int rc = scenes_ctx_check(ctx, fn, false);
+    if (rc != NB_OK) return rc;
+    if (!pos_xyz && !vel_xyz && !inst_16) {
+        ctx->err = std::string(fn) + ": pos_xyz, vel_xyz and inst_16 are all NULL";
+        return NB_ERR_INVALID;
+    }
+    rc = scenes_ctx_check(ctx, fn, true);
+    if (rc != NB_OK) return rc;
+    const size_t records = (size_t)ctx->scenes * ctx->n, bytes = records * 3 * sizeof(float);
+    if (pos_xyz) {
+        NB_HIP(ctx, nbk::launch_unpack((uint32_t)records, ctx->pos, ctx->stage, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(pos_xyz, ctx->stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (vel_xyz) {
+        NB_HIP(ctx, nbk::launch_unpack((uint32_t)records, ctx->vel, ctx->stage + 3 * records, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(vel_xyz, ctx->stage + 3 * records, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (inst_16) {
+        NB_HIP(ctx, first_use(&ctx->inst, records * 16 * sizeof(float)));
+        NB_HIP(ctx, nbk::launch_instances((uint32_t)records, ctx->pos, ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+        NB_HIP(ctx, hipMemcpyAsync(inst_16, ctx->inst, records * 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}

@@ -421,6 +421,98 @@ class Scene:
         return False
 
 
+class SceneBatch:
+    """B independent scenes of n <= NB_SCENES_MAX_BODIES bodies, device-resident, stepped k times by ONE launch with one workgroup
+    per scene.  Every scene gets the bits a :class:`Scene` of its n bodies gets.  ``positions`` and
+    ``velocities`` have shape (B, n, 3); steps are asynchronous on the batch's stream, the accessors wait."""
+
+    def __init__(self, positions, velocities, params: Optional[NbParams] = None):
+        lib = _lib.load()
+        pos = np.ascontiguousarray(positions, np.float32)
+        vel = np.ascontiguousarray(velocities, np.float32)
+        if pos.ndim != 3 or pos.shape[2] != 3 or vel.shape != pos.shape:
+            raise ValueError("positions and velocities must both have shape (scenes, n, 3)")
+        self.scenes, self.n = int(pos.shape[0]), int(pos.shape[1])
+        self.params = params if params is not None else _lib.default_params()
+        self._lib = lib
+        self._ctx = ctypes.c_void_p()
+        self._check(lib.nb_scenes_create(self.scenes, self.n, ctypes.byref(self.params), ctypes.byref(self._ctx)), created=False)
+        try:
+            self._check(lib.nb_scenes_upload(self._ctx, pos.ctypes.data, vel.ctypes.data))
+        except Exception:
+            self.close()
+            raise
+
+    @classmethod
+    def new(cls, scenes: int, n: int, seed: int = 1234, params: Optional[NbParams] = None) -> "SceneBatch":
+        """scene s starts from init_state(n, seed + s)"""
+        states = [init_state(n, seed + s) for s in range(scenes)]
+        return cls(np.stack([p for p, _ in states]) if states else np.zeros((0, n, 3), np.float32),
+                   np.stack([v for _, v in states]) if states else np.zeros((0, n, 3), np.float32), params)
+
+    def _check(self, status: int, created: bool = True) -> None:
+        if status != _lib.NB_OK:
+            msg = self._lib.nb_scenes_last_error(self._ctx if created else None)
+            raise NbError(status, msg.decode("utf-8", "replace") if msg else "")
+
+    def step(self, k: int = 1) -> None:
+        """k update_instance_nbody of every scene (STRICT), one launch"""
+        self._check(self._lib.nb_scenes_step(self._ctx, int(k)))
+
+    def step_boids(self, k: int = 1, params: Optional[NbBoidsParams] = None) -> None:
+        """k update_instance_boids of every scene, one launch"""
+        self._check(self._lib.nb_scenes_step_boids(self._ctx, int(k), ctypes.byref(params) if params is not None else None))
+
+    def _download(self, what: int) -> np.ndarray:
+        out = np.empty((self.scenes, self.n, 4, 4) if what == 2 else (self.scenes, self.n, 3), np.float32)
+        args = [None, None, None]
+        args[what] = out.ctypes.data
+        self._check(self._lib.nb_scenes_download(self._ctx, *args))
+        return out
+
+    def positions(self) -> np.ndarray:
+        return self._download(0)
+
+    def velocities(self) -> np.ndarray:
+        return self._download(1)
+
+    def instances(self) -> np.ndarray:
+        """model matrices of the current state, shape (B, n, 4, 4); [k] is column k"""
+        return self._download(2)
+
+    def device_state(self, with_instances: bool = True):
+        """Device pointers (ints) of the batch's position records, velocity records and model matrices; scene s starts s * n
+        records (matrices) behind each.  Valid until the next step / upload / close."""
+        p, v, m = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.nb_scenes_device_state(self._ctx, ctypes.byref(p), ctypes.byref(v), ctypes.byref(m) if with_instances else None))
+        return p.value, v.value, (m.value if with_instances else None)
+
+    def sync(self) -> None:
+        self._check(self._lib.nb_scenes_sync(self._ctx))
+
+    @property
+    def steps_done(self) -> int:
+        return int(self._lib.nb_scenes_steps(self._ctx))
+
+    def close(self) -> None:
+        if getattr(self, "_ctx", None) is not None and self._ctx:
+            self._lib.nb_scenes_destroy(self._ctx)
+            self._ctx = ctypes.c_void_p()
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 def _check_update_args(instances, positions, old_positions, velocities, old_velocities):
     for name, arr, tail in (("instances", instances, (4, 4)), ("positions", positions, (3,)),
                             ("old_positions", old_positions, (3,)), ("velocities", velocities, (3,)),
