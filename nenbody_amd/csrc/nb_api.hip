@@ -631,48 +631,85 @@ float uniform_f32(uint64_t &s, float lo, float hi)
 
 }  // namespace
 
+// A device buffer of a context (nb_ctx, nb_scenes): its pointer `p`, which the launches take, and its capacity in cells of T.  It is
+// freed with the context and cannot be copied.  reserve(cells) does nothing while the buffer is large enough; otherwise it frees the
+// buffer and allocates a larger one -- the contents are not carried over, and it never shrinks.  After a failure it is empty.  A
+// buffer of a fixed size (vel_alt, cams, inst, frame_cam: allocated at first use) is reserved with that size at every use.
+template <typename T>
+struct DeviceBuffer {
+    T *p = nullptr;
+    size_t cells = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    ~DeviceBuffer() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cells = 0;
+    }
+    hipError_t reserve(size_t want)
+    {
+        if (want <= cells) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+        if (e == hipSuccess)
+            cells = want;
+        else
+            p = nullptr;
+        return e;
+    }
+    void swap(DeviceBuffer &other)
+    {
+        std::swap(p, other.p);
+        std::swap(cells, other.cells);
+    }
+};
+
 struct nb_ctx {
     uint32_t n = 0;
     nb_params p{};
     Plan plan{};
     hipStream_t stream = nullptr;
-    float4 *pos[2] = {nullptr, nullptr};
-    float4 *vel = nullptr;
-    float4 *vel_alt = nullptr;  // second velocity buffer: boids reads every old velocity, so velocities ping-pong too
-    float *stage = nullptr;   // 3n floats: stride-3 staging for upload/download
-    float4 *inst = nullptr;   // 4n float4, allocated on first use
-    float4 *cams = nullptr;   // 4n float4, allocated on first use (nb_cameras, nb_eyes)
-    uint32_t *eye_ids = nullptr;  // nb_eyes' rows, allocated on first use and grown on demand: eye_ids_cap / eye_depth_cap entries
-    float *eye_depth = nullptr;
-    size_t eye_ids_cap = 0, eye_depth_cap = 0;
-    float *eye_rgba = nullptr;    // nb_eyes_colour's rows, likewise: eye_rgba_cap / eye_bgra_cap columns (4 floats / one word each)
-    uint32_t *eye_bgra = nullptr;
-    size_t eye_rgba_cap = 0, eye_bgra_cap = 0;
-    uint32_t *seen_count = nullptr;  // nb_eyes_seen's and nb_step_boids_seen's lists, likewise: seen_*_cap entries (one count an eye, one slot a column)
-    uint32_t *seen_ids = nullptr;
-    float *seen_depth = nullptr;
-    uint32_t *seen_cols = nullptr;
-    size_t seen_count_cap = 0, seen_ids_cap = 0, seen_depth_cap = 0, seen_cols_cap = 0;
-    uint32_t *loc_col = nullptr;     // nb_eyes_located's and nb_step_nbody_located's located rows, likewise: loc_*_cap slots (one word / one record each)
-    float4 *loc_rel = nullptr;
-    size_t loc_col_cap = 0, loc_rel_cap = 0;
-    float *skin = nullptr;        // nb_eyes_skin's texels (skin_w x skin_h x 4 floats); null: the 1 x 1 white skin
+    DeviceBuffer<float4> pos[2];
+    DeviceBuffer<float4> vel;
+    DeviceBuffer<float4> vel_alt;  // second velocity buffer: boids reads every old velocity, so velocities ping-pong too
+    DeviceBuffer<float> stage;     // 3n floats: stride-3 staging for upload/download
+    DeviceBuffer<float4> inst;     // 4n float4, allocated on first use
+    DeviceBuffer<float4> cams;     // 4n float4, allocated on first use (nb_cameras, nb_eyes)
+    DeviceBuffer<uint32_t> eye_ids;  // nb_eyes' rows, allocated on first use and grown on demand: one word a column (a sample under 8 samples)
+    DeviceBuffer<float> eye_depth;
+    DeviceBuffer<float4> eye_rgba;   // nb_eyes_colour's rows, likewise: one record / one word a column
+    DeviceBuffer<uint32_t> eye_bgra;
+    DeviceBuffer<uint32_t> seen_count;  // nb_eyes_seen's and nb_step_boids_seen's lists, likewise: one count an eye, one slot a column
+    DeviceBuffer<uint32_t> seen_ids;
+    DeviceBuffer<float> seen_depth;
+    DeviceBuffer<uint32_t> seen_cols;
+    DeviceBuffer<uint32_t> loc_col;     // nb_eyes_located's and nb_step_nbody_located's located rows, likewise: one word / one record a slot
+    DeviceBuffer<float4> loc_rel;
+    DeviceBuffer<float> skin;        // nb_eyes_skin's texels (skin_w x skin_h x 4 floats); empty: the 1 x 1 white skin
     uint32_t skin_w = 0, skin_h = 0;
-    uint64_t *frame_keys = nullptr;  // nb_frame's and nb_frame_msaa's key plane, grown on demand: frame_keys_cap keys (their rows are the eye rows above)
-    size_t frame_keys_cap = 0;
-    float4 *frame_cam = nullptr;     // 6 float4: nb_frame's camera, then nb_camera_at's eye and direction records
-    float *xfer = nullptr;    // 22n floats [matrices 16n | positions 3n | velocities 3n]: one-copy round trip of the drop-in calls
-    float *hxfer = nullptr;   // its pinned host twin
+    DeviceBuffer<uint64_t> frame_keys;  // nb_frame's and nb_frame_msaa's key plane, grown on demand (their rows are the eye rows above)
+    DeviceBuffer<float4> frame_cam;     // 6 float4: nb_frame's camera, then nb_camera_at's eye and direction records
+    DeviceBuffer<float> xfer;    // 22n floats [matrices 16n | positions 3n | velocities 3n] and a tail: one-copy round trip of the drop-in calls
+    float *hxfer = nullptr;   // its pinned host twin (hipHostMalloc: freed by the destructor below)
     float *hxfer_dev = nullptr;  // the device's address of hxfer (mapped host memory: kernels of the small-set drop-in read and write it directly)
-    uint32_t *done_counter = nullptr;  // export_kernel's workgroup counter (ExportDone)
+    DeviceBuffer<uint32_t> done_counter;  // export_kernel's workgroup counter (ExportDone)
     uint32_t done_seq = 0, polled_calls = 0;
     uint32_t poll_holdoff = 0, poll_backoff = 0;  // calls that take the stream wait after a poll that timed out (wait_export)
-    void *scratch = nullptr;
+    DeviceBuffer<char> scratch;
     StatusWord status;        // sticky failure word of this context's block-chain launches
     int cur = 0;
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
+    // what no DeviceBuffer holds: the pinned buffer and the status word (StatusWord is nb_shard's too)
+    ~nb_ctx()
+    {
+        if (hxfer) (void)hipHostFree(hxfer);
+        if (status.w) (void)hipFree(status.w);
+    }
 };
 
 #define NB_HIP(ctx, call)                                                                          \
@@ -684,11 +721,39 @@ struct nb_ctx {
         }                                                                                          \
     } while (0)
 
-// one of the context's buffers of a fixed size (vel_alt, cams, inst, frame_cam): allocated on first use, kept until nb_destroy
-template <typename T>
-static hipError_t first_use(T **buf, size_t bytes)
+// A context entry's first checks, for nb_ctx and nb_scenes alike: the context is there (the text goes to the thread) and, where
+// `state_hint` is given, it holds a state (the text goes to the context).  state_hint: what the entry's text has behind "no state
+// uploaded" -- "", kCallUpload or kCallScenesUpload --; NULL: the entry needs no state, or checks its arguments first and calls again.
+static const char kCallUpload[] = " (call nb_upload first)";
+static const char kCallScenesUpload[] = " (call nb_scenes_upload first)";
+template <typename Ctx>
+static int ctx_check(Ctx *ctx, const char *fn, const char *state_hint = nullptr)
 {
-    return *buf ? hipSuccess : hipMalloc((void **)buf, bytes);
+    if (!ctx) {
+        g_tls_error = std::string(fn) + ": ctx is null";
+        return NB_ERR_INVALID;
+    }
+    if (state_hint && !ctx->uploaded) {
+        ctx->err = std::string(fn) + ": no state uploaded" + state_hint;
+        return NB_ERR_STATE;
+    }
+    return NB_OK;
+}
+
+// the model matrices of the n records pos / vel on `stream`, into the context's `inst` (4n float4, allocated on first use)
+static hipError_t launch_matrices(uint32_t n, const float4 *pos, const float4 *vel, DeviceBuffer<float4> *inst, hipStream_t stream)
+{
+    const hipError_t e = inst->reserve((size_t)n * 4);
+    if (e != hipSuccess) return e;
+    return nbk::launch_instances(n, pos, vel, inst->p, stream, overrides().inst_device_libm.on() ? 1u : 0u);
+}
+
+// a step of the context is enqueued: the position buffers flip, the velocity buffers swap where the step wrote vel_alt, and it counts
+static void step_done(nb_ctx *c, bool wrote_vel_alt)
+{
+    c->cur ^= 1;
+    if (wrote_vel_alt) c->vel.swap(c->vel_alt);
+    c->steps++;
 }
 
 NB_EXPORT int nb_abi_version(void) { return NB_ABI_VERSION; }
@@ -740,34 +805,10 @@ NB_EXPORT int nb_init_state(uint64_t seed, uint32_t n, float *pos_xyz, float *ve
 NB_EXPORT void nb_destroy(nb_ctx *ctx)
 {
     if (!ctx) return;
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->pos[0]) (void)hipFree(ctx->pos[0]);
-    if (ctx->pos[1]) (void)hipFree(ctx->pos[1]);
-    if (ctx->vel) (void)hipFree(ctx->vel);
-    if (ctx->vel_alt) (void)hipFree(ctx->vel_alt);
-    if (ctx->stage) (void)hipFree(ctx->stage);
-    if (ctx->inst) (void)hipFree(ctx->inst);
-    if (ctx->cams) (void)hipFree(ctx->cams);
-    if (ctx->eye_ids) (void)hipFree(ctx->eye_ids);
-    if (ctx->eye_depth) (void)hipFree(ctx->eye_depth);
-    if (ctx->eye_rgba) (void)hipFree(ctx->eye_rgba);
-    if (ctx->eye_bgra) (void)hipFree(ctx->eye_bgra);
-    if (ctx->seen_count) (void)hipFree(ctx->seen_count);
-    if (ctx->seen_ids) (void)hipFree(ctx->seen_ids);
-    if (ctx->seen_depth) (void)hipFree(ctx->seen_depth);
-    if (ctx->seen_cols) (void)hipFree(ctx->seen_cols);
-    if (ctx->loc_col) (void)hipFree(ctx->loc_col);
-    if (ctx->loc_rel) (void)hipFree(ctx->loc_rel);
-    if (ctx->skin) (void)hipFree(ctx->skin);
-    if (ctx->frame_keys) (void)hipFree(ctx->frame_keys);
-    if (ctx->frame_cam) (void)hipFree(ctx->frame_cam);
-    if (ctx->xfer) (void)hipFree(ctx->xfer);
-    if (ctx->hxfer) (void)hipHostFree(ctx->hxfer);
-    if (ctx->done_counter) (void)hipFree(ctx->done_counter);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->status.w) (void)hipFree(ctx->status.w);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t stream = ctx->stream;
+    if (stream) (void)hipStreamSynchronize(stream);
+    delete ctx;  // frees its buffers: behind the wait, in front of the stream's end
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 // Sets up to this size cross the bus as ONE pinned copy each way (they are all latency: every separate copy and wait
@@ -805,16 +846,16 @@ static bool small_set_poll(uint32_t n) { return small_set_zero_copy(n) && overri
 
 static int ensure_xfer(nb_ctx *c)
 {
-    const size_t bytes = ((size_t)c->n * 22 + 16) * sizeof(float);  // + a tail: the status word and the completion word ride along
-    if (!c->xfer) NB_HIP(c, hipMalloc((void **)&c->xfer, bytes));
+    const size_t floats = (size_t)c->n * 22 + 16;  // + a tail: the status word and the completion word ride along
+    NB_HIP(c, c->xfer.reserve(floats));
     if (!c->hxfer) {
-        NB_HIP(c, hipHostMalloc((void **)&c->hxfer, bytes, hipHostMallocMapped));
+        NB_HIP(c, hipHostMalloc((void **)&c->hxfer, floats * sizeof(float), hipHostMallocMapped));
         NB_HIP(c, hipHostGetDevicePointer((void **)&c->hxfer_dev, c->hxfer, 0));
         std::memset(c->hxfer + 22 * (size_t)c->n, 0, 16 * sizeof(float));
     }
-    if (!c->done_counter) {
-        NB_HIP(c, hipMalloc((void **)&c->done_counter, sizeof(uint32_t)));
-        NB_HIP(c, hipMemset(c->done_counter, 0, sizeof(uint32_t)));
+    if (!c->done_counter.p) {
+        NB_HIP(c, c->done_counter.reserve(1));
+        NB_HIP(c, hipMemset(c->done_counter.p, 0, sizeof(uint32_t)));
     }
     return NB_OK;
 }
@@ -828,7 +869,7 @@ static nbk::ExportDone export_done(nb_ctx *c, bool polled)
         polled = false;
     }
     if (polled) {
-        d.counter = c->done_counter;
+        d.counter = c->done_counter.p;
         d.word = (uint32_t *)(c->hxfer_dev + 22 * (size_t)c->n + kDoneWordAt);
         d.seq = ++c->done_seq ? c->done_seq : ++c->done_seq;  // never 0 (the word's initial value)
     }
@@ -872,7 +913,7 @@ static int wait_export(nb_ctx *c, const nbk::ExportDone &d)
         c->poll_backoff = c->poll_backoff ? std::min(c->poll_backoff * 2u, 4096u) : 64u;
         c->poll_holdoff = c->poll_backoff;
         NB_HIP(c, hipStreamSynchronize(c->stream));
-        if (*w != d.seq) NB_HIP(c, hipMemsetAsync(c->done_counter, 0, sizeof(uint32_t), c->stream));  // (stream-ordered in front of the next export)
+        if (*w != d.seq) NB_HIP(c, hipMemsetAsync(c->done_counter.p, 0, sizeof(uint32_t), c->stream));  // (stream-ordered in front of the next export)
         return NB_OK;
     }
     NB_HIP(c, hipStreamSynchronize(c->stream));
@@ -881,14 +922,12 @@ static int wait_export(nb_ctx *c, const nbk::ExportDone &d)
 
 static int create_impl(nb_ctx *c)
 {
-    const size_t rec = (size_t)c->n * sizeof(float4);
     NB_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    NB_HIP(c, hipMalloc((void **)&c->pos[0], rec));
-    NB_HIP(c, hipMalloc((void **)&c->pos[1], rec));
-    NB_HIP(c, hipMalloc((void **)&c->vel, rec));
-    NB_HIP(c, hipMalloc((void **)&c->stage, (size_t)c->n * 3 * sizeof(float)));
-    const size_t sb = plan_scratch_bytes(c->plan, c->n);
-    if (sb) NB_HIP(c, hipMalloc(&c->scratch, sb));
+    NB_HIP(c, c->pos[0].reserve(c->n));
+    NB_HIP(c, c->pos[1].reserve(c->n));
+    NB_HIP(c, c->vel.reserve(c->n));
+    NB_HIP(c, c->stage.reserve((size_t)c->n * 3));
+    NB_HIP(c, c->scratch.reserve(plan_scratch_bytes(c->plan, c->n)));  // (none for most plans)
     return NB_OK;
 }
 
@@ -928,12 +967,49 @@ NB_EXPORT int nb_create(uint32_t n, uint32_t n_devices, const nb_params *params,
     return NB_OK;
 }
 
+// The two halves of a small set's round trip (n <= kRoundtripMax; ensure_xfer() has been called), shared by nb_upload / nb_download
+// and the drop-ins (nb_dropin.inc: update_roundtrip).  hxfer and xfer hold [matrices 16n | positions 3n | velocities 3n | tail] on
+// the way out and [positions 3n | velocities 3n] on the way in.
+
+// The way in, enqueued and not waited for: the caller's arrays into hxfer, from there into pos[0] and vel.
+static int small_import(nb_ctx *c, const float *pos_xyz, const float *vel_xyz)
+{
+    const size_t n = c->n, bytes = n * 3 * sizeof(float);
+    std::memcpy(c->hxfer, pos_xyz, bytes);
+    std::memcpy(c->hxfer + 3 * n, vel_xyz, bytes);
+    float *src = c->hxfer_dev;  // the kernel reads the pinned buffer through the bus ...
+    if (!small_set_zero_copy(c->n)) {  // ... or a DMA copy stages it in device memory first
+        NB_HIP(c, hipMemcpyAsync(c->xfer.p, c->hxfer, 2 * bytes, hipMemcpyHostToDevice, c->stream));
+        src = c->xfer.p;
+    }
+    NB_HIP(c, nbk::launch_import(c->n, src, src + 3 * n, c->pos[0].p, c->vel.p, c->stream));
+    return NB_OK;
+}
+
+// The way out, up to "the parts wanted and the status are in hxfer" (one launch, one wait): the caller copies them out and reports
+// status_from_tail(c, *with_status), in the order it owes its own caller.
+static int small_export(nb_ctx *c, bool inst, bool pos, bool vel, bool *with_status)
+{
+    const size_t n = c->n;
+    const bool zero_copy = small_set_zero_copy(c->n);
+    float *const dst = zero_copy ? c->hxfer_dev : c->xfer.p;
+    // the sticky status word of this context's block-chain launches comes home in the same buffer: no second wait
+    const bool ws = *with_status = c->status.dirty && c->status.w;
+    const nbk::ExportDone done = export_done(c, small_set_poll(c->n));
+    NB_HIP(c, nbk::launch_export(c->n, c->pos[c->cur].p, c->vel.p, inst ? (float4 *)dst : nullptr, pos ? dst + 16 * n : nullptr,
+                                 vel ? dst + 19 * n : nullptr, ws ? c->status.w : nullptr, ws ? (uint32_t *)(dst + 22 * n) : nullptr,
+                                 c->stream, overrides().inst_device_libm.on() ? 1u : 0u, done));
+    if (!zero_copy) {  // the floats from the first part wanted to the last one, in one DMA copy
+        const size_t lo = inst ? 0 : (pos ? 16 * n : 19 * n), hi = ws ? 22 * n + 1 : vel ? 22 * n : (pos ? 19 * n : 16 * n);
+        NB_HIP(c, hipMemcpyAsync(c->hxfer + lo, c->xfer.p + lo, (hi - lo) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    return wait_export(c, done);
+}
+
 NB_EXPORT int nb_upload(nb_ctx *ctx, const float *pos_xyz, const float *vel_xyz)
 {
-    if (!ctx) {
-        g_tls_error = "nb_upload: ctx is null";
-        return NB_ERR_INVALID;
-    }
+    int rc = ctx_check(ctx, "nb_upload");
+    if (rc != NB_OK) return rc;
     if (!pos_xyz || !vel_xyz) {
         ctx->err = "nb_upload: null array";
         return NB_ERR_INVALID;
@@ -941,27 +1017,21 @@ NB_EXPORT int nb_upload(nb_ctx *ctx, const float *pos_xyz, const float *vel_xyz)
     const size_t bytes = (size_t)ctx->n * 3 * sizeof(float);
     ctx->cur = 0;
     if (ctx->n <= kRoundtripMax) {  // one pinned copy, no wait: the stream orders it before the first step
-        int rc = ensure_xfer(ctx);
+        rc = ensure_xfer(ctx);
         if (rc != NB_OK) return rc;
         NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a download still reading hxfer must be done (it always is: downloads wait)
-        std::memcpy(ctx->hxfer, pos_xyz, bytes);
-        std::memcpy(ctx->hxfer + 3 * (size_t)ctx->n, vel_xyz, bytes);
-        float *src = ctx->hxfer_dev;  // the kernel reads the pinned buffer through the bus ...
-        if (!small_set_zero_copy(ctx->n)) {  // ... or a DMA copy stages it in device memory first
-            NB_HIP(ctx, hipMemcpyAsync(ctx->xfer, ctx->hxfer, 2 * bytes, hipMemcpyHostToDevice, ctx->stream));
-            src = ctx->xfer;
-        }
-        NB_HIP(ctx, nbk::launch_import(ctx->n, src, src + 3 * (size_t)ctx->n, ctx->pos[0], ctx->vel, ctx->stream));
+        rc = small_import(ctx, pos_xyz, vel_xyz);
+        if (rc != NB_OK) return rc;
         NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // hxfer / xfer are reused by the next call
         ctx->uploaded = true;
         ctx->steps = 0;
         return NB_OK;
     }
-    NB_HIP(ctx, hipMemcpyAsync(ctx->stage, pos_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    NB_HIP(ctx, nbk::launch_pack(ctx->n, ctx->stage, ctx->pos[0], ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->stage.p, pos_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, nbk::launch_pack(ctx->n, ctx->stage.p, ctx->pos[0].p, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // stage is reused; the host array is not retained
-    NB_HIP(ctx, hipMemcpyAsync(ctx->stage, vel_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    NB_HIP(ctx, nbk::launch_pack(ctx->n, ctx->stage, ctx->vel, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->stage.p, vel_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, nbk::launch_pack(ctx->n, ctx->stage.p, ctx->vel.p, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->uploaded = true;
     ctx->steps = 0;
@@ -970,21 +1040,14 @@ NB_EXPORT int nb_upload(nb_ctx *ctx, const float *pos_xyz, const float *vel_xyz)
 
 NB_EXPORT int nb_step(nb_ctx *ctx, uint32_t k)
 {
-    if (!ctx) {
-        g_tls_error = "nb_step: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!ctx->uploaded) {
-        ctx->err = "nb_step: no state uploaded (call nb_upload first)";
-        return NB_ERR_STATE;
-    }
+    int rc = ctx_check(ctx, "nb_step", kCallUpload);
+    if (rc != NB_OK) return rc;
     RoctxRange range("nb_step");
     for (uint32_t s = 0; s < k; ++s) {
-        int rc = launch_step_planned(ctx->p, ctx->plan, ctx->n, 0, ctx->n, ctx->pos[ctx->cur], ctx->pos[ctx->cur ^ 1],
-                                     ctx->vel, ctx->scratch, ctx->stream, &ctx->err, &ctx->status);
+        rc = launch_step_planned(ctx->p, ctx->plan, ctx->n, 0, ctx->n, ctx->pos[ctx->cur].p, ctx->pos[ctx->cur ^ 1].p, ctx->vel.p,
+                                 ctx->scratch.p, ctx->stream, &ctx->err, &ctx->status);
         if (rc != NB_OK) return rc;
-        ctx->cur ^= 1;
-        ctx->steps++;
+        step_done(ctx, false);
     }
     return NB_OK;
 }
@@ -1004,46 +1067,32 @@ NB_EXPORT void nb_boids_default_params(nb_boids_params *p)
 
 NB_EXPORT int nb_step_boids(nb_ctx *ctx, uint32_t k, const nb_boids_params *params)
 {
-    if (!ctx) {
-        g_tls_error = "nb_step_boids: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!ctx->uploaded) {
-        ctx->err = "nb_step_boids: no state uploaded (call nb_upload first)";
-        return NB_ERR_STATE;
-    }
+    int rc = ctx_check(ctx, "nb_step_boids", kCallUpload);
+    if (rc != NB_OK) return rc;
     const nb_boids_params p = boids_params_or_default(params);
     nbk::BoidsArgs a;
     uint32_t tile = 0;
-    int rc = make_boids_args(p, ctx->n, 0, ctx->n, &a, &tile, &ctx->err);
+    rc = make_boids_args(p, ctx->n, 0, ctx->n, &a, &tile, &ctx->err);
     if (rc != NB_OK) return rc;
-    NB_HIP(ctx, first_use(&ctx->vel_alt, (size_t)ctx->n * sizeof(float4)));
+    NB_HIP(ctx, ctx->vel_alt.reserve(ctx->n));
     RoctxRange range("nb_step_boids");
     for (uint32_t s = 0; s < k; ++s) {
-        a.pos_in = ctx->pos[ctx->cur];
-        a.pos_out = ctx->pos[ctx->cur ^ 1];
-        a.vel_in = ctx->vel;
-        a.vel_out = ctx->vel_alt;
+        a.pos_in = ctx->pos[ctx->cur].p;
+        a.pos_out = ctx->pos[ctx->cur ^ 1].p;
+        a.vel_in = ctx->vel.p;
+        a.vel_out = ctx->vel_alt.p;
         NB_HIP(ctx, nbk::launch_boids(a, tile, boids_form(a.count), ctx->stream));
-        ctx->cur ^= 1;
-        std::swap(ctx->vel, ctx->vel_alt);
-        ctx->steps++;
+        step_done(ctx, true);
     }
     return NB_OK;
 }
 
 NB_EXPORT int nb_step_random(nb_ctx *ctx, uint32_t k, uint64_t seed)
 {
-    if (!ctx) {
-        g_tls_error = "nb_step_random: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!ctx->uploaded) {
-        ctx->err = "nb_step_random: no state uploaded (call nb_upload first)";
-        return NB_ERR_STATE;
-    }
+    const int rc = ctx_check(ctx, "nb_step_random", kCallUpload);
+    if (rc != NB_OK) return rc;
     for (uint32_t s = 0; s < k; ++s) {
-        NB_HIP(ctx, nbk::launch_random(0, ctx->n, ctx->pos[ctx->cur], ctx->vel, seed, ctx->steps, ctx->stream));
+        NB_HIP(ctx, nbk::launch_random(0, ctx->n, ctx->pos[ctx->cur].p, ctx->vel.p, seed, ctx->steps, ctx->stream));
         ctx->steps++;
     }
     return NB_OK;
@@ -1051,21 +1100,14 @@ NB_EXPORT int nb_step_random(nb_ctx *ctx, uint32_t k, uint64_t seed)
 
 NB_EXPORT int nb_device_state(nb_ctx *ctx, const void **pos_rec, const void **vel_rec, const void **inst_16n)
 {
-    if (!ctx) {
-        g_tls_error = "nb_device_state: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!ctx->uploaded) {
-        ctx->err = "nb_device_state: no state uploaded";
-        return NB_ERR_STATE;
-    }
+    const int rc = ctx_check(ctx, "nb_device_state", "");
+    if (rc != NB_OK) return rc;
     if (inst_16n) {
-        NB_HIP(ctx, first_use(&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-        NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
-        *inst_16n = ctx->inst;
+        NB_HIP(ctx, launch_matrices(ctx->n, ctx->pos[ctx->cur].p, ctx->vel.p, &ctx->inst, ctx->stream));
+        *inst_16n = ctx->inst.p;
     }
-    if (pos_rec) *pos_rec = ctx->pos[ctx->cur];
-    if (vel_rec) *vel_rec = ctx->vel;
+    if (pos_rec) *pos_rec = ctx->pos[ctx->cur].p;
+    if (vel_rec) *vel_rec = ctx->vel.p;
     return NB_OK;
 }
 
@@ -1104,21 +1146,17 @@ NB_EXPORT int nb_camera_constant(float vertical_fov_deg, float aspect_ratio, flo
 
 NB_EXPORT int nb_cameras(nb_ctx *ctx, const float *up_xyz, const float *cp16, float *out_16n)
 {
-    if (!ctx) {
-        g_tls_error = "nb_cameras: ctx is null";
-        return NB_ERR_INVALID;
-    }
+    int rc = ctx_check(ctx, "nb_cameras");
+    if (rc != NB_OK) return rc;
     if (!up_xyz || !cp16 || !out_16n) {
         ctx->err = "nb_cameras: null argument";
         return NB_ERR_INVALID;
     }
-    if (!ctx->uploaded) {
-        ctx->err = "nb_cameras: no state uploaded";
-        return NB_ERR_STATE;
-    }
-    NB_HIP(ctx, first_use(&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_cameras(ctx->n, ctx->pos[ctx->cur], ctx->vel, up_xyz, cp16, ctx->cams, ctx->stream));
-    NB_HIP(ctx, hipMemcpyAsync(out_16n, ctx->cams, (size_t)ctx->n * 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    rc = ctx_check(ctx, "nb_cameras", "");
+    if (rc != NB_OK) return rc;
+    NB_HIP(ctx, ctx->cams.reserve((size_t)ctx->n * 4));
+    NB_HIP(ctx, nbk::launch_cameras(ctx->n, ctx->pos[ctx->cur].p, ctx->vel.p, up_xyz, cp16, ctx->cams.p, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(out_16n, ctx->cams.p, (size_t)ctx->n * 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
 }
@@ -1214,19 +1252,6 @@ static int outputs_check(const char *fn, const ByteRange (&out)[N], uint32_t nee
     return NB_OK;
 }
 
-// grow one of the context's eye rows to `cells` entries of `cell_bytes` each (nothing to do while it is large enough)
-template <typename T>
-static hipError_t grow_row(T **row, size_t *cap, size_t cells, size_t cell_bytes)
-{
-    if (cells <= *cap) return hipSuccess;
-    if (*row) (void)hipFree(*row);
-    *row = nullptr;
-    *cap = 0;
-    const hipError_t e = hipMalloc((void **)row, cells * cell_bytes);
-    if (e == hipSuccess) *cap = cells;
-    return e;
-}
-
 // The context's entries then read: check, stage, launch, download.  The three helpers below are their staging and their download,
 // every operation on the context's stream in the order given.
 
@@ -1234,10 +1259,10 @@ static hipError_t grow_row(T **row, size_t *cap, size_t cells, size_t cell_bytes
 // rgba and bgra8
 static int grow_rows(nb_ctx *ctx, const void *ids, const void *depth, const void *rgba, const void *bgra8, size_t words, size_t cells)
 {
-    if (ids) NB_HIP(ctx, grow_row(&ctx->eye_ids, &ctx->eye_ids_cap, words, sizeof(uint32_t)));
-    if (depth) NB_HIP(ctx, grow_row(&ctx->eye_depth, &ctx->eye_depth_cap, words, sizeof(float)));
-    if (rgba) NB_HIP(ctx, grow_row(&ctx->eye_rgba, &ctx->eye_rgba_cap, cells, 4 * sizeof(float)));
-    if (bgra8) NB_HIP(ctx, grow_row(&ctx->eye_bgra, &ctx->eye_bgra_cap, cells, sizeof(uint32_t)));
+    if (ids) NB_HIP(ctx, ctx->eye_ids.reserve(words));
+    if (depth) NB_HIP(ctx, ctx->eye_depth.reserve(words));
+    if (rgba) NB_HIP(ctx, ctx->eye_rgba.reserve(cells));
+    if (bgra8) NB_HIP(ctx, ctx->eye_bgra.reserve(cells));
     return NB_OK;
 }
 
@@ -1246,21 +1271,20 @@ static int grow_rows(nb_ctx *ctx, const void *ids, const void *depth, const void
 static int stage_matrices(nb_ctx *ctx, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16)
 {
     if (up_xyz) {
-        NB_HIP(ctx, first_use(&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
-        NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur] + first, ctx->vel + first, up_xyz, cp16, ctx->cams, ctx->stream));
+        NB_HIP(ctx, ctx->cams.reserve((size_t)ctx->n * 4));
+        NB_HIP(ctx, nbk::launch_cameras(count, ctx->pos[ctx->cur].p + first, ctx->vel.p + first, up_xyz, cp16, ctx->cams.p, ctx->stream));
     }
-    NB_HIP(ctx, first_use(&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+    NB_HIP(ctx, launch_matrices(ctx->n, ctx->pos[ctx->cur].p, ctx->vel.p, &ctx->inst, ctx->stream));
     return NB_OK;
 }
 
 // the rows to the host, for the outputs wanted, and the wait for them
 static int download_rows(nb_ctx *ctx, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8, size_t words, size_t cells)
 {
-    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth, words * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba, cells * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (ids) NB_HIP(ctx, hipMemcpyAsync(ids, ctx->eye_ids.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (depth) NB_HIP(ctx, hipMemcpyAsync(depth, ctx->eye_depth.p, words * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba) NB_HIP(ctx, hipMemcpyAsync(rgba, ctx->eye_rgba.p, cells * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+    if (bgra8) NB_HIP(ctx, hipMemcpyAsync(bgra8, ctx->eye_bgra.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
 }
@@ -1281,10 +1305,8 @@ template <typename Launch>
 static int ctx_eyes(nb_ctx *ctx, const ViewForm &f, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16, uint32_t width,
                     uint32_t flags, uint32_t *ids, float *depth, float *rgba, uint32_t *bgra8, Launch launch)
 {
-    if (!ctx) {
-        g_tls_error = std::string(f.fn) + ": ctx is null";
-        return NB_ERR_INVALID;
-    }
+    int rc = ctx_check(ctx, f.fn);
+    if (rc != NB_OK) return rc;
     if (!up_xyz || !cp16) {
         ctx->err = std::string(f.fn) + ": null argument";
         return NB_ERR_INVALID;
@@ -1292,13 +1314,10 @@ static int ctx_eyes(nb_ctx *ctx, const ViewForm &f, uint32_t first, uint32_t cou
     const size_t cells = (size_t)count * width, words = f.msaa ? cells * NB_EYES_SAMPLES : cells;
     const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
     const ByteRange out[4] = {{ids, words * 4u}, {depth, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = eyes_range_check(f.fn, ctx->n, first, count, width, f.msaa, flags, &ctx->err);
+    rc = eyes_range_check(f.fn, ctx->n, first, count, width, f.msaa, flags, &ctx->err);
     if (rc == NB_OK) rc = outputs_check(f.fn, out, f.need, f.none_msg, f.aligned4, in, 2, kEyesAlias, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, f.fn, "");
     if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = std::string(f.fn) + ": no state uploaded";
-        return NB_ERR_STATE;
-    }
     if (count == 0) return NB_OK;
     rc = grow_rows(ctx, ids, depth, rgba, bgra8, words, cells);
     if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
@@ -1312,8 +1331,8 @@ NB_EXPORT int nb_eyes(nb_ctx *ctx, uint32_t first, uint32_t count, const float *
 {
     static const ViewForm f = {"nb_eyes", false, 0x3u, kNoIdsDepth, false, nullptr};
     return ctx_eyes(ctx, f, first, count, up_xyz, cp16, width, flags, ids, depth, nullptr, nullptr, [&]() -> int {
-        NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags,
-                                     ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr, ctx->stream));
+        NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, count, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width, flags,
+                                     ids ? ctx->eye_ids.p : nullptr, depth ? ctx->eye_depth.p : nullptr, ctx->stream));
         return NB_OK;
     });
 }
@@ -1346,22 +1365,19 @@ NB_EXPORT int nb_srgb_encode(const float *linear, size_t n, uint8_t *out)
 
 NB_EXPORT int nb_eyes_skin(nb_ctx *ctx, const float *rgba_linear, uint32_t tw, uint32_t th)
 {
-    if (!ctx) {
-        g_tls_error = "nb_eyes_skin: ctx is null";
-        return NB_ERR_INVALID;
-    }
+    const int rc = ctx_check(ctx, "nb_eyes_skin");
+    if (rc != NB_OK) return rc;
     if (rgba_linear && (tw == 0 || th == 0 || tw > NB_EYES_MAX_SKIN || th > NB_EYES_MAX_SKIN)) {
         ctx->err = "nb_eyes_skin: tw and th must be 1 .. NB_EYES_MAX_SKIN (2048)";
         return NB_ERR_INVALID;
     }
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (every eye call waits for its kernel: nothing reads the old skin any more)
-    if (ctx->skin) (void)hipFree(ctx->skin);
-    ctx->skin = nullptr;
+    ctx->skin.release();                              // (a skin is as large as it says: none is kept for a smaller one)
     ctx->skin_w = ctx->skin_h = 0;
     if (!rgba_linear) return NB_OK;                   // back to the 1 x 1 white skin
-    const size_t bytes = (size_t)tw * th * 4 * sizeof(float);
-    NB_HIP(ctx, hipMalloc((void **)&ctx->skin, bytes));
-    NB_HIP(ctx, hipMemcpyAsync(ctx->skin, rgba_linear, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const size_t floats = (size_t)tw * th * 4;
+    NB_HIP(ctx, ctx->skin.reserve(floats));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->skin.p, rgba_linear, floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->skin_w = tw, ctx->skin_h = th;
     return NB_OK;
@@ -1373,9 +1389,9 @@ NB_EXPORT int nb_eyes_colour(nb_ctx *ctx, uint32_t first, uint32_t count, const 
 {
     static const ViewForm f = {"nb_eyes_colour", false, 0xCu, kNoColour, true, nullptr};
     return ctx_eyes(ctx, f, first, count, up_xyz, cp16, width, flags, ids, depth, rgba, bgra8, [&]() -> int {
-        NB_HIP(ctx, nbk::launch_eyes_colour(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
-                                            ctx->skin_w, ctx->skin_h, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
-                                            rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        NB_HIP(ctx, nbk::launch_eyes_colour(ctx->n, first, count, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width, flags, ctx->skin.p,
+                                            ctx->skin_w, ctx->skin_h, ids ? ctx->eye_ids.p : nullptr, depth ? ctx->eye_depth.p : nullptr,
+                                            rgba ? (float *)ctx->eye_rgba.p : nullptr, bgra8 ? ctx->eye_bgra.p : nullptr, ctx->stream));
         return NB_OK;
     });
 }
@@ -1398,9 +1414,9 @@ NB_EXPORT int nb_eyes_msaa(nb_ctx *ctx, uint32_t first, uint32_t count, const fl
 {
     static const ViewForm f = {"nb_eyes_msaa", true, 0xFu, kNoOutputs8, true, nullptr};
     return ctx_eyes(ctx, f, first, count, up_xyz, cp16, width, flags, ids8, depth8, rgba, bgra8, [&]() -> int {
-        NB_HIP(ctx, nbk::launch_eyes_msaa(ctx->n, first, count, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->skin,
-                                          ctx->skin_w, ctx->skin_h, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
-                                          rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        NB_HIP(ctx, nbk::launch_eyes_msaa(ctx->n, first, count, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width, flags, ctx->skin.p,
+                                          ctx->skin_w, ctx->skin_h, ids8 ? ctx->eye_ids.p : nullptr, depth8 ? ctx->eye_depth.p : nullptr,
+                                          rgba ? (float *)ctx->eye_rgba.p : nullptr, bgra8 ? ctx->eye_bgra.p : nullptr, ctx->stream));
         return NB_OK;
     });
 }
@@ -1413,21 +1429,19 @@ NB_EXPORT size_t nb_frame_scratch_bytes(uint32_t width, uint32_t height)
 
 NB_EXPORT int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_xyz, const float *up_xyz, const float *cp16, float *out16)
 {
-    if (!ctx) {
-        g_tls_error = "nb_camera_at: ctx is null";
-        return NB_ERR_INVALID;
-    }
+    const int rc = ctx_check(ctx, "nb_camera_at");
+    if (rc != NB_OK) return rc;
     if (!eye_xyz || !dir_xyz || !up_xyz || !cp16 || !out16) {
         ctx->err = "nb_camera_at: null argument";
         return NB_ERR_INVALID;
     }
-    NB_HIP(ctx, first_use(&ctx->frame_cam, 6 * sizeof(float4)));
+    NB_HIP(ctx, ctx->frame_cam.reserve(6));
     // the eye and the direction as the 16-byte records the camera kernel reads, behind the camera's own four
     const float rec[8] = {eye_xyz[0], eye_xyz[1], eye_xyz[2], 0.0f, dir_xyz[0], dir_xyz[1], dir_xyz[2], 0.0f};
-    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam + 4, rec, sizeof(rec), hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam.p + 4, rec, sizeof(rec), hipMemcpyHostToDevice, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (rec is on the stack)
-    NB_HIP(ctx, nbk::launch_cameras(1, ctx->frame_cam + 4, ctx->frame_cam + 5, up_xyz, cp16, ctx->frame_cam, ctx->stream));
-    NB_HIP(ctx, hipMemcpyAsync(out16, ctx->frame_cam, 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, nbk::launch_cameras(1, ctx->frame_cam.p + 4, ctx->frame_cam.p + 5, up_xyz, cp16, ctx->frame_cam.p, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(out16, ctx->frame_cam.p, 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
 }
@@ -1435,9 +1449,9 @@ NB_EXPORT int nb_camera_at(nb_ctx *ctx, const float *eye_xyz, const float *dir_x
 // the frame's own staging: the key plane (one per context, grown on demand) and the camera
 static int stage_frame(nb_ctx *ctx, const float *cam16, size_t keys)
 {
-    NB_HIP(ctx, grow_row(&ctx->frame_keys, &ctx->frame_keys_cap, keys, sizeof(uint64_t)));
-    NB_HIP(ctx, first_use(&ctx->frame_cam, 6 * sizeof(float4)));
-    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, ctx->frame_keys.reserve(keys));
+    NB_HIP(ctx, ctx->frame_cam.reserve(6));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->frame_cam.p, cam16, 16 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     return NB_OK;
 }
 
@@ -1446,10 +1460,8 @@ template <typename Launch>
 static int ctx_frame(nb_ctx *ctx, const ViewForm &f, const float *cam16, uint32_t width, uint32_t height, uint32_t flags, uint32_t *ids,
                      float *depth, float *rgba, uint32_t *bgra8, Launch launch)
 {
-    if (!ctx) {
-        g_tls_error = std::string(f.fn) + ": ctx is null";
-        return NB_ERR_INVALID;
-    }
+    int rc = ctx_check(ctx, f.fn);
+    if (rc != NB_OK) return rc;
     if (!cam16) {
         ctx->err = std::string(f.fn) + ": null argument";
         return NB_ERR_INVALID;
@@ -1457,13 +1469,10 @@ static int ctx_frame(nb_ctx *ctx, const ViewForm &f, const float *cam16, uint32_
     const size_t cells = (size_t)width * height, words = f.msaa ? cells * NB_EYES_SAMPLES : cells;
     const ByteRange in[1] = {{cam16, 16 * sizeof(float)}};
     const ByteRange out[4] = {{ids, words * 4u}, {depth, words * 4u}, {rgba, cells * 16u}, {bgra8, cells * 4u}};
-    int rc = frame_extent_check(f.fn, width, height, f.msaa, flags, &ctx->err);
+    rc = frame_extent_check(f.fn, width, height, f.msaa, flags, &ctx->err);
     if (rc == NB_OK) rc = outputs_check(f.fn, out, f.need, f.none_msg, f.aligned4, in, 1, kFrameAlias, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, f.fn, "");
     if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = std::string(f.fn) + ": no state uploaded";
-        return NB_ERR_STATE;
-    }
     rc = grow_rows(ctx, ids, depth, rgba, bgra8, words, cells);
     if (rc == NB_OK) rc = stage_frame(ctx, cam16, words);
     if (rc == NB_OK) rc = stage_matrices(ctx, 0, 0, nullptr, nullptr);
@@ -1478,9 +1487,9 @@ NB_EXPORT int nb_frame(nb_ctx *ctx, const float *cam16, uint32_t width, uint32_t
 {
     static const ViewForm f = {"nb_frame", false, 0xFu, kNoOutputs, true, nullptr};
     return ctx_frame(ctx, f, cam16, width, height, flags, ids, depth, rgba, bgra8, [&]() -> int {
-        NB_HIP(ctx, nbk::launch_frame(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
-                                      ctx->skin_h, ctx->frame_keys, ids ? ctx->eye_ids : nullptr, depth ? ctx->eye_depth : nullptr,
-                                      rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        NB_HIP(ctx, nbk::launch_frame(ctx->n, (const float *)ctx->frame_cam.p, (const float *)ctx->inst.p, width, height, ctx->skin.p, ctx->skin_w,
+                                      ctx->skin_h, ctx->frame_keys.p, ids ? ctx->eye_ids.p : nullptr, depth ? ctx->eye_depth.p : nullptr,
+                                      rgba ? (float *)ctx->eye_rgba.p : nullptr, bgra8 ? ctx->eye_bgra.p : nullptr, ctx->stream));
         return NB_OK;
     });
 }
@@ -1511,19 +1520,17 @@ NB_EXPORT int nb_frame_msaa(nb_ctx *ctx, const float *cam16, uint32_t width, uin
 {
     static const ViewForm f = {"nb_frame_msaa", true, 0xFu, kNoOutputs8, true, nullptr};
     return ctx_frame(ctx, f, cam16, width, height, flags, ids8, depth8, rgba, bgra8, [&]() -> int {
-        NB_HIP(ctx, nbk::launch_frame_msaa(ctx->n, (const float *)ctx->frame_cam, (const float *)ctx->inst, width, height, ctx->skin, ctx->skin_w,
-                                           ctx->skin_h, ctx->frame_keys, ids8 ? ctx->eye_ids : nullptr, depth8 ? ctx->eye_depth : nullptr,
-                                           rgba ? ctx->eye_rgba : nullptr, bgra8 ? ctx->eye_bgra : nullptr, ctx->stream));
+        NB_HIP(ctx, nbk::launch_frame_msaa(ctx->n, (const float *)ctx->frame_cam.p, (const float *)ctx->inst.p, width, height, ctx->skin.p, ctx->skin_w,
+                                           ctx->skin_h, ctx->frame_keys.p, ids8 ? ctx->eye_ids.p : nullptr, depth8 ? ctx->eye_depth.p : nullptr,
+                                           rgba ? (float *)ctx->eye_rgba.p : nullptr, bgra8 ? ctx->eye_bgra.p : nullptr, ctx->stream));
         return NB_OK;
     });
 }
 
 NB_EXPORT int nb_sync(nb_ctx *ctx)
 {
-    if (!ctx) {
-        g_tls_error = "nb_sync: ctx is null";
-        return NB_ERR_INVALID;
-    }
+    const int rc = ctx_check(ctx, "nb_sync");
+    if (rc != NB_OK) return rc;
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return check_status(&ctx->status, &ctx->err);
 }
@@ -1532,33 +1539,15 @@ NB_EXPORT uint64_t nb_steps_done(const nb_ctx *ctx) { return ctx ? ctx->steps : 
 
 NB_EXPORT int nb_download(nb_ctx *ctx, float *pos_xyz, float *vel_xyz, float *inst_16n)
 {
-    if (!ctx) {
-        g_tls_error = "nb_download: ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (!ctx->uploaded) {
-        ctx->err = "nb_download: no state uploaded";
-        return NB_ERR_STATE;
-    }
+    int rc = ctx_check(ctx, "nb_download", "");
+    if (rc != NB_OK) return rc;
     const size_t bytes = (size_t)ctx->n * 3 * sizeof(float);
     if (ctx->n <= kRoundtripMax && (pos_xyz || vel_xyz || inst_16n)) {  // [matrices 16n | positions 3n | velocities 3n], one copy, one wait
-        int rc = ensure_xfer(ctx);
+        rc = ensure_xfer(ctx);
         if (rc != NB_OK) return rc;
         const size_t n = ctx->n;
-        const bool zero_copy = small_set_zero_copy(ctx->n);
-        float *const dst = zero_copy ? ctx->hxfer_dev : ctx->xfer;
-        // the sticky status word of this context's block-chain launches comes home in the same buffer: no second wait
-        const bool with_status = ctx->status.dirty && ctx->status.w;
-        const nbk::ExportDone done = export_done(ctx, small_set_poll(ctx->n));
-        NB_HIP(ctx, nbk::launch_export(ctx->n, ctx->pos[ctx->cur], ctx->vel, inst_16n ? (float4 *)dst : nullptr,
-                                       pos_xyz ? dst + 16 * n : nullptr, vel_xyz ? dst + 19 * n : nullptr,
-                                       with_status ? ctx->status.w : nullptr, with_status ? (uint32_t *)(dst + 22 * n) : nullptr, ctx->stream,
-                                       overrides().inst_device_libm.on() ? 1u : 0u, done));
-        if (!zero_copy) {
-            const size_t lo = inst_16n ? 0 : (pos_xyz ? 16 * n : 19 * n), hi = with_status ? 22 * n + 1 : vel_xyz ? 22 * n : (pos_xyz ? 19 * n : 16 * n);
-            NB_HIP(ctx, hipMemcpyAsync(ctx->hxfer + lo, ctx->xfer + lo, (hi - lo) * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        rc = wait_export(ctx, done);
+        bool with_status = false;
+        rc = small_export(ctx, inst_16n != nullptr, pos_xyz != nullptr, vel_xyz != nullptr, &with_status);
         if (rc != NB_OK) return rc;
         if (inst_16n) std::memcpy(inst_16n, ctx->hxfer, n * 16 * sizeof(float));
         if (pos_xyz) std::memcpy(pos_xyz, ctx->hxfer + 16 * n, bytes);
@@ -1566,19 +1555,18 @@ NB_EXPORT int nb_download(nb_ctx *ctx, float *pos_xyz, float *vel_xyz, float *in
         return status_from_tail(ctx, with_status);
     }
     if (pos_xyz) {
-        NB_HIP(ctx, nbk::launch_unpack(ctx->n, ctx->pos[ctx->cur], ctx->stage, ctx->stream));
-        NB_HIP(ctx, hipMemcpyAsync(pos_xyz, ctx->stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        NB_HIP(ctx, nbk::launch_unpack(ctx->n, ctx->pos[ctx->cur].p, ctx->stage.p, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(pos_xyz, ctx->stage.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
         NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (vel_xyz) {
-        NB_HIP(ctx, nbk::launch_unpack(ctx->n, ctx->vel, ctx->stage, ctx->stream));
-        NB_HIP(ctx, hipMemcpyAsync(vel_xyz, ctx->stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        NB_HIP(ctx, nbk::launch_unpack(ctx->n, ctx->vel.p, ctx->stage.p, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(vel_xyz, ctx->stage.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
         NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (inst_16n) {
-        NB_HIP(ctx, first_use(&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
-        NB_HIP(ctx, nbk::launch_instances(ctx->n, ctx->pos[ctx->cur], ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
-        NB_HIP(ctx, hipMemcpyAsync(inst_16n, ctx->inst, (size_t)ctx->n * 16 * sizeof(float), hipMemcpyDeviceToHost,
+        NB_HIP(ctx, launch_matrices(ctx->n, ctx->pos[ctx->cur].p, ctx->vel.p, &ctx->inst, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(inst_16n, ctx->inst.p, (size_t)ctx->n * 16 * sizeof(float), hipMemcpyDeviceToHost,
                                    ctx->stream));
         NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }

@@ -96,30 +96,20 @@ int update_roundtrip(nb_ctx *c, int kind, const nb_boids_params *bp, const float
     const size_t n = c->n, xyz = 3 * sizeof(float);
     int rc = ensure_xfer(c);
     if (rc != NB_OK) return rc;
-    std::memcpy(c->hxfer, pos, n * xyz);
-    std::memcpy(c->hxfer + 3 * n, vel, n * xyz);
     c->cur = 0;
     c->uploaded = true;
     c->steps = 0;
     // the pack / unpack kernels read and write the pinned host buffer THROUGH THE BUS themselves: the two DMA operations of a
     // staged copy cost more in fixed latency than these few kilobytes cost in bandwidth (kZeroCopyMax)
-    const bool zero_copy = small_set_zero_copy(c->n);
-    float *const in = zero_copy ? c->hxfer_dev : c->xfer, *const out = zero_copy ? c->hxfer_dev : c->xfer;
-    if (!zero_copy) NB_HIP(c, hipMemcpyAsync(c->xfer, c->hxfer, 2 * n * xyz, hipMemcpyHostToDevice, c->stream));
-    NB_HIP(c, nbk::launch_import(c->n, in, in + 3 * n, c->pos[0], c->vel, c->stream));
+    rc = small_import(c, pos, vel);  // (no wait between the import and the step)
+    if (rc != NB_OK) return rc;
     if (kind == 2) c->steps = step;  // the random walk's stream is indexed by the step counter
     rc = kind == 2 ? nb_step_random(c, 1, seed) : kind == 1 ? nb_step_boids(c, 1, bp) : nb_step(c, 1);
     if (rc != NB_OK) return rc;
-    // the sticky status word of this context's block-chain launches comes home in the same buffer: no second wait per frame
-    const bool with_status = c->status.dirty && c->status.w;
-    const nbk::ExportDone done = export_done(c, small_set_poll(c->n));
-    NB_HIP(c, nbk::launch_export(c->n, c->pos[c->cur], c->vel, (float4 *)out, out + 16 * n, out + 19 * n, with_status ? c->status.w : nullptr,
-                                 with_status ? (uint32_t *)(out + 22 * n) : nullptr, c->stream, overrides().inst_device_libm.on() ? 1u : 0u, done));
-    if (!zero_copy)
-        NB_HIP(c, hipMemcpyAsync(c->hxfer, c->xfer, (n * 22 + (with_status ? 1 : 0)) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    rc = wait_export(c, done);
-    if (rc != NB_OK) return rc;
-    rc = status_from_tail(c, with_status);
+    bool with_status = false;
+    rc = small_export(c, true, true, true, &with_status);
+    // a failure is reported before anything is copied out: the caller's arrays are also this call's inputs
+    if (rc == NB_OK) rc = status_from_tail(c, with_status);
     if (rc != NB_OK) return rc;
     std::memcpy(inst_out, c->hxfer, count * 16 * sizeof(float));
     std::memcpy(pos_out, c->hxfer + 16 * n, count * xyz);

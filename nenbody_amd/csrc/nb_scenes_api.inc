@@ -131,9 +131,9 @@ struct nb_scenes {
     uint32_t scenes = 0, n = 0;
     nb_params p{};
     hipStream_t stream = nullptr;
-    float4 *pos = nullptr, *vel = nullptr;   // scenes * n records each, stepped in place
-    float *stage = nullptr;                  // 6 * scenes * n floats: the stride-3 arrays of an upload or a download
-    float4 *inst = nullptr;                  // 4 * scenes * n records, allocated on first use
+    DeviceBuffer<float4> pos, vel;           // scenes * n records each, stepped in place
+    DeviceBuffer<float> stage;               // 6 * scenes * n floats: the stride-3 arrays of an upload or a download
+    DeviceBuffer<float4> inst;               // 4 * scenes * n records, allocated on first use
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
@@ -144,22 +144,19 @@ NB_EXPORT const char *nb_scenes_last_error(const nb_scenes *ctx) { return ctx ? 
 NB_EXPORT void nb_scenes_destroy(nb_scenes *ctx)
 {
     if (!ctx) return;
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->pos) (void)hipFree(ctx->pos);
-    if (ctx->vel) (void)hipFree(ctx->vel);
-    if (ctx->stage) (void)hipFree(ctx->stage);
-    if (ctx->inst) (void)hipFree(ctx->inst);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t stream = ctx->stream;
+    if (stream) (void)hipStreamSynchronize(stream);
+    delete ctx;  // frees its buffers: behind the wait, in front of the stream's end
+    if (stream) (void)hipStreamDestroy(stream);
 }
 
 static int scenes_create_impl(nb_scenes *c)
 {
     const size_t records = (size_t)c->scenes * c->n;
     NB_HIP(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    NB_HIP(c, hipMalloc((void **)&c->pos, records * sizeof(float4)));
-    NB_HIP(c, hipMalloc((void **)&c->vel, records * sizeof(float4)));
-    NB_HIP(c, hipMalloc((void **)&c->stage, records * 6 * sizeof(float)));
+    NB_HIP(c, c->pos.reserve(records));
+    NB_HIP(c, c->vel.reserve(records));
+    NB_HIP(c, c->stage.reserve(records * 6));
     return NB_OK;
 }
 
@@ -192,32 +189,18 @@ NB_EXPORT int nb_scenes_create(uint32_t scenes, uint32_t n, const nb_params *par
     return NB_OK;
 }
 
-// a context entry's first two checks: the context is there, and (where `state`) it holds a state
-static int scenes_ctx_check(nb_scenes *ctx, const char *fn, bool state)
-{
-    if (!ctx) {
-        g_tls_error = std::string(fn) + ": ctx is null";
-        return NB_ERR_INVALID;
-    }
-    if (state && !ctx->uploaded) {
-        ctx->err = std::string(fn) + ": no state uploaded (call nb_scenes_upload first)";
-        return NB_ERR_STATE;
-    }
-    return NB_OK;
-}
-
 NB_EXPORT int nb_scenes_upload(nb_scenes *ctx, const float *pos_xyz, const float *vel_xyz)
 {
-    int rc = scenes_ctx_check(ctx, "nb_scenes_upload", false);
+    int rc = ctx_check(ctx, "nb_scenes_upload");
     if (rc != NB_OK) return rc;
     if (!pos_xyz || !vel_xyz) {
         ctx->err = "nb_scenes_upload: null array";
         return NB_ERR_INVALID;
     }
     const size_t records = (size_t)ctx->scenes * ctx->n, bytes = records * 3 * sizeof(float);
-    NB_HIP(ctx, hipMemcpyAsync(ctx->stage, pos_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    NB_HIP(ctx, hipMemcpyAsync(ctx->stage + 3 * records, vel_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    NB_HIP(ctx, nbk::launch_import((uint32_t)records, ctx->stage, ctx->stage + 3 * records, ctx->pos, ctx->vel, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->stage.p, pos_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->stage.p + 3 * records, vel_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, nbk::launch_import((uint32_t)records, ctx->stage.p, ctx->stage.p + 3 * records, ctx->pos.p, ctx->vel.p, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host arrays are not retained
     ctx->uploaded = true;
     ctx->steps = 0;
@@ -226,10 +209,10 @@ NB_EXPORT int nb_scenes_upload(nb_scenes *ctx, const float *pos_xyz, const float
 
 NB_EXPORT int nb_scenes_step(nb_scenes *ctx, uint32_t k)
 {
-    int rc = scenes_ctx_check(ctx, "nb_scenes_step", true);
+    int rc = ctx_check(ctx, "nb_scenes_step", kCallScenesUpload);
     if (rc != NB_OK) return rc;
     nbk::ScenesNbodyArgs a;
-    rc = scenes_nbody_args(ctx->p, ctx->scenes, ctx->n, k, ctx->pos, ctx->vel, &a, &ctx->err);
+    rc = scenes_nbody_args(ctx->p, ctx->scenes, ctx->n, k, ctx->pos.p, ctx->vel.p, &a, &ctx->err);
     if (rc != NB_OK) return rc;
     if (k == 0) return NB_OK;
     RoctxRange range("nb_scenes_step");
@@ -241,40 +224,39 @@ NB_EXPORT int nb_scenes_step(nb_scenes *ctx, uint32_t k)
 NB_EXPORT int nb_scenes_step_boids(nb_scenes *ctx, uint32_t k, const nb_boids_params *params)
 {
     static const char fn[] = "nb_scenes_step_boids";
-    int rc = scenes_ctx_check(ctx, fn, false);
+    int rc = ctx_check(ctx, fn);
     if (rc != NB_OK) return rc;
     const nb_boids_params p = boids_params_or_default(params);
     rc = scenes_boids_params_check(fn, p, &ctx->err);
-    if (rc == NB_OK) rc = scenes_ctx_check(ctx, fn, true);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
     nbk::BoidsArgs c;
     uint32_t tile = 0;
     if (rc == NB_OK) rc = make_boids_args(p, ctx->n, 0, ctx->n, &c, &tile, &ctx->err);
     if (rc != NB_OK) return rc;
     if (k == 0) return NB_OK;
     RoctxRange range(fn);
-    NB_HIP(ctx, nbk::launch_scenes_boids(c, ctx->pos, ctx->vel, ctx->scenes, k, ctx->stream));
+    NB_HIP(ctx, nbk::launch_scenes_boids(c, ctx->pos.p, ctx->vel.p, ctx->scenes, k, ctx->stream));
     ctx->steps += k;
     return NB_OK;
 }
 
 NB_EXPORT int nb_scenes_device_state(nb_scenes *ctx, const void **pos_rec, const void **vel_rec, const void **inst_16n)
 {
-    int rc = scenes_ctx_check(ctx, "nb_scenes_device_state", true);
+    int rc = ctx_check(ctx, "nb_scenes_device_state", kCallScenesUpload);
     if (rc != NB_OK) return rc;
     const size_t records = (size_t)ctx->scenes * ctx->n;
     if (inst_16n) {
-        NB_HIP(ctx, first_use(&ctx->inst, records * 16 * sizeof(float)));
-        NB_HIP(ctx, nbk::launch_instances((uint32_t)records, ctx->pos, ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
-        *inst_16n = ctx->inst;
+        NB_HIP(ctx, launch_matrices((uint32_t)records, ctx->pos.p, ctx->vel.p, &ctx->inst, ctx->stream));
+        *inst_16n = ctx->inst.p;
     }
-    if (pos_rec) *pos_rec = ctx->pos;
-    if (vel_rec) *vel_rec = ctx->vel;
+    if (pos_rec) *pos_rec = ctx->pos.p;
+    if (vel_rec) *vel_rec = ctx->vel.p;
     return NB_OK;
 }
 
 NB_EXPORT int nb_scenes_sync(nb_scenes *ctx)
 {
-    int rc = scenes_ctx_check(ctx, "nb_scenes_sync", false);
+    int rc = ctx_check(ctx, "nb_scenes_sync");
     if (rc != NB_OK) return rc;
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
@@ -285,27 +267,26 @@ NB_EXPORT uint64_t nb_scenes_steps(const nb_scenes *ctx) { return ctx ? ctx->ste
 NB_EXPORT int nb_scenes_download(nb_scenes *ctx, float *pos_xyz, float *vel_xyz, float *inst_16)
 {
     static const char fn[] = "nb_scenes_download";
-    int rc = scenes_ctx_check(ctx, fn, false);
+    int rc = ctx_check(ctx, fn);
     if (rc != NB_OK) return rc;
     if (!pos_xyz && !vel_xyz && !inst_16) {
         ctx->err = std::string(fn) + ": pos_xyz, vel_xyz and inst_16 are all NULL";
         return NB_ERR_INVALID;
     }
-    rc = scenes_ctx_check(ctx, fn, true);
+    rc = ctx_check(ctx, fn, kCallScenesUpload);
     if (rc != NB_OK) return rc;
     const size_t records = (size_t)ctx->scenes * ctx->n, bytes = records * 3 * sizeof(float);
     if (pos_xyz) {
-        NB_HIP(ctx, nbk::launch_unpack((uint32_t)records, ctx->pos, ctx->stage, ctx->stream));
-        NB_HIP(ctx, hipMemcpyAsync(pos_xyz, ctx->stage, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        NB_HIP(ctx, nbk::launch_unpack((uint32_t)records, ctx->pos.p, ctx->stage.p, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(pos_xyz, ctx->stage.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (vel_xyz) {
-        NB_HIP(ctx, nbk::launch_unpack((uint32_t)records, ctx->vel, ctx->stage + 3 * records, ctx->stream));
-        NB_HIP(ctx, hipMemcpyAsync(vel_xyz, ctx->stage + 3 * records, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        NB_HIP(ctx, nbk::launch_unpack((uint32_t)records, ctx->vel.p, ctx->stage.p + 3 * records, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(vel_xyz, ctx->stage.p + 3 * records, bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (inst_16) {
-        NB_HIP(ctx, first_use(&ctx->inst, records * 16 * sizeof(float)));
-        NB_HIP(ctx, nbk::launch_instances((uint32_t)records, ctx->pos, ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
-        NB_HIP(ctx, hipMemcpyAsync(inst_16, ctx->inst, records * 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        NB_HIP(ctx, launch_matrices((uint32_t)records, ctx->pos.p, ctx->vel.p, &ctx->inst, ctx->stream));
+        NB_HIP(ctx, hipMemcpyAsync(inst_16, ctx->inst.p, records * 16 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     }
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;

@@ -377,9 +377,9 @@ NB_EXPORT int nb_diag_step_clock(const nb_params *params, uint32_t n, double sec
             // the stamped step: the same launch with StepArgs::stamps set
             if (rc == NB_OK) e = hipEventRecord(e0, c->stream);
             if (rc == NB_OK && e == hipSuccess) {
-                nbk::StepArgs a = step_args(p, pl, n, 0, n, c->pos[c->cur], c->pos[c->cur ^ 1], c->vel, c->scratch);
+                nbk::StepArgs a = step_args(p, pl, n, 0, n, c->pos[c->cur].p, c->pos[c->cur ^ 1].p, c->vel.p, c->scratch.p);
                 a.stamps = stamps;
-                e = launch_planned(pl, a, c->scratch, nullptr, c->stream);  // (no stamped form reports through the status word)
+                e = launch_planned(pl, a, c->scratch.p, nullptr, c->stream);  // (no stamped form reports through the status word)
             }
             if (rc == NB_OK && e == hipSuccess) e = hipEventRecord(e1, c->stream);
             if (rc == NB_OK && e == hipSuccess) e = hipEventSynchronize(e1);

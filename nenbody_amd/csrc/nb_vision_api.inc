@@ -2,7 +2,7 @@
 // eye sees its members (nb_seen_located_launch, nb_eyes_located), and the two steps over what each body sees: boids over the seen
 // sets (nb_launch_boids_seen_step, nb_step_boids_seen) and gravity over the located ones (nb_nbody_located_step_launch,
 // nb_step_nbody_located).  Included by nb_api.hip behind the eye entries, whose checks (eyes_range_check, outputs_check) and staging
-// (grow_row, grow_rows, stage_matrices, first_use) it uses.  The context's entries are one chain -- eye rows, seen sets, located
+// (grow_rows, stage_matrices, launch_matrices) it uses.  The context's entries are one chain -- eye rows, seen sets, located
 // sets -- behind one row-entry body and one step body; every check runs before anything touches the device.
 
 static const char kNoSeenOutputs[] = ": seen_count, seen_ids, seen_depth and seen_cols are all NULL";
@@ -123,12 +123,12 @@ static int grow_vision(nb_ctx *ctx, const VisionRows &r, size_t eyes, size_t cel
 {
     const int rc = grow_rows(ctx, ctx, r.depth ? ctx : nullptr, nullptr, nullptr, cells, cells);
     if (rc != NB_OK) return rc;
-    NB_HIP(ctx, grow_row(&ctx->seen_count, &ctx->seen_count_cap, eyes, sizeof(uint32_t)));
-    NB_HIP(ctx, grow_row(&ctx->seen_ids, &ctx->seen_ids_cap, cells, sizeof(uint32_t)));
-    if (r.depth) NB_HIP(ctx, grow_row(&ctx->seen_depth, &ctx->seen_depth_cap, cells, sizeof(float)));
-    if (r.cols) NB_HIP(ctx, grow_row(&ctx->seen_cols, &ctx->seen_cols_cap, cells, sizeof(uint32_t)));
-    if (r.col) NB_HIP(ctx, grow_row(&ctx->loc_col, &ctx->loc_col_cap, cells, sizeof(uint32_t)));
-    if (r.located) NB_HIP(ctx, grow_row(&ctx->loc_rel, &ctx->loc_rel_cap, cells, sizeof(float4)));
+    NB_HIP(ctx, ctx->seen_count.reserve(eyes));
+    NB_HIP(ctx, ctx->seen_ids.reserve(cells));
+    if (r.depth) NB_HIP(ctx, ctx->seen_depth.reserve(cells));
+    if (r.cols) NB_HIP(ctx, ctx->seen_cols.reserve(cells));
+    if (r.col) NB_HIP(ctx, ctx->loc_col.reserve(cells));
+    if (r.located) NB_HIP(ctx, ctx->loc_rel.reserve(cells));
     return NB_OK;
 }
 
@@ -137,13 +137,14 @@ static int grow_vision(nb_ctx *ctx, const VisionRows &r, size_t eyes, size_t cel
 static int vision_chain(nb_ctx *ctx, const VisionRows &r, uint32_t first, uint32_t cnt, uint32_t width, uint32_t flags, const float *up_xyz,
                         const float *cp16)
 {
-    NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, cnt, (const float *)ctx->cams, (const float *)ctx->inst, width, flags, ctx->eye_ids,
-                                 r.depth ? ctx->eye_depth : nullptr, ctx->stream));
-    NB_HIP(ctx, nbk::launch_seen(cnt, width, ctx->eye_ids, r.depth ? ctx->eye_depth : nullptr, ctx->seen_count, ctx->seen_ids,
-                                 r.depth ? ctx->seen_depth : nullptr, r.cols ? ctx->seen_cols : nullptr, ctx->stream));
+    NB_HIP(ctx, nbk::launch_eyes(ctx->n, first, cnt, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width, flags, ctx->eye_ids.p,
+                                 r.depth ? ctx->eye_depth.p : nullptr, ctx->stream));
+    NB_HIP(ctx, nbk::launch_seen(cnt, width, ctx->eye_ids.p, r.depth ? ctx->eye_depth.p : nullptr, ctx->seen_count.p, ctx->seen_ids.p,
+                                 r.depth ? ctx->seen_depth.p : nullptr, r.cols ? ctx->seen_cols.p : nullptr, ctx->stream));
     if (r.located)
-        NB_HIP(ctx, nbk::launch_located(located_args(cnt, width, ctx->eye_ids, ctx->eye_depth, ctx->seen_count, ctx->seen_ids, ctx->seen_depth,
-                                                     ctx->vel + first, up_xyz, cp16, r.col ? ctx->loc_col : nullptr, ctx->loc_rel),
+        NB_HIP(ctx, nbk::launch_located(located_args(cnt, width, ctx->eye_ids.p, ctx->eye_depth.p, ctx->seen_count.p, ctx->seen_ids.p,
+                                                     ctx->seen_depth.p, ctx->vel.p + first, up_xyz, cp16, r.col ? ctx->loc_col.p : nullptr,
+                                                     ctx->loc_rel.p),
                                         ctx->stream));
     return NB_OK;
 }
@@ -153,10 +154,8 @@ static int vision_chain(nb_ctx *ctx, const VisionRows &r, uint32_t first, uint32
 static int ctx_vision_rows(nb_ctx *ctx, const char *fn, bool located, uint32_t first, uint32_t count, const float *up_xyz, const float *cp16,
                            uint32_t width, uint32_t flags, void *const (&host)[6])
 {
-    if (!ctx) {
-        g_tls_error = std::string(fn) + ": ctx is null";
-        return NB_ERR_INVALID;
-    }
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
     if (!up_xyz || !cp16) {
         ctx->err = std::string(fn) + ": null argument";
         return NB_ERR_INVALID;
@@ -165,21 +164,18 @@ static int ctx_vision_rows(nb_ctx *ctx, const char *fn, bool located, uint32_t f
     const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
     const ByteRange out[6] = {{host[0], (size_t)count * 4u}, {host[1], cells * 4u}, {host[2], cells * 4u},
                               {host[3], cells * 4u},         {host[4], cells * 4u}, {host[5], cells * 16u}};
-    int rc = eyes_range_check(fn, ctx->n, first, count, width, false, flags, &ctx->err);
+    rc = eyes_range_check(fn, ctx->n, first, count, width, false, flags, &ctx->err);
     if (rc == NB_OK && located) rc = located_cp_check(fn, cp16, &ctx->err);
     if (rc == NB_OK) rc = outputs_check(fn, out, 0x3Fu, located ? kNoLocatedOutputs : kNoSeenOutputs, false, in, 2, kSeenAlias, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, "");
     if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = std::string(fn) + ": no state uploaded";
-        return NB_ERR_STATE;
-    }
     if (count == 0) return NB_OK;
     const VisionRows r = {located || host[2], host[3] != nullptr, located, host[4] != nullptr};
     rc = grow_vision(ctx, r, count, cells);
     if (rc == NB_OK) rc = stage_matrices(ctx, first, count, up_xyz, cp16);
     if (rc == NB_OK) rc = vision_chain(ctx, r, first, count, width, flags, up_xyz, cp16);
     if (rc != NB_OK) return rc;
-    const void *const rows[6] = {ctx->seen_count, ctx->seen_ids, ctx->seen_depth, ctx->seen_cols, ctx->loc_col, ctx->loc_rel};
+    const void *const rows[6] = {ctx->seen_count.p, ctx->seen_ids.p, ctx->seen_depth.p, ctx->seen_cols.p, ctx->loc_col.p, ctx->loc_rel.p};
     for (int a = 0; a < 6; ++a)
         if (host[a]) NB_HIP(ctx, hipMemcpyAsync(host[a], rows[a], out[a].bytes, hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -309,44 +305,35 @@ template <typename Prepare, typename Fold>
 static int ctx_vision_step(nb_ctx *ctx, const VisionStep &f, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width, uint32_t batch,
                            Prepare prepare, Fold fold)
 {
-    if (!ctx) {
-        g_tls_error = std::string(f.fn) + ": ctx is null";
-        return NB_ERR_INVALID;
-    }
+    int rc = ctx_check(ctx, f.fn);
+    if (rc != NB_OK) return rc;
     if (!up_xyz || !cp16) {
         ctx->err = std::string(f.fn) + ": null argument";
         return NB_ERR_INVALID;
     }
-    int rc = eyes_range_check(f.fn, ctx->n, 0, ctx->n, width, false, 0, &ctx->err);
+    rc = eyes_range_check(f.fn, ctx->n, 0, ctx->n, width, false, 0, &ctx->err);
     if (rc == NB_OK && f.rows.located) rc = located_cp_check(f.fn, cp16, &ctx->err);
-    if (rc != NB_OK) return rc;
-    if (!ctx->uploaded) {
-        ctx->err = std::string(f.fn) + ": no state uploaded (call nb_upload first)";
-        return NB_ERR_STATE;
-    }
-    rc = prepare();
+    if (rc == NB_OK) rc = ctx_check(ctx, f.fn, kCallUpload);
+    if (rc == NB_OK) rc = prepare();
     if (rc != NB_OK) return rc;
     if (k == 0) return NB_OK;
     const uint32_t per = std::min(batch ? batch : vision_default_batch(ctx->n, width, f.col_bytes), ctx->n);
     rc = grow_vision(ctx, f.rows, per, (size_t)per * width);
     if (rc != NB_OK) return rc;
-    NB_HIP(ctx, first_use(&ctx->vel_alt, (size_t)ctx->n * sizeof(float4)));
-    NB_HIP(ctx, first_use(&ctx->cams, (size_t)ctx->n * 16 * sizeof(float)));
-    NB_HIP(ctx, first_use(&ctx->inst, (size_t)ctx->n * 16 * sizeof(float)));
+    NB_HIP(ctx, ctx->vel_alt.reserve(ctx->n));
+    NB_HIP(ctx, ctx->cams.reserve((size_t)ctx->n * 4));
     RoctxRange range(f.fn);
     for (uint32_t s = 0; s < k; ++s) {
-        const float4 *pos = ctx->pos[ctx->cur];
-        NB_HIP(ctx, nbk::launch_instances(ctx->n, pos, ctx->vel, ctx->inst, ctx->stream, overrides().inst_device_libm.on() ? 1u : 0u));
+        const float4 *pos = ctx->pos[ctx->cur].p;
+        NB_HIP(ctx, launch_matrices(ctx->n, pos, ctx->vel.p, &ctx->inst, ctx->stream));
         for (uint32_t b0 = 0; b0 < ctx->n; b0 += per) {
             const uint32_t cnt = std::min(per, ctx->n - b0);
-            NB_HIP(ctx, nbk::launch_cameras(cnt, pos + b0, ctx->vel + b0, up_xyz, cp16, ctx->cams, ctx->stream));
+            NB_HIP(ctx, nbk::launch_cameras(cnt, pos + b0, ctx->vel.p + b0, up_xyz, cp16, ctx->cams.p, ctx->stream));
             rc = vision_chain(ctx, f.rows, b0, cnt, width, 0u, up_xyz, cp16);
             if (rc != NB_OK) return rc;
             NB_HIP(ctx, fold(b0, cnt));
         }
-        ctx->cur ^= 1;
-        std::swap(ctx->vel, ctx->vel_alt);
-        ctx->steps++;
+        step_done(ctx, true);
     }
     return NB_OK;
 }
@@ -363,9 +350,9 @@ NB_EXPORT int nb_step_boids_seen(nb_ctx *ctx, uint32_t k, const nb_boids_params 
             return make_boids_args(boids_params_or_default(params), ctx->n, 0, ctx->n, &a, &tile, &ctx->err);
         },
         [&](uint32_t b0, uint32_t cnt) {
-            a.pos_in = ctx->pos[ctx->cur], a.pos_out = ctx->pos[ctx->cur ^ 1], a.vel_in = ctx->vel, a.vel_out = ctx->vel_alt;
+            a.pos_in = ctx->pos[ctx->cur].p, a.pos_out = ctx->pos[ctx->cur ^ 1].p, a.vel_in = ctx->vel.p, a.vel_out = ctx->vel_alt.p;
             a.first = b0, a.count = cnt;
-            return nbk::launch_boids_seen(a, ctx->seen_count, ctx->seen_ids, width, ctx->stream);
+            return nbk::launch_boids_seen(a, ctx->seen_count.p, ctx->seen_ids.p, width, ctx->stream);
         });
 }
 
@@ -380,8 +367,8 @@ NB_EXPORT int nb_step_nbody_located(nb_ctx *ctx, uint32_t k, const float *up_xyz
             return NB_OK;
         },
         [&](uint32_t b0, uint32_t cnt) {
-            a.pos_in = ctx->pos[ctx->cur], a.pos_out = ctx->pos[ctx->cur ^ 1], a.vel_in = ctx->vel, a.vel_out = ctx->vel_alt;
+            a.pos_in = ctx->pos[ctx->cur].p, a.pos_out = ctx->pos[ctx->cur ^ 1].p, a.vel_in = ctx->vel.p, a.vel_out = ctx->vel_alt.p;
             a.first = b0, a.count = cnt;
-            return nbk::launch_nbody_located(a, ctx->seen_count, ctx->loc_rel, width, ctx->stream);
+            return nbk::launch_nbody_located(a, ctx->seen_count.p, ctx->loc_rel.p, width, ctx->stream);
         });
 }

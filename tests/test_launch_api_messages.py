@@ -7,7 +7,8 @@ two arguments wrong at once and pin which check comes first.  The answers were r
 host side of the launch API was folded into shared helpers; the table holds that refactor, and later ones, to them byte for byte.
 
 No row may reach the device: on a machine with a GPU the fake addresses would be used.  nb_launch_status has no row for that
-reason (it has no argument to refuse and waits for the device at once).
+reason (it has no argument to refuse and waits for the device at once).  The context's entries have rows for the one refusal that
+needs no context -- there is none --; what they answer with one is tests/test_gpu_ctx_entries.py's and tests/test_gpu_vision_entries.py's.
 """
 import ctypes
 
@@ -429,7 +430,41 @@ ROWS = [
     ('nb_frame_msaa', (None, A, 8, 8, 0, C, D, E, F), -1, 'nb_frame_msaa: ctx is null'),
     # nb_step_boids_seen
     ('nb_step_boids_seen', (None, 1, None, A, B, 8, 0), -1, 'nb_step_boids_seen: ctx is null'),
+    # The base entries of the context without one (recorded before the context's preamble became one helper); "two faults": a second
+    # argument the entry would refuse, which it never gets to.
+    # nb_upload
+    ('nb_upload', (None, A, B), -1, 'nb_upload: ctx is null'),
+    ('nb_upload', (None, None, None), -1, 'nb_upload: ctx is null'),   # two faults
+    # nb_step
+    ('nb_step', (None, 1), -1, 'nb_step: ctx is null'),
+    ('nb_step', (None, 0), -1, 'nb_step: ctx is null'),
+    # nb_step_boids
+    ('nb_step_boids', (None, 1, None), -1, 'nb_step_boids: ctx is null'),
+    ('nb_step_boids', (None, 1, 'boids'), -1, 'nb_step_boids: ctx is null'),
+    ('nb_step_boids', (None, 1, 'boids_badtile'), -1, 'nb_step_boids: ctx is null'),   # two faults
+    # nb_step_random
+    ('nb_step_random', (None, 1, 7), -1, 'nb_step_random: ctx is null'),
+    # nb_device_state
+    ('nb_device_state', (None, None, None, None), -1, 'nb_device_state: ctx is null'),
+    # nb_cameras
+    ('nb_cameras', (None, A, B, C), -1, 'nb_cameras: ctx is null'),
+    ('nb_cameras', (None, None, B, C), -1, 'nb_cameras: ctx is null'),   # two faults
+    ('nb_cameras', (None, None, None, None), -1, 'nb_cameras: ctx is null'),   # two faults
+    # nb_camera_at
+    ('nb_camera_at', (None, A, B, C, D, E), -1, 'nb_camera_at: ctx is null'),
+    ('nb_camera_at', (None, A, B, C, D, None), -1, 'nb_camera_at: ctx is null'),   # two faults
+    # nb_eyes_skin
+    ('nb_eyes_skin', (None, A, 2, 2), -1, 'nb_eyes_skin: ctx is null'),
+    ('nb_eyes_skin', (None, None, 0, 0), -1, 'nb_eyes_skin: ctx is null'),
+    ('nb_eyes_skin', (None, A, 0, 2049), -1, 'nb_eyes_skin: ctx is null'),   # two faults
+    # nb_sync
+    ('nb_sync', (None,), -1, 'nb_sync: ctx is null'),
+    # nb_download
+    ('nb_download', (None, A, B, C), -1, 'nb_download: ctx is null'),
+    ('nb_download', (None, None, None, None), -1, 'nb_download: ctx is null'),
 ]
+BASE_CONTEXT_ENTRIES = {"nb_upload", "nb_step", "nb_step_boids", "nb_step_random", "nb_device_state", "nb_cameras", "nb_camera_at",
+                        "nb_eyes_skin", "nb_sync", "nb_download"}
 
 
 def test_no_row_expects_the_device():
@@ -438,6 +473,9 @@ def test_no_row_expects_the_device():
     stateless = {name for name in _lib.PROTOTYPES if name.startswith("nb_launch_") or "scratch_bytes" in name}
     assert stateless - entries == {"nb_launch_status"}
     assert {"nb_ring_partners", "nb_ring_phased", "nb_eyes", "nb_eyes_colour", "nb_eyes_msaa", "nb_frame", "nb_frame_msaa"} <= entries
+    assert BASE_CONTEXT_ENTRIES <= entries
+    # a context entry's rows here have no context: with one, the call would go on to the device
+    assert all(args[0] is None for entry, args, _, _ in ROWS if entry in BASE_CONTEXT_ENTRIES)
 
 
 @pytest.mark.parametrize("entry", sorted({entry for entry, _, _, _ in ROWS}))
