@@ -309,6 +309,24 @@ int nb_scenes_sync(nb_scenes *ctx);
 uint64_t nb_scenes_steps(const nb_scenes *ctx); /* steps applied since the last upload */
 const char *nb_scenes_last_error(const nb_scenes *ctx);
 
+/* ---- scene batches: the boids step over what each body sees -----------------------------------------
+ * The eye set-up is (up_xyz, cp16, width) as nb_step_boids_seen takes it, 1 <= width <= NB_EYES_MAX_WIDTH.  One kernel per step
+ * for the whole batch: the eye's row and its seen set stay on chip, no row and no list is written to device memory.
+ *   SV1  k applications give scene s exactly the records nb_step_boids_seen(ctx, k, params, up_xyz, cp16, width, 0) gives a context
+ *        of n bodies uploaded with scene s's records -- every bit.  An eye sees only bodies of its own scene, ids are scene-local
+ *        (0 .. n-1), an eye does not see its own body (flags = 0), the radius thresholds are those of a set of n bodies; a body that
+ *        sees nobody gets velocity (0, 0, 0) and stays where it is
+ *   SV2  no scene's result depends on another scene's records, on `scenes`, on the grid, on the launch shape chosen for n, or on how
+ *        k steps are split over calls
+ *   SV3  the seen sets the step folds over are observable: eye i of scene s has seen_count and width slots of seen_ids, the words
+ *        nb_eyes_seen gives a context holding that scene (S1-S3): members ascending, NB_EYES_NONE behind the count.  seen_depth and
+ *        seen_cols are NOT offered: the step keeps only which ids occur in a row (a bitmap), not their depths or column counts
+ *   SV4  the same bits from run to run */
+
+/* The four entries are declared in nenbody_scenes_seen.h, which this header includes: nb_scenes_boids_seen_step_launch and
+ * nb_scenes_seen_launch on caller-owned device memory, nb_scenes_step_boids_seen and nb_scenes_eyes_seen on a context. */
+#include "nenbody_scenes_seen.h"
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which

@@ -355,6 +355,34 @@ public:
     uint32_t n() const { return n_; }
     void step(uint32_t k = 1) { check_sc(nb_scenes_step(ctx_, k)); }
     void step_boids(uint32_t k = 1, const nb_boids_params *params = nullptr) { check_sc(nb_scenes_step_boids(ctx_, k, params)); }
+    // k update_instance_boids of every scene restricted to what each entity sees of its own scene (nb_scenes_step_boids_seen,
+    // DESIGN.md section 14.1): the bits Scene::step_boids_seen_n gives each scene; one fused launch per step for the whole batch
+    void step_boids_seen(uint32_t k, const Mat4 &cp, uint32_t width = 1024, const nb_boids_params *params = nullptr,
+                         const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        check_sc(nb_scenes_step_boids_seen(ctx_, k, params, up.data(), cp[0].data(), width));
+    }
+    // The seen sets that step folds over (nb_scenes_eyes_seen) for scenes [first_scene, first_scene + scene_count): count[s * n + i]
+    // members of eye i of scene s, its `width` slots at ids[(s * n + i) * width], scene-local ids ascending, NB_EYES_NONE behind them.
+    // Depths and column counts are not kept by the batch's step and are not offered.
+    struct Seen {
+        uint32_t width = 0;
+        std::vector<uint32_t> count, ids;
+    };
+    Seen seen(const Mat4 &cp, uint32_t width = 1024, uint32_t first_scene = 0, uint32_t scene_count = UINT32_MAX,
+              const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (scene_count == UINT32_MAX) scene_count = first_scene <= scenes_ ? scenes_ - first_scene : 0;
+        Seen s;
+        s.width = width;
+        const size_t eyes = (size_t)scene_count * n_;
+        s.count.resize(eyes ? eyes : 1);
+        s.ids.resize(eyes && width ? eyes * width : 1);
+        check_sc(nb_scenes_eyes_seen(ctx_, first_scene, scene_count, up.data(), cp[0].data(), width, s.count.data(), s.ids.data()));
+        s.count.resize(eyes);
+        s.ids.resize(eyes * width);
+        return s;
+    }
     void sync() { check_sc(nb_scenes_sync(ctx_)); }
     uint64_t steps_done() const { return nb_scenes_steps(ctx_); }
     void download(std::vector<Vec3> &positions, std::vector<Vec3> &velocities, std::vector<Mat4> &instances)

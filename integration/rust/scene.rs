@@ -110,6 +110,11 @@ extern "C" {
     fn nb_scenes_sync(ctx: *mut NbScenes) -> c_int;
     fn nb_scenes_steps(ctx: *const NbScenes) -> u64;
     fn nb_scenes_last_error(ctx: *const NbScenes) -> *const c_char;
+    // the boids step over what each body sees of its own scene, one fused launch per step, and the seen sets it folds over
+    fn nb_scenes_step_boids_seen(ctx: *mut NbScenes, k: u32, params: *const NbBoidsParams, up_xyz: *const f32, cp16: *const f32, width: u32) -> c_int;
+    fn nb_scenes_eyes_seen(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, seen_count: *mut u32, seen_ids: *mut u32) -> c_int;
+    fn nb_scenes_boids_seen_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, pos_in: *const c_void, vel_in: *const c_void, pos_out: *mut c_void, vel_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_seen_launch(scenes: u32, n: u32, first_eye: u32, count: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, seen_count: *mut c_void, seen_ids: *mut c_void, stream: *mut c_void) -> c_int;
     // the same on caller-owned device memory, in place
     fn nb_scenes_nbody_step_launch(params: *const NbParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_boids_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
@@ -773,6 +778,34 @@ impl SceneBatch {
     /// k `update_instance_boids` of every scene with the reference's constants, asynchronous
     pub fn step_boids(&mut self, k: u32) -> Result<(), SceneError> {
         check_scenes(unsafe { nb_scenes_step_boids(self.ctx, k, std::ptr::null()) }, self.ctx)
+    }
+
+    /// k `update_instance_boids` of every scene restricted to what each entity sees of its own scene,
+    /// with the reference's constants, asynchronous; `cp`: the eyes' camera constant, column-major
+    pub fn step_boids_seen(&mut self, k: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<(), SceneError> {
+        let up = [0.0f32, 0.0, 1.0];
+        check_scenes(
+            unsafe { nb_scenes_step_boids_seen(self.ctx, k, std::ptr::null(), up.as_ptr(), cp.as_ptr() as *const f32, width) },
+            self.ctx,
+        )
+    }
+
+    /// the seen sets that step folds over, for scenes [first_scene, first_scene + scene_count): (count, ids) with `width` slots an
+    /// eye, scene-local ids ascending, NB_EYES_NONE behind the count
+    pub fn seen(&mut self, first_scene: u32, scene_count: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<(Vec<u32>, Vec<u32>), SceneError> {
+        let up = [0.0f32, 0.0, 1.0];
+        let eyes = scene_count as usize * self.n;
+        let mut count = vec![0u32; eyes.max(1)];
+        let mut ids = vec![0u32; (eyes * width as usize).max(1)];
+        check_scenes(
+            unsafe {
+                nb_scenes_eyes_seen(self.ctx, first_scene, scene_count, up.as_ptr(), cp.as_ptr() as *const f32, width, count.as_mut_ptr(), ids.as_mut_ptr())
+            },
+            self.ctx,
+        )?;
+        count.truncate(eyes);
+        ids.truncate(eyes * width as usize);
+        Ok((count, ids))
     }
 
     /// positions, velocities and model matrices of every body, scene after scene

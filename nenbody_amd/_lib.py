@@ -227,6 +227,15 @@ PROTOTYPES = {
     "nb_shard_last_error": (c_char_p, [c_void_p]),
 }
 
+# include/nenbody_scenes_seen.h: the seen boids step of scene batches, bound with the table above
+SCENES_SEEN_PROTOTYPES = {
+    "nb_scenes_boids_seen_step_launch": (c_int, [POINTER(NbBoidsParams), c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_seen_launch": (c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_step_boids_seen": (c_int, [c_void_p, c_uint32, POINTER(NbBoidsParams), c_void_p, c_void_p, c_uint32]),
+    "nb_scenes_eyes_seen": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+}
+
 # every symbol include/nenbody_diag.h declares (self-tests, the test suite's switches): not part of the drop-in boundary
 DIAG_PROTOTYPES = {
     "nb_selftest_ladder": (c_int, [c_uint32, c_uint32, POINTER(c_uint64), c_void_p]),
@@ -288,7 +297,7 @@ def _bind(path: str) -> ctypes.CDLL:
         )
     _preload_torch_hip_runtime()
     lib = ctypes.CDLL(path)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SCENES_SEEN_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

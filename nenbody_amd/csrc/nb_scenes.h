@@ -28,4 +28,16 @@ hipError_t launch_scenes_nbody(const ScenesNbodyArgs &a, hipStream_t s);
 // first = 0) as make_boids_args forms them; its four buffer pointers are not read.
 hipError_t launch_scenes_boids(const BoidsArgs &c, float4 *pos, float4 *vel, uint32_t scenes, uint32_t k, hipStream_t s);
 
+// The seen boids step of a batch (nb_scenes_seen.inc): one workgroup per eye, the eye's row and its seen set
+// in LDS only.  A scene of at most kScenesSeenWaveBodies bodies takes one wave per eye, a larger one four; the bits are the same.
+constexpr uint32_t kScenesSeenWaveBodies = 128;
+// ONE step, out of place.  `c`: the constants of a set of n bodies as make_boids_args forms them (n_total = n, first = 0), with the
+// four record pointers set to the batch's scenes * n records.  cams, inst: the 4 / 4 float4 of every body of the batch as
+// launch_cameras / launch_instances leave them for those records.
+hipError_t launch_scenes_boids_seen(const BoidsArgs &c, uint32_t scenes, const float *cams, const float *inst, uint32_t width, hipStream_t s);
+// The seen sets that step folds over (S1-S3) for eyes [first_eye, first_eye + count) of the batch: seen_count, count words;
+// seen_ids, count x width words; either may be NULL.  cams and inst as above, indexed by the eye's number in the batch.
+hipError_t launch_scenes_seen(uint32_t n, uint32_t first_eye, uint32_t count, const float *cams, const float *inst, uint32_t width,
+                              uint32_t *seen_count, uint32_t *seen_ids, hipStream_t s);
+
 }  // namespace nbk

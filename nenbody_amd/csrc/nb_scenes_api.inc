@@ -1,5 +1,7 @@
 // nb_scenes_api.inc -- the C ABI of DESIGN.md section 14: scene batches.  The two stateless entries (nb_scenes_nbody_step_launch,
-// nb_scenes_boids_step_launch) step caller-owned records in place; the context nb_scenes owns a batch and a stream.  Included by
+// nb_scenes_boids_step_launch) step caller-owned records in place; the context nb_scenes owns a batch and a stream.  Section 14.1 adds
+// the boids step over what each body sees: nb_scenes_boids_seen_step_launch and nb_scenes_seen_launch, stateless, and the context's
+// nb_scenes_step_boids_seen and nb_scenes_eyes_seen.  Included by
 // nb_api.hip behind nb_vision_api.inc.  Every check runs before anything touches the device and has its own message naming the entry.
 
 static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
@@ -126,6 +128,82 @@ NB_EXPORT int nb_scenes_boids_step_launch(const nb_boids_params *params, uint32_
                          "nb: boids kernel launch failed (scene batch): ", &g_tls_error);
 }
 
+// ---- the seen boids step (DESIGN.md section 14.1): the stateless entries ------------------------------------------------------------------
+static const char kScenesSeenAlias[] = ": the outputs must not overlap each other or an input";
+
+static int scenes_width_check(const char *fn, uint32_t width, std::string *err)
+{
+    if (width == 0 || width > NB_EYES_MAX_WIDTH) {
+        *err = std::string(fn) + ": width must be 1 .. NB_EYES_MAX_WIDTH (4096)";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_boids_seen_step_launch(const nb_boids_params *params, uint32_t scenes, uint32_t n, const void *cams_16,
+                                               const void *inst_16, uint32_t width, const void *pos_in, const void *vel_in, void *pos_out,
+                                               void *vel_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_boids_seen_step_launch";
+    if (!cams_16 || !inst_16 || !pos_in || !vel_in || !pos_out || !vel_out) {
+        g_tls_error = std::string(fn) + ": cams_16, inst_16 and the four record buffers must be non-null";
+        return NB_ERR_INVALID;
+    }
+    const nb_boids_params p = boids_params_or_default(params);
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_boids_params_check(fn, p, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16 | (uintptr_t)pos_in | (uintptr_t)vel_in | (uintptr_t)pos_out | (uintptr_t)vel_out) & 15u) {
+        g_tls_error = std::string(fn) + ": cams_16, inst_16 and the four record buffers must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t records = (size_t)scenes * n, bytes = records * sizeof(float4);
+    const ByteRange in[4] = {{cams_16, bytes * 4u}, {inst_16, bytes * 4u}, {pos_in, bytes}, {vel_in, bytes}};
+    const ByteRange out[2] = {{pos_out, bytes}, {vel_out, bytes}};
+    rc = outputs_check(fn, out, 0x3u, "", false, in, 4, kScenesSeenAlias, &g_tls_error);
+    nbk::BoidsArgs c;
+    uint32_t tile = 0;
+    if (rc == NB_OK) rc = make_boids_args(p, n, 0, n, &c, &tile, &g_tls_error);
+    if (rc == NB_OK) rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    c.pos_in = (const float4 *)pos_in, c.vel_in = (const float4 *)vel_in, c.pos_out = (float4 *)pos_out, c.vel_out = (float4 *)vel_out;
+    return launch_status(nbk::launch_scenes_boids_seen(c, scenes, (const float *)cams_16, (const float *)inst_16, width, (hipStream_t)stream),
+                         "nb: boids kernel launch failed (scene batch, seen form): ", &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_seen_launch(uint32_t scenes, uint32_t n, uint32_t first_eye, uint32_t count, const void *cams_16, const void *inst_16,
+                                    uint32_t width, void *seen_count, void *seen_ids, void *stream)
+{
+    static const char fn[] = "nb_scenes_seen_launch";
+    if (!cams_16 || !inst_16) {
+        g_tls_error = std::string(fn) + ": cams_16 and inst_16 must be non-null";
+        return NB_ERR_INVALID;
+    }
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16) & 15u) {
+        g_tls_error = std::string(fn) + ": cams_16 and inst_16 must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)first_eye + count > (uint64_t)scenes * n) {
+        g_tls_error = std::string(fn) + ": eyes [first_eye, first_eye + count) exceed the batch";
+        return NB_ERR_INVALID;
+    }
+    const size_t matrices = (size_t)scenes * n * 16 * sizeof(float);
+    const ByteRange in[2] = {{cams_16, matrices}, {inst_16, matrices}};
+    const ByteRange out[2] = {{seen_count, (size_t)count * 4u}, {seen_ids, (size_t)count * width * 4u}};
+    rc = outputs_check(fn, out, 0x3u, ": seen_count and seen_ids are both NULL", true, in, 2, kScenesSeenAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = device_for_launch(inst_16, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    return launch_status(nbk::launch_scenes_seen(n, first_eye, count, (const float *)cams_16, (const float *)inst_16, width,
+                                                 (uint32_t *)seen_count, (uint32_t *)seen_ids, (hipStream_t)stream),
+                         "nb: seen kernel launch failed (scene batch): ", &g_tls_error);
+}
+
 // ---- the context --------------------------------------------------------------------------------------------------------------------------
 struct nb_scenes {
     uint32_t scenes = 0, n = 0;
@@ -134,6 +212,9 @@ struct nb_scenes {
     DeviceBuffer<float4> pos, vel;           // scenes * n records each, stepped in place
     DeviceBuffer<float> stage;               // 6 * scenes * n floats: the stride-3 arrays of an upload or a download
     DeviceBuffer<float4> inst;               // 4 * scenes * n records, allocated on first use
+    DeviceBuffer<float4> pos_alt, vel_alt;   // the seen boids step's outputs, allocated on first use: it swaps them with pos and vel
+    DeviceBuffer<float4> cams;               // 4 * scenes * n records, likewise: every body's eye camera
+    DeviceBuffer<uint32_t> seen_count, seen_ids;   // nb_scenes_eyes_seen's lists for one range of scenes, likewise and grown on demand
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
@@ -237,6 +318,96 @@ NB_EXPORT int nb_scenes_step_boids(nb_scenes *ctx, uint32_t k, const nb_boids_pa
     RoctxRange range(fn);
     NB_HIP(ctx, nbk::launch_scenes_boids(c, ctx->pos.p, ctx->vel.p, ctx->scenes, k, ctx->stream));
     ctx->steps += k;
+    return NB_OK;
+}
+
+// the eye set-up of the context's two seen entries: there, and the width
+static int scenes_eye_setup_check(nb_scenes *ctx, const char *fn, const float *up_xyz, const float *cp16, uint32_t width)
+{
+    if (!up_xyz || !cp16) {
+        ctx->err = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    return scenes_width_check(fn, width, &ctx->err);
+}
+
+// the model matrices and the eye cameras of every body of the current state, on the context's stream
+static int scenes_stage_eyes(nb_scenes *ctx, const float *up_xyz, const float *cp16)
+{
+    const size_t records = (size_t)ctx->scenes * ctx->n;
+    NB_HIP(ctx, ctx->cams.reserve(records * 4));
+    NB_HIP(ctx, launch_matrices((uint32_t)records, ctx->pos.p, ctx->vel.p, &ctx->inst, ctx->stream));
+    NB_HIP(ctx, nbk::launch_cameras((uint32_t)records, ctx->pos.p, ctx->vel.p, up_xyz, cp16, ctx->cams.p, ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_step_boids_seen(nb_scenes *ctx, uint32_t k, const nb_boids_params *params, const float *up_xyz, const float *cp16,
+                                        uint32_t width)
+{
+    static const char fn[] = "nb_scenes_step_boids_seen";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    const nb_boids_params p = boids_params_or_default(params);
+    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    if (rc == NB_OK) rc = scenes_boids_params_check(fn, p, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
+    nbk::BoidsArgs c;
+    uint32_t tile = 0;
+    if (rc == NB_OK) rc = make_boids_args(p, ctx->n, 0, ctx->n, &c, &tile, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (k == 0) return NB_OK;
+    const size_t records = (size_t)ctx->scenes * ctx->n;
+    NB_HIP(ctx, ctx->pos_alt.reserve(records));
+    NB_HIP(ctx, ctx->vel_alt.reserve(records));
+    RoctxRange range(fn);
+    for (uint32_t s = 0; s < k; ++s) {
+        rc = scenes_stage_eyes(ctx, up_xyz, cp16);
+        if (rc != NB_OK) return rc;
+        c.pos_in = ctx->pos.p, c.vel_in = ctx->vel.p, c.pos_out = ctx->pos_alt.p, c.vel_out = ctx->vel_alt.p;
+        NB_HIP(ctx, nbk::launch_scenes_boids_seen(c, ctx->scenes, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width, ctx->stream));
+        ctx->pos.swap(ctx->pos_alt);
+        ctx->vel.swap(ctx->vel_alt);
+        ctx->steps++;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_eyes_seen(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
+                                  uint32_t width, uint32_t *seen_count, uint32_t *seen_ids)
+{
+    static const char fn[] = "nb_scenes_eyes_seen";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    if (rc != NB_OK) return rc;
+    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
+        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
+        return NB_ERR_INVALID;
+    }
+    const size_t eyes = (size_t)scene_count * ctx->n;
+    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
+    const ByteRange out[2] = {{seen_count, eyes * 4u}, {seen_ids, eyes * width * 4u}};
+    rc = outputs_check(fn, out, 0x3u, ": seen_count and seen_ids are both NULL", false, in, 2, kScenesSeenAlias, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
+    if (rc != NB_OK) return rc;
+    if (scene_count == 0) return NB_OK;
+    // scenes per launch: the most whose lists (4 bytes a slot, 4 bytes of count an eye) stay at or below 64 MiB, one at least
+    const size_t per_scene = (size_t)ctx->n * ((size_t)width * 4u + 4u);
+    const uint32_t per = (uint32_t)std::min<size_t>(scene_count, std::max<size_t>(1, ((size_t)64 << 20) / per_scene));
+    NB_HIP(ctx, ctx->seen_count.reserve((size_t)per * ctx->n));
+    if (seen_ids) NB_HIP(ctx, ctx->seen_ids.reserve((size_t)per * ctx->n * width));
+    rc = scenes_stage_eyes(ctx, up_xyz, cp16);
+    if (rc != NB_OK) return rc;
+    for (uint32_t s0 = 0; s0 < scene_count; s0 += per) {
+        const uint32_t cnt = std::min(per, scene_count - s0) * ctx->n, first_eye = (first_scene + s0) * ctx->n;
+        const size_t at = (size_t)s0 * ctx->n;
+        NB_HIP(ctx, nbk::launch_scenes_seen(ctx->n, first_eye, cnt, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width,
+                                            ctx->seen_count.p, seen_ids ? ctx->seen_ids.p : nullptr, ctx->stream));
+        if (seen_count) NB_HIP(ctx, hipMemcpyAsync(seen_count + at, ctx->seen_count.p, (size_t)cnt * 4u, hipMemcpyDeviceToHost, ctx->stream));
+        if (seen_ids)
+            NB_HIP(ctx, hipMemcpyAsync(seen_ids + at * width, ctx->seen_ids.p, (size_t)cnt * width * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
 }
 

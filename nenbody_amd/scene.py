@@ -463,6 +463,36 @@ class SceneBatch:
         """k update_instance_boids of every scene, one launch"""
         self._check(self._lib.nb_scenes_step_boids(self._ctx, int(k), ctypes.byref(params) if params is not None else None))
 
+    @staticmethod
+    def _eye_setup(width, up, cp):
+        if cp is None:   # (an invalid width is the library's to refuse)
+            cp = eye_constant(width) if 0 < width <= _lib.NB_EYES_MAX_WIDTH else np.zeros((4, 4), np.float32)
+        return np.ascontiguousarray(up, np.float32).reshape(3), np.ascontiguousarray(cp, np.float32).reshape(16)
+
+    def step_boids_seen(self, k: int = 1, params: Optional[NbBoidsParams] = None, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None) -> None:
+        """k update_instance_boids of every scene restricted to what each entity sees of its own scene (nb_scenes_step_boids_seen,
+        DESIGN.md section 14.1): the bits :meth:`Scene.step_boids_seen_n` gives each scene, one fused launch per step for the whole
+        batch.  ``cp``: the eyes' camera constant, None: :func:`eye_constant`."""
+        upv, cpm = self._eye_setup(width, up, cp)
+        self._check(self._lib.nb_scenes_step_boids_seen(self._ctx, int(k), ctypes.byref(params) if params is not None else None,
+                                                        upv.ctypes.data, cpm.ctypes.data, width))
+
+    def seen(self, first_scene: int = 0, scene_count: Optional[int] = None, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None):
+        """The seen sets :meth:`step_boids_seen` folds over (nb_scenes_eyes_seen) for scenes [first_scene, first_scene + scene_count)
+        of the current state: per eye the scene-local ids in its row, ascending.  Returns (count uint32 (S, n), ids uint32
+        (S, n, width) -- NB_EYES_NONE behind the first count slots); the words of :meth:`Scene.seen` per scene.  Depths and column
+        counts are not kept by the batch's step and are not offered."""
+        if scene_count is None:
+            scene_count = self.scenes - first_scene
+        if first_scene < 0 or scene_count < 0:
+            raise ValueError("first_scene and scene_count must be >= 0")
+        upv, cpm = self._eye_setup(width, up, cp)
+        count = np.empty((scene_count, self.n), np.uint32)
+        ids = np.empty((scene_count, self.n, max(int(width), 0)), np.uint32)
+        self._check(self._lib.nb_scenes_eyes_seen(self._ctx, first_scene, scene_count, upv.ctypes.data, cpm.ctypes.data, width,
+                                                  count.ctypes.data, ids.ctypes.data))
+        return count, ids
+
     def _download(self, what: int) -> np.ndarray:
         out = np.empty((self.scenes, self.n, 4, 4) if what == 2 else (self.scenes, self.n, 3), np.float32)
         args = [None, None, None]
