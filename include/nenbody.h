@@ -327,6 +327,28 @@ const char *nb_scenes_last_error(const nb_scenes *ctx);
  * nb_scenes_seen_launch on caller-owned device memory, nb_scenes_step_boids_seen and nb_scenes_eyes_seen on a context. */
 #include "nenbody_scenes_seen.h"
 
+/* ---- scene batches: gravity from located vision ----------------------------------------------------
+ * The eye set-up is (up_xyz, cp16, width) as nb_step_nbody_located takes it, 1 <= width <= NB_EYES_MAX_WIDTH; dt, G and bias are
+ * nb_params'.  One kernel per step for the whole batch: the eye's row, its members' depths and columns, the located points and the
+ * quotients stay on chip.
+ *   SL1  k applications give scene s exactly the records nb_step_nbody_located(ctx, k, up_xyz, cp16, width, batch) gives a context of
+ *        n bodies uploaded with scene s's records -- every bit, for any batch.  An eye sees only bodies of its own scene, ids are
+ *        scene-local (0 .. n-1), an eye does not draw its own body (flags = 0); a body that sees nobody coasts (G3); a body with
+ *        zero or non-finite velocity sees nobody, and its own record still takes G3
+ *   SL2  no scene's result depends on another scene's records, on `scenes`, on the grid, on the launch shape chosen for n, or on how
+ *        k steps are split over calls
+ *   SL3  the located sets the step folds over are observable: eye i of scene s has seen_count and width slots each of seen_ids,
+ *        seen_depth, seen_col and seen_rel (16 bytes a slot), the words nb_eyes_located gives a context holding that scene (S1-S3,
+ *        L1-L5), padding included: NB_EYES_NONE for ids and col, 1.0f for depth, four +0 words for rel.  seen_cols, the column
+ *        count, is NOT offered: the step keeps a member's nearest depth and its column, not how many columns hold it
+ *   SL4  the same bits from run to run
+ *   SL5  L6 holds: a cp16 that cannot be inverted is refused on the host, with L6's texts behind the entry's name, before the
+ *        device is touched */
+
+/* The four entries are declared in nenbody_scenes_located.h, which this header includes: nb_scenes_nbody_located_step_launch and
+ * nb_scenes_located_launch on caller-owned device memory, nb_scenes_step_nbody_located and nb_scenes_eyes_located on a context. */
+#include "nenbody_scenes_located.h"
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which

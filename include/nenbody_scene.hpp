@@ -383,6 +383,36 @@ public:
         s.ids.resize(eyes * width);
         return s;
     }
+    // k update_instance_nbody of every scene from vision alone (nb_scenes_step_nbody_located): the bits
+    // Scene::step_nbody_located_n gives each scene; one fused launch per step for the whole batch.  cp: a perspective constant
+    void step_nbody_located(uint32_t k, const Mat4 &cp, uint32_t width = 1024, const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        check_sc(nb_scenes_step_nbody_located(ctx_, k, up.data(), cp[0].data(), width));
+    }
+    // The located sets that step folds over (nb_scenes_eyes_located) for scenes [first_scene, first_scene + scene_count): per eye
+    // s * n + i its count and `width` slots each of ids, depth, col and rel (4 floats a slot: x, y, z, range), the words of
+    // Scene's located sets per scene, padding included.  Column counts are not kept by the batch's step and are not offered.
+    struct Located {
+        uint32_t width = 0;
+        std::vector<uint32_t> count, ids, col;
+        std::vector<float> depth, rel;
+    };
+    Located located(const Mat4 &cp, uint32_t width = 1024, uint32_t first_scene = 0, uint32_t scene_count = UINT32_MAX,
+                    const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (scene_count == UINT32_MAX) scene_count = first_scene <= scenes_ ? scenes_ - first_scene : 0;
+        Located l;
+        l.width = width;
+        const size_t eyes = (size_t)scene_count * n_, cells = eyes * width;
+        l.count.resize(eyes ? eyes : 1);
+        l.ids.resize(cells ? cells : 1), l.depth.resize(cells ? cells : 1), l.col.resize(cells ? cells : 1);
+        l.rel.resize(cells ? cells * 4 : 4);
+        check_sc(nb_scenes_eyes_located(ctx_, first_scene, scene_count, up.data(), cp[0].data(), width, l.count.data(), l.ids.data(),
+                                        l.depth.data(), l.col.data(), l.rel.data()));
+        l.count.resize(eyes);
+        l.ids.resize(cells), l.depth.resize(cells), l.col.resize(cells), l.rel.resize(cells * 4);
+        return l;
+    }
     void sync() { check_sc(nb_scenes_sync(ctx_)); }
     uint64_t steps_done() const { return nb_scenes_steps(ctx_); }
     void download(std::vector<Vec3> &positions, std::vector<Vec3> &velocities, std::vector<Mat4> &instances)

@@ -115,6 +115,11 @@ extern "C" {
     fn nb_scenes_eyes_seen(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, seen_count: *mut u32, seen_ids: *mut u32) -> c_int;
     fn nb_scenes_boids_seen_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, pos_in: *const c_void, vel_in: *const c_void, pos_out: *mut c_void, vel_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_seen_launch(scenes: u32, n: u32, first_eye: u32, count: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, seen_count: *mut c_void, seen_ids: *mut c_void, stream: *mut c_void) -> c_int;
+    // gravity from located vision of every scene, one fused launch per step, and the located sets it folds over
+    fn nb_scenes_step_nbody_located(ctx: *mut NbScenes, k: u32, up_xyz: *const f32, cp16: *const f32, width: u32) -> c_int;
+    fn nb_scenes_eyes_located(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, seen_count: *mut u32, seen_ids: *mut u32, seen_depth: *mut f32, seen_col: *mut u32, seen_rel: *mut f32) -> c_int;
+    fn nb_scenes_nbody_located_step_launch(params: *const NbParams, scenes: u32, n: u32, cams_16: *const c_void, inst_16: *const c_void, up_xyz: *const f32, cp16: *const f32, width: u32, pos_in: *const c_void, vel_in: *const c_void, pos_out: *mut c_void, vel_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_located_launch(scenes: u32, n: u32, first_eye: u32, count: u32, cams_16: *const c_void, inst_16: *const c_void, vel_in: *const c_void, up_xyz: *const f32, cp16: *const f32, width: u32, seen_count: *mut c_void, seen_ids: *mut c_void, seen_depth: *mut c_void, seen_col: *mut c_void, seen_rel: *mut c_void, stream: *mut c_void) -> c_int;
     // the same on caller-owned device memory, in place
     fn nb_scenes_nbody_step_launch(params: *const NbParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_boids_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
@@ -733,6 +738,16 @@ fn check_scenes(rc: c_int, ctx: *const NbScenes) -> Result<(), SceneError> {
     Err(SceneError(rc, msg))
 }
 
+/// What `SceneBatch::located` returns: per eye `s * n + i` its count and `width` slots of each list (no column counts).
+pub struct BatchLocated {
+    pub width: u32,
+    pub count: Vec<u32>,
+    pub ids: Vec<u32>,
+    pub depth: Vec<f32>,
+    pub col: Vec<u32>,
+    pub rel: Vec<[f32; 4]>,
+}
+
 /// B independent scenes of n <= `NB_SCENES_MAX_BODIES` bodies, device-resident; one launch steps every scene k times, one
 /// workgroup per scene, and every scene gets the bits a `Scene` of its n bodies gets.  Body i of scene s is element `s * n + i`.
 pub struct SceneBatch {
@@ -806,6 +821,44 @@ impl SceneBatch {
         count.truncate(eyes);
         ids.truncate(eyes * width as usize);
         Ok((count, ids))
+    }
+
+    /// k `update_instance_nbody` of every scene from vision alone: every body folds the law over where its
+    /// own eye sees the bodies of its own scene; asynchronous; `cp`: the eyes' perspective constant, column-major
+    pub fn step_nbody_located(&mut self, k: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<(), SceneError> {
+        let up = [0.0f32, 0.0, 1.0];
+        check_scenes(
+            unsafe { nb_scenes_step_nbody_located(self.ctx, k, up.as_ptr(), cp.as_ptr() as *const f32, width) },
+            self.ctx,
+        )
+    }
+
+    /// the located sets that step folds over, for scenes [first_scene, first_scene + scene_count): `width` slots an eye of ids,
+    /// depth, col and rel (x, y, z, range), padded with NB_EYES_NONE, 1.0, NB_EYES_NONE and +0 behind the count
+    pub fn located(&mut self, first_scene: u32, scene_count: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<BatchLocated, SceneError> {
+        let up = [0.0f32, 0.0, 1.0];
+        let eyes = scene_count as usize * self.n;
+        let cells = eyes * width as usize;
+        let mut l = BatchLocated {
+            width,
+            count: vec![0u32; eyes.max(1)],
+            ids: vec![0u32; cells.max(1)],
+            depth: vec![0f32; cells.max(1)],
+            col: vec![0u32; cells.max(1)],
+            rel: vec![[0f32; 4]; cells.max(1)],
+        };
+        check_scenes(
+            unsafe {
+                nb_scenes_eyes_located(self.ctx, first_scene, scene_count, up.as_ptr(), cp.as_ptr() as *const f32, width, l.count.as_mut_ptr(), l.ids.as_mut_ptr(), l.depth.as_mut_ptr(), l.col.as_mut_ptr(), l.rel.as_mut_ptr() as *mut f32)
+            },
+            self.ctx,
+        )?;
+        l.count.truncate(eyes);
+        l.ids.truncate(cells);
+        l.depth.truncate(cells);
+        l.col.truncate(cells);
+        l.rel.truncate(cells);
+        Ok(l)
     }
 
     /// positions, velocities and model matrices of every body, scene after scene

@@ -236,6 +236,17 @@ SCENES_SEEN_PROTOTYPES = {
     "nb_scenes_eyes_seen": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
 }
 
+# include/nenbody_scenes_located.h: gravity from located vision for scene batches, bound likewise
+SCENES_LOCATED_PROTOTYPES = {
+    "nb_scenes_nbody_located_step_launch": (c_int, [POINTER(NbParams), c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_located_launch": (c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_step_nbody_located": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]),
+    "nb_scenes_eyes_located": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+}
+
 # every symbol include/nenbody_diag.h declares (self-tests, the test suite's switches): not part of the drop-in boundary
 DIAG_PROTOTYPES = {
     "nb_selftest_ladder": (c_int, [c_uint32, c_uint32, POINTER(c_uint64), c_void_p]),
@@ -297,7 +308,8 @@ def _bind(path: str) -> ctypes.CDLL:
         )
     _preload_torch_hip_runtime()
     lib = ctypes.CDLL(path)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SCENES_SEEN_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SCENES_SEEN_PROTOTYPES.items()) + list(SCENES_LOCATED_PROTOTYPES.items()) \
+            + list(DIAG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -47,6 +47,7 @@
 //   nb_located.inc       where each eye sees the members of its seen set; the gravity step over those relative positions (SLP-off unit; launchers in nb_located.h)
 //   nb_scenes.inc        scene batches: B scenes of up to 2 048 bodies, k steps, one workgroup per scene (SLP-off unit; launchers in nb_scenes.h)
 //   nb_scenes_seen.inc   scene batches: the seen boids step, eye row and seen set in LDS, one workgroup per eye (SLP-off unit; launchers in nb_scenes.h)
+//   nb_scenes_located.inc scene batches: gravity from located vision, row, depths, columns and quotients in LDS, one workgroup per eye (SLP-off unit; launchers in nb_scenes.h)
 //   nb_launch.inc        host-side launchers
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -89,6 +90,7 @@ static_assert(kMsaaOffsets16 == sample_nibbles(kEyeSampleX16) && kFrameMsaaOffse
 #include "nb_located.inc"     // the located seen sets and the gravity step over them: likewise; uses nb_seen.inc's constants and nb_nbody_strict.inc's integrate
 #include "nb_scenes.inc"      // scene batches, one workgroup per scene: likewise; uses nb_nbody_strict.inc's folds and nb_boids.inc's pair and epilogue
 #include "nb_scenes_seen.inc" // the seen boids step of a batch, one workgroup per eye: likewise; uses nb_eyes.inc's loop body, nb_seen.inc's pair and nb_boids.inc's epilogue
+#include "nb_scenes_located.inc" // gravity from located vision for a batch, one workgroup per eye: likewise; uses nb_eyes.inc's loop body, nb_located.inc's normalize and nb_nbody_strict.inc's integrate
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

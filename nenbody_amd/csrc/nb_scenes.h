@@ -40,4 +40,30 @@ hipError_t launch_scenes_boids_seen(const BoidsArgs &c, uint32_t scenes, const f
 hipError_t launch_scenes_seen(uint32_t n, uint32_t first_eye, uint32_t count, const float *cams, const float *inst, uint32_t width,
                               uint32_t *seen_count, uint32_t *seen_ids, hipStream_t s);
 
+// Gravity from located vision for a batch (nb_scenes_located.inc): one workgroup per eye, the eye's row, its
+// members' nearest depths and columns and the quotients in LDS only -- 8 width + 12 n + 256 bytes, at most 57 600.  The launch shape
+// follows kScenesSeenWaveBodies as above; the bits are the same.  The caller has checked the arguments (1 <= n <= kScenesMaxBodies,
+// 1 <= width <= NB_EYES_MAX_WIDTH, count >= 1, a constant that L2 inverts: L6).
+struct ScenesLocatedArgs {
+    uint32_t n, first_eye, count, width;     // eyes [first_eye, first_eye + count) of the batch; eye b is body b % n of scene b / n
+    const float4 *__restrict__ cams;         // 4 / 4 float4 per body of the WHOLE batch, as launch_cameras / launch_instances leave them
+    const float4 *__restrict__ inst;
+    const float4 *__restrict__ pos_in;       // the batch's records; the step reads both, the sets vel_in alone (the eye's direction)
+    const float4 *__restrict__ vel_in;
+    float ux, uy, uz;
+    float cp0, cp10, cp14;
+    float dt, G, bias;                       // main.rs:411-413; the step's
+    float4 *__restrict__ pos_out;            // the step's: record b written
+    float4 *__restrict__ vel_out;
+    uint32_t *__restrict__ seen_count;       // the sets' (SL3): count words, and count x width words or records; any may be NULL
+    uint32_t *__restrict__ seen_ids;
+    uint32_t *__restrict__ seen_depth;       // bit patterns
+    uint32_t *__restrict__ seen_col;
+    float4 *__restrict__ seen_rel;
+};
+// ONE step, out of place, for every eye the arguments name (the entries pass the whole batch).
+hipError_t launch_scenes_nbody_located(const ScenesLocatedArgs &a, hipStream_t s);
+// The located sets that step folds over: the words nb_eyes_located gives a context holding the eye's scene, indexed from first_eye.
+hipError_t launch_scenes_located(const ScenesLocatedArgs &a, hipStream_t s);
+
 }  // namespace nbk

@@ -1,7 +1,8 @@
 // nb_scenes_api.inc -- the C ABI of DESIGN.md section 14: scene batches.  The two stateless entries (nb_scenes_nbody_step_launch,
 // nb_scenes_boids_step_launch) step caller-owned records in place; the context nb_scenes owns a batch and a stream.  Section 14.1 adds
 // the boids step over what each body sees: nb_scenes_boids_seen_step_launch and nb_scenes_seen_launch, stateless, and the context's
-// nb_scenes_step_boids_seen and nb_scenes_eyes_seen.  Included by
+// nb_scenes_step_boids_seen and nb_scenes_eyes_seen.  Section 14.2 adds gravity from located vision in the same four shapes:
+// nb_scenes_nbody_located_step_launch, nb_scenes_located_launch, nb_scenes_step_nbody_located and nb_scenes_eyes_located.  Included by
 // nb_api.hip behind nb_vision_api.inc.  Every check runs before anything touches the device and has its own message naming the entry.
 
 static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
@@ -204,6 +205,91 @@ NB_EXPORT int nb_scenes_seen_launch(uint32_t scenes, uint32_t n, uint32_t first_
                          "nb: seen kernel launch failed (scene batch): ", &g_tls_error);
 }
 
+// ---- gravity from located vision (DESIGN.md section 14.2): the stateless entries ----------------------------------------------------------
+static const char kNoScenesLocatedOutputs[] = ": seen_count, seen_ids, seen_depth, seen_col and seen_rel are all NULL";
+
+// the kernel's arguments but for its buffers: the eye set-up and the law's constants
+static nbk::ScenesLocatedArgs scenes_located_args(const nb_params &p, uint32_t n, uint32_t first_eye, uint32_t count, const void *cams,
+                                                  const void *inst, const float *up_xyz, const float *cp16, uint32_t width)
+{
+    nbk::ScenesLocatedArgs a{};
+    a.n = n, a.first_eye = first_eye, a.count = count, a.width = width;
+    a.cams = (const float4 *)cams, a.inst = (const float4 *)inst;
+    a.ux = up_xyz[0], a.uy = up_xyz[1], a.uz = up_xyz[2];
+    a.cp0 = cp16[0], a.cp10 = cp16[10], a.cp14 = cp16[14];
+    a.dt = p.dt, a.G = p.G, a.bias = p.bias;
+    return a;
+}
+
+NB_EXPORT int nb_scenes_nbody_located_step_launch(const nb_params *params, uint32_t scenes, uint32_t n, const void *cams_16,
+                                                  const void *inst_16, const float *up_xyz, const float *cp16, uint32_t width,
+                                                  const void *pos_in, const void *vel_in, void *pos_out, void *vel_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_nbody_located_step_launch";
+    if (!cams_16 || !inst_16 || !up_xyz || !cp16 || !pos_in || !vel_in || !pos_out || !vel_out) {
+        g_tls_error = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    const nb_params p = params_or_default(params);
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
+    if (rc == NB_OK) rc = located_cp_check(fn, cp16, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16 | (uintptr_t)pos_in | (uintptr_t)vel_in | (uintptr_t)pos_out | (uintptr_t)vel_out) & 15u) {
+        g_tls_error = std::string(fn) + ": cams_16, inst_16 and the four record buffers must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t records = (size_t)scenes * n, bytes = records * sizeof(float4);
+    const ByteRange in[6] = {{cams_16, bytes * 4u}, {inst_16, bytes * 4u},          {pos_in, bytes},
+                             {vel_in, bytes},       {up_xyz, 3 * sizeof(float)},    {cp16, 16 * sizeof(float)}};
+    const ByteRange out[2] = {{pos_out, bytes}, {vel_out, bytes}};
+    rc = outputs_check(fn, out, 0x3u, "", false, in, 6, kScenesSeenAlias, &g_tls_error);
+    if (rc == NB_OK) rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    nbk::ScenesLocatedArgs a = scenes_located_args(p, n, 0u, (uint32_t)records, cams_16, inst_16, up_xyz, cp16, width);
+    a.pos_in = (const float4 *)pos_in, a.vel_in = (const float4 *)vel_in, a.pos_out = (float4 *)pos_out, a.vel_out = (float4 *)vel_out;
+    return launch_status(nbk::launch_scenes_nbody_located(a, (hipStream_t)stream),
+                         "nb: gravity kernel launch failed (scene batch, located form): ", &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_located_launch(uint32_t scenes, uint32_t n, uint32_t first_eye, uint32_t count, const void *cams_16,
+                                       const void *inst_16, const void *vel_in, const float *up_xyz, const float *cp16, uint32_t width,
+                                       void *seen_count, void *seen_ids, void *seen_depth, void *seen_col, void *seen_rel, void *stream)
+{
+    static const char fn[] = "nb_scenes_located_launch";
+    if (!cams_16 || !inst_16 || !vel_in || !up_xyz || !cp16) {
+        g_tls_error = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
+    if (rc == NB_OK) rc = located_cp_check(fn, cp16, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (((uintptr_t)cams_16 | (uintptr_t)inst_16 | (uintptr_t)vel_in | (uintptr_t)seen_rel) & 15u) {
+        g_tls_error = std::string(fn) + ": cams_16, inst_16, vel_in and seen_rel must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)first_eye + count > (uint64_t)scenes * n) {
+        g_tls_error = std::string(fn) + ": eyes [first_eye, first_eye + count) exceed the batch";
+        return NB_ERR_INVALID;
+    }
+    const size_t records = (size_t)scenes * n, cells = (size_t)count * width;
+    const ByteRange in[5] = {{cams_16, records * 64u}, {inst_16, records * 64u}, {vel_in, records * 16u}, {up_xyz, 3 * sizeof(float)},
+                             {cp16, 16 * sizeof(float)}};
+    const ByteRange out[5] = {{seen_count, (size_t)count * 4u}, {seen_ids, cells * 4u}, {seen_depth, cells * 4u}, {seen_col, cells * 4u},
+                              {seen_rel, cells * 16u}};
+    rc = outputs_check(fn, out, 0x1Fu, kNoScenesLocatedOutputs, true, in, 5, kScenesSeenAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = device_for_launch(inst_16, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    nbk::ScenesLocatedArgs a = scenes_located_args(nb_params{}, n, first_eye, count, cams_16, inst_16, up_xyz, cp16, width);
+    a.vel_in = (const float4 *)vel_in;
+    a.seen_count = (uint32_t *)seen_count, a.seen_ids = (uint32_t *)seen_ids, a.seen_depth = (uint32_t *)seen_depth;
+    a.seen_col = (uint32_t *)seen_col, a.seen_rel = (float4 *)seen_rel;
+    return launch_status(nbk::launch_scenes_located(a, (hipStream_t)stream), "nb: located kernel launch failed (scene batch): ", &g_tls_error);
+}
+
 // ---- the context --------------------------------------------------------------------------------------------------------------------------
 struct nb_scenes {
     uint32_t scenes = 0, n = 0;
@@ -215,6 +301,8 @@ struct nb_scenes {
     DeviceBuffer<float4> pos_alt, vel_alt;   // the seen boids step's outputs, allocated on first use: it swaps them with pos and vel
     DeviceBuffer<float4> cams;               // 4 * scenes * n records, likewise: every body's eye camera
     DeviceBuffer<uint32_t> seen_count, seen_ids;   // nb_scenes_eyes_seen's lists for one range of scenes, likewise and grown on demand
+    DeviceBuffer<uint32_t> seen_depth, seen_col;   // nb_scenes_eyes_located's further lists, likewise: depth bits and columns
+    DeviceBuffer<float4> seen_rel;                 // and its located points
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
@@ -406,6 +494,88 @@ NB_EXPORT int nb_scenes_eyes_seen(nb_scenes *ctx, uint32_t first_scene, uint32_t
         if (seen_count) NB_HIP(ctx, hipMemcpyAsync(seen_count + at, ctx->seen_count.p, (size_t)cnt * 4u, hipMemcpyDeviceToHost, ctx->stream));
         if (seen_ids)
             NB_HIP(ctx, hipMemcpyAsync(seen_ids + at * width, ctx->seen_ids.p, (size_t)cnt * width * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+// ---- gravity from located vision (DESIGN.md section 14.2): the context's entries ----------------------------------------------------------
+NB_EXPORT int nb_scenes_step_nbody_located(nb_scenes *ctx, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
+{
+    static const char fn[] = "nb_scenes_step_nbody_located";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    if (rc == NB_OK) rc = located_cp_check(fn, cp16, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
+    if (rc != NB_OK) return rc;
+    if (k == 0) return NB_OK;
+    const size_t records = (size_t)ctx->scenes * ctx->n;
+    NB_HIP(ctx, ctx->pos_alt.reserve(records));
+    NB_HIP(ctx, ctx->vel_alt.reserve(records));
+    RoctxRange range(fn);
+    for (uint32_t s = 0; s < k; ++s) {
+        rc = scenes_stage_eyes(ctx, up_xyz, cp16);
+        if (rc != NB_OK) return rc;
+        nbk::ScenesLocatedArgs a = scenes_located_args(ctx->p, ctx->n, 0u, (uint32_t)records, ctx->cams.p, ctx->inst.p, up_xyz, cp16, width);
+        a.pos_in = ctx->pos.p, a.vel_in = ctx->vel.p, a.pos_out = ctx->pos_alt.p, a.vel_out = ctx->vel_alt.p;
+        NB_HIP(ctx, nbk::launch_scenes_nbody_located(a, ctx->stream));
+        ctx->pos.swap(ctx->pos_alt);
+        ctx->vel.swap(ctx->vel_alt);
+        ctx->steps++;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_eyes_located(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
+                                     uint32_t width, uint32_t *seen_count, uint32_t *seen_ids, float *seen_depth, uint32_t *seen_col,
+                                     float *seen_rel)
+{
+    static const char fn[] = "nb_scenes_eyes_located";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    if (rc == NB_OK) rc = located_cp_check(fn, cp16, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
+        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
+        return NB_ERR_INVALID;
+    }
+    const size_t eyes = (size_t)scene_count * ctx->n, cells = eyes * width;
+    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
+    const ByteRange out[5] = {{seen_count, eyes * 4u}, {seen_ids, cells * 4u}, {seen_depth, cells * 4u}, {seen_col, cells * 4u},
+                              {seen_rel, cells * 16u}};
+    rc = outputs_check(fn, out, 0x1Fu, kNoScenesLocatedOutputs, false, in, 2, kScenesSeenAlias, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
+    if (rc != NB_OK) return rc;
+    if (scene_count == 0) return NB_OK;
+    // scenes per launch: the most whose lists (4 bytes a slot of ids, depth and col, 16 of rel, counting the lists asked for, and 4
+    // bytes of count an eye: 28 width + 4 bytes with all five) stay at or below 64 MiB, one at least
+    const size_t slot = (seen_ids ? 4u : 0u) + (seen_depth ? 4u : 0u) + (seen_col ? 4u : 0u) + (seen_rel ? 16u : 0u);
+    const size_t per_scene = (size_t)ctx->n * ((size_t)width * slot + 4u);
+    const uint32_t per = (uint32_t)std::min<size_t>(scene_count, std::max<size_t>(1, ((size_t)64 << 20) / per_scene));
+    const size_t per_cells = (size_t)per * ctx->n * width;
+    NB_HIP(ctx, ctx->seen_count.reserve((size_t)per * ctx->n));
+    if (seen_ids) NB_HIP(ctx, ctx->seen_ids.reserve(per_cells));
+    if (seen_depth) NB_HIP(ctx, ctx->seen_depth.reserve(per_cells));
+    if (seen_col) NB_HIP(ctx, ctx->seen_col.reserve(per_cells));
+    if (seen_rel) NB_HIP(ctx, ctx->seen_rel.reserve(per_cells));
+    rc = scenes_stage_eyes(ctx, up_xyz, cp16);
+    if (rc != NB_OK) return rc;
+    for (uint32_t s0 = 0; s0 < scene_count; s0 += per) {
+        const uint32_t cnt = std::min(per, scene_count - s0) * ctx->n, first_eye = (first_scene + s0) * ctx->n;
+        const size_t at = (size_t)s0 * ctx->n, words = (size_t)cnt * width * 4u;
+        nbk::ScenesLocatedArgs a = scenes_located_args(ctx->p, ctx->n, first_eye, cnt, ctx->cams.p, ctx->inst.p, up_xyz, cp16, width);
+        a.vel_in = ctx->vel.p;
+        a.seen_count = ctx->seen_count.p, a.seen_ids = seen_ids ? ctx->seen_ids.p : nullptr;
+        a.seen_depth = seen_depth ? ctx->seen_depth.p : nullptr, a.seen_col = seen_col ? ctx->seen_col.p : nullptr;
+        a.seen_rel = seen_rel ? ctx->seen_rel.p : nullptr;
+        NB_HIP(ctx, nbk::launch_scenes_located(a, ctx->stream));
+        if (seen_count) NB_HIP(ctx, hipMemcpyAsync(seen_count + at, ctx->seen_count.p, (size_t)cnt * 4u, hipMemcpyDeviceToHost, ctx->stream));
+        if (seen_ids) NB_HIP(ctx, hipMemcpyAsync(seen_ids + at * width, ctx->seen_ids.p, words, hipMemcpyDeviceToHost, ctx->stream));
+        if (seen_depth) NB_HIP(ctx, hipMemcpyAsync(seen_depth + at * width, ctx->seen_depth.p, words, hipMemcpyDeviceToHost, ctx->stream));
+        if (seen_col) NB_HIP(ctx, hipMemcpyAsync(seen_col + at * width, ctx->seen_col.p, words, hipMemcpyDeviceToHost, ctx->stream));
+        if (seen_rel) NB_HIP(ctx, hipMemcpyAsync(seen_rel + at * width * 4u, ctx->seen_rel.p, words * 4u, hipMemcpyDeviceToHost, ctx->stream));
     }
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;

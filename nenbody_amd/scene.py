@@ -493,6 +493,32 @@ class SceneBatch:
                                                   count.ctypes.data, ids.ctypes.data))
         return count, ids
 
+    def step_nbody_located(self, k: int = 1, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None) -> None:
+        """k update_instance_nbody of every scene from vision alone (nb_scenes_step_nbody_located): the bits
+        :meth:`Scene.step_nbody_located_n` gives each scene, one fused launch per step for the whole batch.  ``cp``: the eyes' camera
+        constant, a perspective constant as :func:`camera_constant` forms it; None: :func:`eye_constant`."""
+        upv, cpm = self._eye_setup(width, up, cp)
+        self._check(self._lib.nb_scenes_step_nbody_located(self._ctx, int(k), upv.ctypes.data, cpm.ctypes.data, width))
+
+    def located(self, first_scene: int = 0, scene_count: Optional[int] = None, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None):
+        """The located sets :meth:`step_nbody_located` folds over (nb_scenes_eyes_located) for scenes [first_scene, first_scene +
+        scene_count) of the current state.  Returns (count uint32 (S, n), ids uint32 (S, n, width), depth float32 (S, n, width), col
+        uint32 (S, n, width), rel float32 (S, n, width, 4)): the words of :meth:`Scene.located` per scene, padding included, without
+        its column counts, which the batch's step does not keep."""
+        if scene_count is None:
+            scene_count = self.scenes - first_scene
+        if first_scene < 0 or scene_count < 0:
+            raise ValueError("first_scene and scene_count must be >= 0")
+        upv, cpm = self._eye_setup(width, up, cp)
+        shape = (scene_count, self.n, max(int(width), 0))
+        count = np.empty(shape[:2], np.uint32)
+        ids, depth, col = np.empty(shape, np.uint32), np.empty(shape, np.float32), np.empty(shape, np.uint32)
+        rel = np.empty(shape + (4,), np.float32)
+        self._check(self._lib.nb_scenes_eyes_located(self._ctx, first_scene, scene_count, upv.ctypes.data, cpm.ctypes.data, width,
+                                                     count.ctypes.data, ids.ctypes.data, depth.ctypes.data, col.ctypes.data,
+                                                     rel.ctypes.data))
+        return count, ids, depth, col, rel
+
     def _download(self, what: int) -> np.ndarray:
         out = np.empty((self.scenes, self.n, 4, 4) if what == 2 else (self.scenes, self.n, 3), np.float32)
         args = [None, None, None]
