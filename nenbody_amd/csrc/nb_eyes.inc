@@ -128,6 +128,51 @@ __device__ __forceinline__ float4 eye_shade(uint64_t key, uint32_t c, const floa
 }
 
 #ifdef __HIPCC__
+// What eye_row_fill leaves to the kind of row: how many columns of a span its own lane walks, that lane's call at one of them, and
+// the wave's walk over a span handed to it (b.lo: the first column left).  Here one sample per column, a column per lane.
+struct EyeCover1 {
+    static constexpr uint32_t kOwnCols = kEyeOwnCols;
+    static __device__ __forceinline__ void own(uint64_t *keys, uint32_t c, const EyeSeg &s, uint32_t j) { eye_cover(keys, c, s, j); }
+    static __device__ __forceinline__ void wave(uint64_t *keys, uint32_t lane, const EyeSeg &b, uint32_t bj)
+    {
+        for (uint32_t c = b.lo + lane; c < b.hi; c += 64u) eye_cover(keys, c, b, bj);
+    }
+};
+
+// The row of one eye, its keys cleared and a barrier behind the clearing: every body j < n_total of `inst` but `self` (unless
+// see_self) into `keys`.  The ONE copy of the loop: eyes_kernel, eyes_msaa_kernel and the two scenes kernels (nb_scenes_seen.inc,
+// nb_scenes_located.inc: see_self a literal 0u, inst the scene's) call it from workgroups of LANES lanes, all lanes together.
+template <int LANES, class Cover>
+__device__ __forceinline__ void eye_row_fill(uint64_t *keys, const float *C, const float4 *__restrict__ inst, uint32_t n_total, uint32_t self,
+                                             uint32_t see_self, float h, uint32_t width)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    for (uint32_t j0 = 0; j0 < n_total; j0 += LANES) {   // every lane of the workgroup runs every pass (the wave loops below)
+        const uint32_t j = j0 + tid;
+        float P[3][4] = {};
+        bool live = j < n_total && (see_self || j != self);
+        if (live) live = raster_vertices_culled(C, inst, j, P);   // a body wholly behind the eye stops at its z rows
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            EyeSeg s{};
+            const bool has = live && eye_edge(P[k], P[k == 2 ? 0 : k + 1], h, width, s);   // [s.lo, s.hi) holds every covered sample's column too
+            uint32_t rest = 0;   // first column left to the wave (rest < s.hi: some are)
+            if (has) {
+                const uint32_t own = s.hi - s.lo < Cover::kOwnCols ? s.hi : s.lo + Cover::kOwnCols;
+                for (uint32_t c = s.lo; c < own; ++c) Cover::own(keys, c, s, j);
+                rest = own;
+            }
+            uint64_t wide = __ballot(has && rest < s.hi);
+            while (wide) {
+                const int src = __ffsll((unsigned long long)wide) - 1;
+                wide &= wide - 1;
+                const EyeSeg b = eye_seg_bcast(s, rest, src);
+                Cover::wave(keys, lane, b, eye_bcast(j, src));
+            }
+        }
+    }
+}
+
 // kColour = false: ids / depth alone (nb_eyes, nb_launch_eyes).  kColour = true: the shading pass too, while the eye's keys are still
 // in LDS -- a lane per column -- with T behind the keys in LDS (width * 8 + 1024 bytes); rgba is a float4 row, bgra8 a uint32 row.
 template <bool kColour>
@@ -144,39 +189,14 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_kernel(uint32_t n_total, uint3
         enc = reinterpret_cast<float *>(eye_keys + width);
         enc[threadIdx.x] = kSrgbEncodeT[threadIdx.x];   // (the first barrier below orders it)
     }
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t tid = threadIdx.x;
     const float h = (float)width * 0.5f;     // exact
     for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
         for (uint32_t c = tid; c < width; c += kEyeBlock) eye_keys[c] = ~0ull;
         __syncthreads();
         float C[16];
         raster_load16(cams + (size_t)e * 4, C);
-        const uint32_t self = first + e;
-        for (uint32_t j0 = 0; j0 < n_total; j0 += kEyeBlock) {   // every lane of the workgroup runs every pass (the wave loops below)
-            const uint32_t j = j0 + tid;
-            float P[3][4] = {};
-            bool live = j < n_total && (see_self || j != self);
-            if (live) live = raster_vertices_culled(C, inst, j, P);   // a body wholly behind the eye stops at its z rows
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                EyeSeg s{};
-                const bool has = live && eye_edge(P[k], P[k == 2 ? 0 : k + 1], h, width, s);
-                uint32_t rest = 0;   // first column left to the wave (rest < s.hi: some are)
-                if (has) {
-                    const uint32_t own = s.hi - s.lo < kEyeOwnCols ? s.hi : s.lo + kEyeOwnCols;
-                    for (uint32_t c = s.lo; c < own; ++c) eye_cover(eye_keys, c, s, j);
-                    rest = own;
-                }
-                uint64_t wide = __ballot(has && rest < s.hi);
-                while (wide) {
-                    const int src = __ffsll((unsigned long long)wide) - 1;
-                    wide &= wide - 1;
-                    const EyeSeg b = eye_seg_bcast(s, rest, src);
-                    const uint32_t bj = eye_bcast(j, src);
-                    for (uint32_t c = b.lo + lane; c < b.hi; c += 64u) eye_cover(eye_keys, c, b, bj);
-                }
-            }
-        }
+        eye_row_fill<kEyeBlock, EyeCover1>(eye_keys, C, inst, n_total, first + e, see_self, h, width);
         __syncthreads();
         for (uint32_t c = tid; c < width; c += kEyeBlock) {   // coalesced rows of ids and depths
             const uint64_t key = eye_keys[c];

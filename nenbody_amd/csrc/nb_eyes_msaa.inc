@@ -1,8 +1,9 @@
 // nb_eyes_msaa.inc -- every entity's eye view through 8 samples per column, resolved (DESIGN.md section 10, steps M1-M5): what the
 // reference's eye targets hold with msaa_samples = 8 (src/main.rs:652; sample_count, :263; resolve_target, :547, :611).
 // Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit after nb_frame.inc.  The edge is nb_eyes.inc's (eye_edge,
-// EyeSeg, eye_key_load, eye_seg_bcast); the vertex products, the depth of a parameter, the fragment, the mean, the sample offsets and
-// the sRGB bytes are nb_raster.inc's; this file adds the cover of a sample, the 8-sample shade and the kernel.  Launcher: nb_eyes.h.
+// EyeSeg, eye_key_load) and so is the loop over the bodies (eye_row_fill, with this file's EyeCover8); the vertex products, the depth
+// of a parameter, the fragment, the mean, the sample offsets and the sRGB bytes are nb_raster.inc's; this file adds the cover of a
+// sample, the 8-sample shade and the kernel.  Launcher: nb_eyes.h.
 //
 // The rule continues section 10's steps 1-11, one binary32 operation per step in the order written (-ffp-contract=off, IEEE '/');
 // tests/eyes_msaa_restatement.py states it again in numpy and the GPU tests compare every bit:
@@ -87,6 +88,20 @@ __device__ __forceinline__ float4 eye_msaa_shade(const uint64_t *keys, uint32_t 
 }
 
 #ifdef __HIPCC__
+// eye_row_fill's cover for 8 samples per column: the owning lane takes a column's eight samples, the wave 8 columns x 8 samples
+struct EyeCover8 {
+    static constexpr uint32_t kOwnCols = kMsaaOwnCols;
+    static __device__ __forceinline__ void own(uint64_t *keys, uint32_t c, const EyeSeg &s, uint32_t j)
+    {
+#pragma unroll
+        for (uint32_t m = 0; m < kMsaaSamples; ++m) eye_msaa_cover(keys, c, m, s, j);
+    }
+    static __device__ __forceinline__ void wave(uint64_t *keys, uint32_t lane, const EyeSeg &b, uint32_t bj)
+    {
+        for (uint32_t c = b.lo + (lane >> 3); c < b.hi; c += 8u) eye_msaa_cover(keys, c, lane & 7u, b, bj);   // c < width
+    }
+};
+
 __global__ __launch_bounds__(kEyeBlock) void eyes_msaa_kernel(uint32_t n_total, uint32_t first, uint32_t count,
                                                              const float4 *__restrict__ cams, const float4 *__restrict__ inst,
                                                              uint32_t width, uint32_t see_self, const float4 *__restrict__ skin,
@@ -99,41 +114,14 @@ __global__ __launch_bounds__(kEyeBlock) void eyes_msaa_kernel(uint32_t n_total, 
     const uint32_t cells = width * kMsaaSamples;
     float *enc = reinterpret_cast<float *>(msaa_keys + cells);
     enc[threadIdx.x] = kSrgbEncodeT[threadIdx.x];   // (the first barrier below orders it)
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t tid = threadIdx.x;
     const float h = (float)width * 0.5f;      // exact
     for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
         for (uint32_t i = tid; i < cells; i += kEyeBlock) msaa_keys[i] = ~0ull;
         __syncthreads();
         float C[16];
         raster_load16(cams + (size_t)e * 4, C);
-        const uint32_t self = first + e;
-        for (uint32_t j0 = 0; j0 < n_total; j0 += kEyeBlock) {   // every lane of the workgroup runs every pass (the wave loops below)
-            const uint32_t j = j0 + tid;
-            float P[3][4] = {};
-            bool live = j < n_total && (see_self || j != self);
-            if (live) live = raster_vertices_culled(C, inst, j, P);   // a body wholly behind the eye stops at its z rows
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                EyeSeg s{};
-                const bool has = live && eye_edge(P[k], P[k == 2 ? 0 : k + 1], h, width, s);   // [s.lo, s.hi) holds every covered sample's column too
-                uint32_t rest = 0;   // first column left to the wave (rest < s.hi: some are)
-                if (has) {
-                    const uint32_t own = s.hi - s.lo < kMsaaOwnCols ? s.hi : s.lo + kMsaaOwnCols;
-                    for (uint32_t c = s.lo; c < own; ++c)
-#pragma unroll
-                        for (uint32_t m = 0; m < kMsaaSamples; ++m) eye_msaa_cover(msaa_keys, c, m, s, j);
-                    rest = own;
-                }
-                uint64_t wide = __ballot(has && rest < s.hi);
-                while (wide) {
-                    const int src = __ffsll((unsigned long long)wide) - 1;
-                    wide &= wide - 1;
-                    const EyeSeg b = eye_seg_bcast(s, rest, src);
-                    const uint32_t bj = eye_bcast(j, src);
-                    for (uint32_t c = b.lo + (lane >> 3); c < b.hi; c += 8u) eye_msaa_cover(msaa_keys, c, lane & 7u, b, bj);   // c < width
-                }
-            }
-        }
+        eye_row_fill<kEyeBlock, EyeCover8>(msaa_keys, C, inst, n_total, first + e, see_self, h, width);
         __syncthreads();
         const size_t row = (size_t)e * cells;
         if (ids8 || depth8)

@@ -89,8 +89,8 @@ static_assert(kMsaaOffsets16 == sample_nibbles(kEyeSampleX16) && kFrameMsaaOffse
 #include "nb_seen.inc"        // the seen set of every eye row and the boids step over it: likewise; uses nb_boids.inc's accumulators and epilogue
 #include "nb_located.inc"     // the located seen sets and the gravity step over them: likewise; uses nb_seen.inc's constants and nb_nbody_strict.inc's integrate
 #include "nb_scenes.inc"      // scene batches, one workgroup per scene: likewise; uses nb_nbody_strict.inc's folds and nb_boids.inc's pair and epilogue
-#include "nb_scenes_seen.inc" // the seen boids step of a batch, one workgroup per eye: likewise; uses nb_eyes.inc's loop body, nb_seen.inc's pair and nb_boids.inc's epilogue
-#include "nb_scenes_located.inc" // gravity from located vision for a batch, one workgroup per eye: likewise; uses nb_eyes.inc's loop body, nb_located.inc's normalize and nb_nbody_strict.inc's integrate
+#include "nb_scenes_seen.inc" // the seen boids step of a batch, one workgroup per eye: likewise; uses nb_eyes.inc's eye_row_fill, nb_seen.inc's pair and nb_boids.inc's epilogue
+#include "nb_scenes_located.inc" // gravity from located vision for a batch, one workgroup per eye: likewise; uses nb_eyes.inc's eye_row_fill, nb_located.inc's L2-L4 and G2 helpers, nb_scenes_seen.inc's bitmap helpers and nb_nbody_strict.inc's integrate
 #else
 #include "nb_nbody_pc.inc"
 #include "nb_nbody_bc.inc"

@@ -39,6 +39,42 @@ __device__ __forceinline__ void loc_normalize3(float &x, float &y, float &z)
     z = z * s;
 }
 
+// The three below take any argument struct with the fields they read: LocatedArgs, LocatedStepArgs and nb_scenes.h's ScenesLocatedArgs.
+// L3: f = normalize(d), s = normalize(f x up)
+template <class Args>
+__device__ __forceinline__ void located_basis(const Args &a, const float4 &d, float &fx, float &fy, float &fz, float &sx, float &sy, float &sz)
+{
+    float f0 = d.x, f1 = d.y, f2 = d.z;
+    loc_normalize3(f0, f1, f2);                                                       // f = dir.normalize()
+    const float a0 = f1 * a.uz, a1 = f2 * a.uy, b0 = f2 * a.ux, b1 = f0 * a.uz, c0 = f0 * a.uy, c1 = f1 * a.ux;
+    float s0 = a0 - a1, s1 = b0 - b1, s2 = c0 - c1;                                   // s = f.cross(up)
+    loc_normalize3(s0, s1, s2);
+    fx = f0, fy = f1, fz = f2, sx = s0, sy = s1, sz = s2;
+}
+
+// L2 and L4 for one member: column col, depth bits dbits, f and s of the eye, h = width / 2
+template <class Args>
+__device__ __forceinline__ float4 located_rel(const Args &a, float h, uint32_t col, uint32_t dbits, float fx, float fy, float fz, float sx,
+                                              float sy, float sz)
+{
+    const float xc = (float)col + 0.5f;                                               // L2
+    const float xn = (xc - h) / h;
+    const float r = a.cp14 / (__uint_as_float(dbits) + a.cp10);
+    const float xv = (xn * r) / a.cp0;
+    const float p0 = r * fx, p1 = r * fy, p2 = r * fz, q0 = xv * sx, q1 = xv * sy, q2 = xv * sz;
+    return make_float4(p0 + q0, p1 + q1, p2 + q2, r);                                 // L4
+}
+
+// G2 for one located point: dist and the three quotients, as pair_strict<IEEE = true> forms them
+template <class Args>
+__device__ __forceinline__ void located_quotients(const Args &a, const float4 &vec, float &qx, float &qy, float &qz)
+{
+    const float xx = vec.x * vec.x, yy = vec.y * vec.y, zz = vec.z * vec.z;
+    const float dist = ((xx + yy) + zz) + a.bias;                                     // main.rs:429
+    const float nx = vec.x * a.G, ny = vec.y * a.G, nz = vec.z * a.G;
+    qx = nx / dist, qy = ny / dist, qz = nz / dist;                                   // main.rs:430
+}
+
 __global__ __launch_bounds__(kLocBlock) void located_kernel(LocatedArgs a)
 {
     extern __shared__ uint32_t loc_lds[];
@@ -69,23 +105,13 @@ __global__ __launch_bounds__(kLocBlock) void located_kernel(LocatedArgs a)
         }
         __syncthreads();
         const float4 d = a.dirs[e];
-        float fx = d.x, fy = d.y, fz = d.z;
-        loc_normalize3(fx, fy, fz);                                                   // L3: f = dir.normalize()
-        const float a0 = fy * a.uz, a1 = fz * a.uy, b0 = fz * a.ux, b1 = fx * a.uz, c0 = fx * a.uy, c1 = fy * a.ux;
-        float sx = a0 - a1, sy = b0 - b1, sz = c0 - c1;                               // s = f.cross(up)
-        loc_normalize3(sx, sy, sz);
+        float fx, fy, fz, sx, sy, sz;
+        located_basis(a, d, fx, fy, fz, sx, sy, sz);
         for (uint32_t k = tid; k < a.width; k += kLocBlock) {
             uint32_t col = kSeenNone;
             float4 rel = make_float4(0.f, 0.f, 0.f, 0.f);                             // L5, and L1's slot without a column
             if (k < cnt) col = l_col[k];
-            if (col != kSeenNone) {
-                const float xc = (float)col + 0.5f;                                   // L2
-                const float xn = (xc - h) / h;
-                const float r = a.cp14 / (__uint_as_float(l_bits[k]) + a.cp10);
-                const float xv = (xn * r) / a.cp0;
-                const float p0 = r * fx, p1 = r * fy, p2 = r * fz, q0 = xv * sx, q1 = xv * sy, q2 = xv * sz;
-                rel = make_float4(p0 + q0, p1 + q1, p2 + q2, r);                      // L4
-            }
+            if (col != kSeenNone) rel = located_rel(a, h, col, l_bits[k], fx, fy, fz, sx, sy, sz);
             if (a.seen_col) a.seen_col[row + k] = col;
             a.seen_rel[row + k] = rel;
         }
@@ -104,13 +130,9 @@ __global__ __launch_bounds__(kBlock) void nbody_located_kernel(LocatedStepArgs a
     const uint32_t len = seen_count[l] < stride ? seen_count[l] : stride;
     float sx = 0.f, sy = 0.f, sz = 0.f;                                               // main.rs:425
     for (uint32_t k = 0; k < len; ++k) {
-        const float4 vec = list[k];                                                   // main.rs:428, from the row
-        const float xx = vec.x * vec.x, yy = vec.y * vec.y, zz = vec.z * vec.z;
-        const float dist = ((xx + yy) + zz) + a.bias;                                 // main.rs:429
-        const float nx = vec.x * a.G, ny = vec.y * a.G, nz = vec.z * a.G;
-        sx = sx + nx / dist;                                                          // main.rs:430
-        sy = sy + ny / dist;
-        sz = sz + nz / dist;
+        float qx, qy, qz;
+        located_quotients(a, list[k], qx, qy, qz);                                    // main.rs:428-430, the vector from the row
+        sx = sx + qx, sy = sy + qy, sz = sz + qz;                                     // in slot order
     }
     integrate(p, v, sx, sy, sz, a.dt);                                                // main.rs:434, 436
     a.pos_out[n] = p;

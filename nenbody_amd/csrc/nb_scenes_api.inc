@@ -26,7 +26,8 @@ static int scenes_shape_check(const char *fn, uint32_t scenes, uint32_t n, std::
     return NB_OK;
 }
 
-// gravity: STRICT only; the tile is validated as elsewhere and otherwise unused
+// the nb_params of a batch -- the stateless gravity entry's and the context's, whose located step takes dt, G and bias from them too --:
+// a mode there is, then STRICT only (NB_MODE_FAST is NB_ERR_UNSUPPORTED); the tile is validated as elsewhere and otherwise unused
 static int scenes_params_check(const char *fn, const nb_params &p, std::string *err)
 {
     if (p.mode != NB_MODE_STRICT && p.mode != NB_MODE_FAST) {
@@ -53,13 +54,23 @@ static int scenes_boids_params_check(const char *fn, const nb_boids_params &p, s
     return NB_OK;
 }
 
+// every pointer of the list 16-byte aligned; `subject` names them in the message
+static int scenes_aligned16_check(const char *fn, std::initializer_list<const void *> ptrs, const char *subject, std::string *err)
+{
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= (uintptr_t)p;
+    if (bits & 15u) {
+        *err = std::string(fn) + ": " + subject + " must be 16-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
 // the records of a stateless entry: there, 16-byte aligned, not overlapping
 static int scenes_records_check(const char *fn, uint32_t scenes, uint32_t n, const void *pos, const void *vel, std::string *err)
 {
-    if (((uintptr_t)pos | (uintptr_t)vel) & 15u) {
-        *err = std::string(fn) + ": pos and vel must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
+    const int rc = scenes_aligned16_check(fn, {pos, vel}, "pos and vel", err);
+    if (rc != NB_OK) return rc;
     const size_t bytes = (size_t)scenes * n * sizeof(float4);
     if (ranges_overlap(pos, bytes, vel, bytes)) {
         *err = std::string(fn) + ": pos and vel must not overlap";
@@ -141,6 +152,41 @@ static int scenes_width_check(const char *fn, uint32_t width, std::string *err)
     return NB_OK;
 }
 
+// what the four stateless vision entries check behind their null test: the batch's shape, the width and, where the entry locates
+// (cp16 given), a constant that L2 can invert
+static int scenes_vision_check(const char *fn, uint32_t scenes, uint32_t n, uint32_t width, const float *cp16, std::string *err)
+{
+    int rc = scenes_shape_check(fn, scenes, n, err);
+    if (rc == NB_OK) rc = scenes_width_check(fn, width, err);
+    if (rc == NB_OK && cp16) rc = located_cp_check(fn, cp16, err);
+    return rc;
+}
+
+// eyes [first_eye, first_eye + count) of the two stateless sets entries lie in the batch
+static int scenes_eye_range_check(const char *fn, uint32_t scenes, uint32_t n, uint32_t first_eye, uint32_t count, std::string *err)
+{
+    if ((uint64_t)first_eye + count > (uint64_t)scenes * n) {
+        *err = std::string(fn) + ": eyes [first_eye, first_eye + count) exceed the batch";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// the buffers of a stateless vision step: 16-byte aligned, pos_out and vel_out clear of each other and of every input (up_xyz and
+// cp16: the located step's, NULL otherwise)
+static int scenes_step_buffers_check(const char *fn, size_t records, const void *cams_16, const void *inst_16, const void *pos_in,
+                                     const void *vel_in, const void *pos_out, const void *vel_out, const float *up_xyz, const float *cp16,
+                                     std::string *err)
+{
+    const int rc = scenes_aligned16_check(fn, {cams_16, inst_16, pos_in, vel_in, pos_out, vel_out}, "cams_16, inst_16 and the four record buffers", err);
+    if (rc != NB_OK) return rc;
+    const size_t bytes = records * sizeof(float4);
+    const ByteRange in[6] = {{cams_16, bytes * 4u}, {inst_16, bytes * 4u},          {pos_in, bytes},
+                             {vel_in, bytes},       {up_xyz, 3 * sizeof(float)},    {cp16, 16 * sizeof(float)}};
+    const ByteRange out[2] = {{pos_out, bytes}, {vel_out, bytes}};
+    return outputs_check(fn, out, 0x3u, "", false, in, 6, kScenesSeenAlias, err);
+}
+
 NB_EXPORT int nb_scenes_boids_seen_step_launch(const nb_boids_params *params, uint32_t scenes, uint32_t n, const void *cams_16,
                                                const void *inst_16, uint32_t width, const void *pos_in, const void *vel_in, void *pos_out,
                                                void *vel_out, void *stream)
@@ -151,18 +197,10 @@ NB_EXPORT int nb_scenes_boids_seen_step_launch(const nb_boids_params *params, ui
         return NB_ERR_INVALID;
     }
     const nb_boids_params p = boids_params_or_default(params);
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
-    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
+    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
     if (rc == NB_OK) rc = scenes_boids_params_check(fn, p, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    if (((uintptr_t)cams_16 | (uintptr_t)inst_16 | (uintptr_t)pos_in | (uintptr_t)vel_in | (uintptr_t)pos_out | (uintptr_t)vel_out) & 15u) {
-        g_tls_error = std::string(fn) + ": cams_16, inst_16 and the four record buffers must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    const size_t records = (size_t)scenes * n, bytes = records * sizeof(float4);
-    const ByteRange in[4] = {{cams_16, bytes * 4u}, {inst_16, bytes * 4u}, {pos_in, bytes}, {vel_in, bytes}};
-    const ByteRange out[2] = {{pos_out, bytes}, {vel_out, bytes}};
-    rc = outputs_check(fn, out, 0x3u, "", false, in, 4, kScenesSeenAlias, &g_tls_error);
+    if (rc == NB_OK)
+        rc = scenes_step_buffers_check(fn, (size_t)scenes * n, cams_16, inst_16, pos_in, vel_in, pos_out, vel_out, nullptr, nullptr, &g_tls_error);
     nbk::BoidsArgs c;
     uint32_t tile = 0;
     if (rc == NB_OK) rc = make_boids_args(p, n, 0, n, &c, &tile, &g_tls_error);
@@ -181,17 +219,10 @@ NB_EXPORT int nb_scenes_seen_launch(uint32_t scenes, uint32_t n, uint32_t first_
         g_tls_error = std::string(fn) + ": cams_16 and inst_16 must be non-null";
         return NB_ERR_INVALID;
     }
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
-    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
+    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned16_check(fn, {cams_16, inst_16}, "cams_16 and inst_16", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_eye_range_check(fn, scenes, n, first_eye, count, &g_tls_error);
     if (rc != NB_OK) return rc;
-    if (((uintptr_t)cams_16 | (uintptr_t)inst_16) & 15u) {
-        g_tls_error = std::string(fn) + ": cams_16 and inst_16 must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if ((uint64_t)first_eye + count > (uint64_t)scenes * n) {
-        g_tls_error = std::string(fn) + ": eyes [first_eye, first_eye + count) exceed the batch";
-        return NB_ERR_INVALID;
-    }
     const size_t matrices = (size_t)scenes * n * 16 * sizeof(float);
     const ByteRange in[2] = {{cams_16, matrices}, {inst_16, matrices}};
     const ByteRange out[2] = {{seen_count, (size_t)count * 4u}, {seen_ids, (size_t)count * width * 4u}};
@@ -231,19 +262,9 @@ NB_EXPORT int nb_scenes_nbody_located_step_launch(const nb_params *params, uint3
         return NB_ERR_INVALID;
     }
     const nb_params p = params_or_default(params);
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
-    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
-    if (rc == NB_OK) rc = located_cp_check(fn, cp16, &g_tls_error);
-    if (rc != NB_OK) return rc;
-    if (((uintptr_t)cams_16 | (uintptr_t)inst_16 | (uintptr_t)pos_in | (uintptr_t)vel_in | (uintptr_t)pos_out | (uintptr_t)vel_out) & 15u) {
-        g_tls_error = std::string(fn) + ": cams_16, inst_16 and the four record buffers must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    const size_t records = (size_t)scenes * n, bytes = records * sizeof(float4);
-    const ByteRange in[6] = {{cams_16, bytes * 4u}, {inst_16, bytes * 4u},          {pos_in, bytes},
-                             {vel_in, bytes},       {up_xyz, 3 * sizeof(float)},    {cp16, 16 * sizeof(float)}};
-    const ByteRange out[2] = {{pos_out, bytes}, {vel_out, bytes}};
-    rc = outputs_check(fn, out, 0x3u, "", false, in, 6, kScenesSeenAlias, &g_tls_error);
+    int rc = scenes_vision_check(fn, scenes, n, width, cp16, &g_tls_error);
+    const size_t records = (size_t)scenes * n;
+    if (rc == NB_OK) rc = scenes_step_buffers_check(fn, records, cams_16, inst_16, pos_in, vel_in, pos_out, vel_out, up_xyz, cp16, &g_tls_error);
     if (rc == NB_OK) rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
     nbk::ScenesLocatedArgs a = scenes_located_args(p, n, 0u, (uint32_t)records, cams_16, inst_16, up_xyz, cp16, width);
@@ -261,18 +282,10 @@ NB_EXPORT int nb_scenes_located_launch(uint32_t scenes, uint32_t n, uint32_t fir
         g_tls_error = std::string(fn) + ": null argument";
         return NB_ERR_INVALID;
     }
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
-    if (rc == NB_OK) rc = scenes_width_check(fn, width, &g_tls_error);
-    if (rc == NB_OK) rc = located_cp_check(fn, cp16, &g_tls_error);
+    int rc = scenes_vision_check(fn, scenes, n, width, cp16, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned16_check(fn, {cams_16, inst_16, vel_in, seen_rel}, "cams_16, inst_16, vel_in and seen_rel", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_eye_range_check(fn, scenes, n, first_eye, count, &g_tls_error);
     if (rc != NB_OK) return rc;
-    if (((uintptr_t)cams_16 | (uintptr_t)inst_16 | (uintptr_t)vel_in | (uintptr_t)seen_rel) & 15u) {
-        g_tls_error = std::string(fn) + ": cams_16, inst_16, vel_in and seen_rel must be 16-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if ((uint64_t)first_eye + count > (uint64_t)scenes * n) {
-        g_tls_error = std::string(fn) + ": eyes [first_eye, first_eye + count) exceed the batch";
-        return NB_ERR_INVALID;
-    }
     const size_t records = (size_t)scenes * n, cells = (size_t)count * width;
     const ByteRange in[5] = {{cams_16, records * 64u}, {inst_16, records * 64u}, {vel_in, records * 16u}, {up_xyz, 3 * sizeof(float)},
                              {cp16, 16 * sizeof(float)}};
@@ -302,7 +315,7 @@ struct nb_scenes {
     DeviceBuffer<float4> cams;               // 4 * scenes * n records, likewise: every body's eye camera
     DeviceBuffer<uint32_t> seen_count, seen_ids;   // nb_scenes_eyes_seen's lists for one range of scenes, likewise and grown on demand
     DeviceBuffer<uint32_t> seen_depth, seen_col;   // nb_scenes_eyes_located's further lists, likewise: depth bits and columns
-    DeviceBuffer<float4> seen_rel;                 // and its located points
+    DeviceBuffer<uint32_t> seen_rel;               // and its located points, four words a slot
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
@@ -429,6 +442,76 @@ static int scenes_stage_eyes(nb_scenes *ctx, const float *up_xyz, const float *c
     return NB_OK;
 }
 
+// k steps of a controller that sees (sections 14.1, 14.2), the entry's checks behind it: per step the eyes of the current state, ONE
+// fused kernel -- launch(ctx) issues it from pos / vel into pos_alt / vel_alt and returns a status -- and the swap
+template <typename Launch>
+static int scenes_vision_step(nb_scenes *ctx, const char *fn, uint32_t k, const float *up_xyz, const float *cp16, Launch launch)
+{
+    if (k == 0) return NB_OK;
+    const size_t records = (size_t)ctx->scenes * ctx->n;
+    NB_HIP(ctx, ctx->pos_alt.reserve(records));
+    NB_HIP(ctx, ctx->vel_alt.reserve(records));
+    RoctxRange range(fn);
+    for (uint32_t s = 0; s < k; ++s) {
+        int rc = scenes_stage_eyes(ctx, up_xyz, cp16);
+        if (rc == NB_OK) rc = launch(ctx);
+        if (rc != NB_OK) return rc;
+        ctx->pos.swap(ctx->pos_alt);
+        ctx->vel.swap(ctx->vel_alt);
+        ctx->steps++;
+    }
+    return NB_OK;
+}
+
+// One output of nb_scenes_eyes_seen / nb_scenes_eyes_located: the caller's array (NULL: not asked for), the context's buffer behind
+// it and the 4-byte words an eye has in it.  Row 0 of an entry's table is the count, which the kernel writes whether asked for or not.
+struct ScenesEyesOutput {
+    void *host;
+    DeviceBuffer<uint32_t> *dev;
+    size_t words;
+};
+
+// The sets of scenes [first_scene, first_scene + scene_count), the entry's eye set-up checked: the range, the outputs (none_msg: none is
+// asked for) and the state; then the eyes staged once and as many scenes per launch as keep the outputs asked for (4 bytes of count
+// an eye and 4 bytes a word) at or below 64 MiB, one at least.  launch(ctx, first_eye, count) issues the kernel for one such chunk
+// into the context's buffers and returns a status.
+template <int N, typename Launch>
+static int scenes_eyes_download(nb_scenes *ctx, const char *fn, uint32_t first_scene, uint32_t scene_count, const float *up_xyz,
+                                const float *cp16, const ScenesEyesOutput (&out)[N], const char *none_msg, Launch launch)
+{
+    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
+        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
+    ByteRange user[N];
+    for (int r = 0; r < N; ++r) user[r] = {out[r].host, (size_t)scene_count * ctx->n * out[r].words * 4u};
+    int rc = outputs_check(fn, user, (1u << N) - 1u, none_msg, false, in, 2, kScenesSeenAlias, &ctx->err);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
+    if (rc != NB_OK) return rc;
+    if (scene_count == 0) return NB_OK;
+    const auto wanted = [&out](int r) { return r == 0 || out[r].host; };
+    size_t per_eye = 0;
+    for (int r = 0; r < N; ++r) per_eye += wanted(r) ? out[r].words * 4u : 0u;
+    const uint32_t per = (uint32_t)std::min<size_t>(scene_count, std::max<size_t>(1, ((size_t)64 << 20) / (ctx->n * per_eye)));
+    for (int r = 0; r < N; ++r)
+        if (wanted(r)) NB_HIP(ctx, out[r].dev->reserve((size_t)per * ctx->n * out[r].words));
+    rc = scenes_stage_eyes(ctx, up_xyz, cp16);
+    if (rc != NB_OK) return rc;
+    for (uint32_t s0 = 0; s0 < scene_count; s0 += per) {
+        const uint32_t cnt = std::min(per, scene_count - s0) * ctx->n;
+        const size_t at = (size_t)s0 * ctx->n;
+        rc = launch(ctx, (first_scene + s0) * ctx->n, cnt);
+        if (rc != NB_OK) return rc;
+        for (int r = 0; r < N; ++r)
+            if (out[r].host)
+                NB_HIP(ctx, hipMemcpyAsync((uint32_t *)out[r].host + at * out[r].words, out[r].dev->p, cnt * out[r].words * 4u,
+                                           hipMemcpyDeviceToHost, ctx->stream));
+    }
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
 NB_EXPORT int nb_scenes_step_boids_seen(nb_scenes *ctx, uint32_t k, const nb_boids_params *params, const float *up_xyz, const float *cp16,
                                         uint32_t width)
 {
@@ -443,21 +526,11 @@ NB_EXPORT int nb_scenes_step_boids_seen(nb_scenes *ctx, uint32_t k, const nb_boi
     uint32_t tile = 0;
     if (rc == NB_OK) rc = make_boids_args(p, ctx->n, 0, ctx->n, &c, &tile, &ctx->err);
     if (rc != NB_OK) return rc;
-    if (k == 0) return NB_OK;
-    const size_t records = (size_t)ctx->scenes * ctx->n;
-    NB_HIP(ctx, ctx->pos_alt.reserve(records));
-    NB_HIP(ctx, ctx->vel_alt.reserve(records));
-    RoctxRange range(fn);
-    for (uint32_t s = 0; s < k; ++s) {
-        rc = scenes_stage_eyes(ctx, up_xyz, cp16);
-        if (rc != NB_OK) return rc;
+    return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [&c, width](nb_scenes *ctx) -> int {
         c.pos_in = ctx->pos.p, c.vel_in = ctx->vel.p, c.pos_out = ctx->pos_alt.p, c.vel_out = ctx->vel_alt.p;
         NB_HIP(ctx, nbk::launch_scenes_boids_seen(c, ctx->scenes, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width, ctx->stream));
-        ctx->pos.swap(ctx->pos_alt);
-        ctx->vel.swap(ctx->vel_alt);
-        ctx->steps++;
-    }
-    return NB_OK;
+        return NB_OK;
+    });
 }
 
 NB_EXPORT int nb_scenes_eyes_seen(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
@@ -468,35 +541,13 @@ NB_EXPORT int nb_scenes_eyes_seen(nb_scenes *ctx, uint32_t first_scene, uint32_t
     if (rc != NB_OK) return rc;
     rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
     if (rc != NB_OK) return rc;
-    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
-        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
-        return NB_ERR_INVALID;
-    }
-    const size_t eyes = (size_t)scene_count * ctx->n;
-    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
-    const ByteRange out[2] = {{seen_count, eyes * 4u}, {seen_ids, eyes * width * 4u}};
-    rc = outputs_check(fn, out, 0x3u, ": seen_count and seen_ids are both NULL", false, in, 2, kScenesSeenAlias, &ctx->err);
-    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
-    if (rc != NB_OK) return rc;
-    if (scene_count == 0) return NB_OK;
-    // scenes per launch: the most whose lists (4 bytes a slot, 4 bytes of count an eye) stay at or below 64 MiB, one at least
-    const size_t per_scene = (size_t)ctx->n * ((size_t)width * 4u + 4u);
-    const uint32_t per = (uint32_t)std::min<size_t>(scene_count, std::max<size_t>(1, ((size_t)64 << 20) / per_scene));
-    NB_HIP(ctx, ctx->seen_count.reserve((size_t)per * ctx->n));
-    if (seen_ids) NB_HIP(ctx, ctx->seen_ids.reserve((size_t)per * ctx->n * width));
-    rc = scenes_stage_eyes(ctx, up_xyz, cp16);
-    if (rc != NB_OK) return rc;
-    for (uint32_t s0 = 0; s0 < scene_count; s0 += per) {
-        const uint32_t cnt = std::min(per, scene_count - s0) * ctx->n, first_eye = (first_scene + s0) * ctx->n;
-        const size_t at = (size_t)s0 * ctx->n;
+    const ScenesEyesOutput lists[2] = {{seen_count, &ctx->seen_count, 1}, {seen_ids, &ctx->seen_ids, width}};
+    const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
         NB_HIP(ctx, nbk::launch_scenes_seen(ctx->n, first_eye, cnt, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width,
                                             ctx->seen_count.p, seen_ids ? ctx->seen_ids.p : nullptr, ctx->stream));
-        if (seen_count) NB_HIP(ctx, hipMemcpyAsync(seen_count + at, ctx->seen_count.p, (size_t)cnt * 4u, hipMemcpyDeviceToHost, ctx->stream));
-        if (seen_ids)
-            NB_HIP(ctx, hipMemcpyAsync(seen_ids + at * width, ctx->seen_ids.p, (size_t)cnt * width * 4u, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NB_OK;
+        return NB_OK;
+    };
+    return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, lists, ": seen_count and seen_ids are both NULL", launch);
 }
 
 // ---- gravity from located vision (DESIGN.md section 14.2): the context's entries ----------------------------------------------------------
@@ -509,22 +560,13 @@ NB_EXPORT int nb_scenes_step_nbody_located(nb_scenes *ctx, uint32_t k, const flo
     if (rc == NB_OK) rc = located_cp_check(fn, cp16, &ctx->err);
     if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
     if (rc != NB_OK) return rc;
-    if (k == 0) return NB_OK;
-    const size_t records = (size_t)ctx->scenes * ctx->n;
-    NB_HIP(ctx, ctx->pos_alt.reserve(records));
-    NB_HIP(ctx, ctx->vel_alt.reserve(records));
-    RoctxRange range(fn);
-    for (uint32_t s = 0; s < k; ++s) {
-        rc = scenes_stage_eyes(ctx, up_xyz, cp16);
-        if (rc != NB_OK) return rc;
-        nbk::ScenesLocatedArgs a = scenes_located_args(ctx->p, ctx->n, 0u, (uint32_t)records, ctx->cams.p, ctx->inst.p, up_xyz, cp16, width);
+    return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [=](nb_scenes *ctx) -> int {
+        nbk::ScenesLocatedArgs a =
+            scenes_located_args(ctx->p, ctx->n, 0u, ctx->scenes * ctx->n, ctx->cams.p, ctx->inst.p, up_xyz, cp16, width);
         a.pos_in = ctx->pos.p, a.vel_in = ctx->vel.p, a.pos_out = ctx->pos_alt.p, a.vel_out = ctx->vel_alt.p;
         NB_HIP(ctx, nbk::launch_scenes_nbody_located(a, ctx->stream));
-        ctx->pos.swap(ctx->pos_alt);
-        ctx->vel.swap(ctx->vel_alt);
-        ctx->steps++;
-    }
-    return NB_OK;
+        return NB_OK;
+    });
 }
 
 NB_EXPORT int nb_scenes_eyes_located(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
@@ -537,48 +579,19 @@ NB_EXPORT int nb_scenes_eyes_located(nb_scenes *ctx, uint32_t first_scene, uint3
     rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
     if (rc == NB_OK) rc = located_cp_check(fn, cp16, &ctx->err);
     if (rc != NB_OK) return rc;
-    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
-        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
-        return NB_ERR_INVALID;
-    }
-    const size_t eyes = (size_t)scene_count * ctx->n, cells = eyes * width;
-    const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
-    const ByteRange out[5] = {{seen_count, eyes * 4u}, {seen_ids, cells * 4u}, {seen_depth, cells * 4u}, {seen_col, cells * 4u},
-                              {seen_rel, cells * 16u}};
-    rc = outputs_check(fn, out, 0x1Fu, kNoScenesLocatedOutputs, false, in, 2, kScenesSeenAlias, &ctx->err);
-    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
-    if (rc != NB_OK) return rc;
-    if (scene_count == 0) return NB_OK;
-    // scenes per launch: the most whose lists (4 bytes a slot of ids, depth and col, 16 of rel, counting the lists asked for, and 4
-    // bytes of count an eye: 28 width + 4 bytes with all five) stay at or below 64 MiB, one at least
-    const size_t slot = (seen_ids ? 4u : 0u) + (seen_depth ? 4u : 0u) + (seen_col ? 4u : 0u) + (seen_rel ? 16u : 0u);
-    const size_t per_scene = (size_t)ctx->n * ((size_t)width * slot + 4u);
-    const uint32_t per = (uint32_t)std::min<size_t>(scene_count, std::max<size_t>(1, ((size_t)64 << 20) / per_scene));
-    const size_t per_cells = (size_t)per * ctx->n * width;
-    NB_HIP(ctx, ctx->seen_count.reserve((size_t)per * ctx->n));
-    if (seen_ids) NB_HIP(ctx, ctx->seen_ids.reserve(per_cells));
-    if (seen_depth) NB_HIP(ctx, ctx->seen_depth.reserve(per_cells));
-    if (seen_col) NB_HIP(ctx, ctx->seen_col.reserve(per_cells));
-    if (seen_rel) NB_HIP(ctx, ctx->seen_rel.reserve(per_cells));
-    rc = scenes_stage_eyes(ctx, up_xyz, cp16);
-    if (rc != NB_OK) return rc;
-    for (uint32_t s0 = 0; s0 < scene_count; s0 += per) {
-        const uint32_t cnt = std::min(per, scene_count - s0) * ctx->n, first_eye = (first_scene + s0) * ctx->n;
-        const size_t at = (size_t)s0 * ctx->n, words = (size_t)cnt * width * 4u;
+    const ScenesEyesOutput lists[5] = {{seen_count, &ctx->seen_count, 1},     {seen_ids, &ctx->seen_ids, width},
+                                       {seen_depth, &ctx->seen_depth, width}, {seen_col, &ctx->seen_col, width},
+                                       {seen_rel, &ctx->seen_rel, (size_t)width * 4u}};   // 28 width + 4 bytes an eye with all five
+    const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
         nbk::ScenesLocatedArgs a = scenes_located_args(ctx->p, ctx->n, first_eye, cnt, ctx->cams.p, ctx->inst.p, up_xyz, cp16, width);
         a.vel_in = ctx->vel.p;
         a.seen_count = ctx->seen_count.p, a.seen_ids = seen_ids ? ctx->seen_ids.p : nullptr;
         a.seen_depth = seen_depth ? ctx->seen_depth.p : nullptr, a.seen_col = seen_col ? ctx->seen_col.p : nullptr;
-        a.seen_rel = seen_rel ? ctx->seen_rel.p : nullptr;
+        a.seen_rel = seen_rel ? (float4 *)ctx->seen_rel.p : nullptr;
         NB_HIP(ctx, nbk::launch_scenes_located(a, ctx->stream));
-        if (seen_count) NB_HIP(ctx, hipMemcpyAsync(seen_count + at, ctx->seen_count.p, (size_t)cnt * 4u, hipMemcpyDeviceToHost, ctx->stream));
-        if (seen_ids) NB_HIP(ctx, hipMemcpyAsync(seen_ids + at * width, ctx->seen_ids.p, words, hipMemcpyDeviceToHost, ctx->stream));
-        if (seen_depth) NB_HIP(ctx, hipMemcpyAsync(seen_depth + at * width, ctx->seen_depth.p, words, hipMemcpyDeviceToHost, ctx->stream));
-        if (seen_col) NB_HIP(ctx, hipMemcpyAsync(seen_col + at * width, ctx->seen_col.p, words, hipMemcpyDeviceToHost, ctx->stream));
-        if (seen_rel) NB_HIP(ctx, hipMemcpyAsync(seen_rel + at * width * 4u, ctx->seen_rel.p, words * 4u, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return NB_OK;
+        return NB_OK;
+    };
+    return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, lists, kNoScenesLocatedOutputs, launch);
 }
 
 NB_EXPORT int nb_scenes_device_state(nb_scenes *ctx, const void **pos_rec, const void **vel_rec, const void **inst_16n)

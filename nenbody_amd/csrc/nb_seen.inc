@@ -99,6 +99,25 @@ __global__ __launch_bounds__(kSeenBlock) void seen_kernel(uint32_t count, uint32
     }
 }
 
+// Rules 1-3 of body (pn, vn) on one neighbour (pj, vj): V2's pair, for boids_seen_kernel and scenes_boids_seen_kernel (nb_scenes_seen.inc)
+__device__ __forceinline__ void boids_seen_pair(const BoidsArgs &a, BoidsAcc &s, const float4 &pn, const float4 &vn, const float4 &pj,
+                                                const float4 &vj)
+{
+    const float dx = pj.x - pn.x, dy = pj.y - pn.y, dz = pj.z - pn.z;         // distance2: (other - self)
+    const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+    const float ex = vj.x - vn.x, ey = vj.y - vn.y, ez = vj.z - vn.z;
+    const float e2 = ((ex * ex) + (ey * ey)) + (ez * ez);
+    if (d2 < a.r1) {                                                          // main.rs:474-476
+        s.cx = s.cx + pj.x, s.cy = s.cy + pj.y, s.cz = s.cz + pj.z;
+        s.cnt = s.cnt + 1.f;
+    }
+    if (d2 <= a.t2) s.rx = s.rx - dx, s.ry = s.ry - dy, s.rz = s.rz - dz;     // main.rs:485-487  sqrt(d2) < rule_2_distance
+    if (e2 <= a.t3) {                                                         // main.rs:497-499  sqrt(e2) < rule_3_distance
+        s.mx = s.mx + vj.x, s.my = s.my + vj.y, s.mz = s.mz + vj.z;
+        s.vcnt = s.vcnt + 1.f;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void boids_seen_kernel(BoidsArgs a, const uint32_t *__restrict__ seen_count,
                                                            const uint32_t *__restrict__ seen_ids, uint32_t stride)
 {
@@ -112,20 +131,7 @@ __global__ __launch_bounds__(kBlock) void boids_seen_kernel(BoidsArgs a, const u
     for (uint32_t k = 0; k < len; ++k) {
         const uint32_t i = list[k];
         if (i == n || i >= a.n_total) continue;                               // main.rs:475 n != i; an entry outside the set is not read
-        const float4 pj = a.pos_in[i], vj = a.vel_in[i];
-        const float dx = pj.x - pn.x, dy = pj.y - pn.y, dz = pj.z - pn.z;     // distance2: (other - self)
-        const float d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
-        const float ex = vj.x - vn.x, ey = vj.y - vn.y, ez = vj.z - vn.z;
-        const float e2 = ((ex * ex) + (ey * ey)) + (ez * ez);
-        if (d2 < a.r1) {                                                      // main.rs:474-476
-            s.cx = s.cx + pj.x, s.cy = s.cy + pj.y, s.cz = s.cz + pj.z;
-            s.cnt = s.cnt + 1.f;
-        }
-        if (d2 <= a.t2) s.rx = s.rx - dx, s.ry = s.ry - dy, s.rz = s.rz - dz; // main.rs:485-487  sqrt(d2) < rule_2_distance
-        if (e2 <= a.t3) {                                                     // main.rs:497-499  sqrt(e2) < rule_3_distance
-            s.mx = s.mx + vj.x, s.my = s.my + vj.y, s.mz = s.mz + vj.z;
-            s.vcnt = s.vcnt + 1.f;
-        }
+        boids_seen_pair(a, s, pn, vn, a.pos_in[i], a.vel_in[i]);
     }
     boids_finish(a, s, l, pn);
 }
