@@ -349,6 +349,38 @@ const char *nb_scenes_last_error(const nb_scenes *ctx);
  * nb_scenes_located_launch on caller-owned device memory, nb_scenes_step_nbody_located and nb_scenes_eyes_located on a context. */
 #include "nenbody_scenes_located.h"
 
+/* ---- scene batches: a neural policy over each body's eye row ----------------------------------------
+ * A controller of the caller's own: a small two-layer network reads a pooled depth row and outputs thrust and turn in the eye's own
+ * frame; either one network is shared or each scene has its own.  One kernel per step for the whole batch: the row, the features and
+ * the hidden layer stay on chip.  Every step below is one binary32 operation, round to nearest, in the order written; there is no
+ * contraction: a product is rounded before it is added.
+ * The eye set-up is (up_xyz, cp16, width) as nb_scenes_step_boids_seen takes it.  A policy shape (F, H) has
+ * 1 <= F <= NB_POLICY_MAX_FEATURES, F dividing width, 1 <= H <= NB_POLICY_MAX_HIDDEN.  One policy is F*H + H + 2*H + 2 floats:
+ * w1[f*H + j], b1[j], w2[k*H + j] for k = 0, 1, b2[k].  `policies` is 1 (every scene uses policy 0) or `scenes` (scene s uses policy
+ * s).  A limit L >= 0 (accel_limit) applies to the outputs; +inf means no limit.  For body i of scene s, from the snapshot (P, V):
+ *   P1  row: the eye row as nb_eyes forms it with flags = 0; it covers the bodies of its own scene only (SV1's first sentence)
+ *   P2  features: bin f covers columns [f*W/F, (f+1)*W/F); d_f is the value whose bits are the unsigned minimum of the depth bits
+ *       over the bin's non-empty columns, 1.0f if the bin has none; x_f = 1.0f - d_f: an empty bin gives +0, nearer gives larger
+ *   P3  hidden: t_j = b1[j]; then for f = 0 .. F-1 in order t_j = t_j + (w1[f*H + j] * x_f); h_j = (t_j > 0) ? t_j : +0, so a NaN
+ *       gives +0
+ *   P4  outputs: o_k = b2[k]; then for j = 0 .. H-1 in order o_k = o_k + (w2[k*H + j] * h_j); then
+ *       o_k = (o_k < -L) ? -L : ((o_k > L) ? L : o_k), so a NaN passes through
+ *   P5  actuation: f and s of the eye are as L3 forms them from the body's velocity record and up.  If any of their six components
+ *       is not finite -- a zero velocity, a non-finite velocity, a velocity parallel to up -- a = (+0, +0, +0) and the body coasts;
+ *       otherwise a_c = (o_0 * f_c) + (o_1 * s_c)
+ *   P6  integration: v = v + a*dt; p = v + p, with dt from nb_params.  G, bias and mode do not enter, but are validated as the
+ *       other entries validate them
+ *   P7  no scene's result depends on another scene's records or policy, on `scenes`, on the grid, on the launch shape chosen for n,
+ *       or on how k steps are split over calls; the same bits from run to run
+ *   P8  per eye the F words of x and the two words of o (behind the limit) are observable without stepping */
+#define NB_POLICY_MAX_FEATURES 256u
+#define NB_POLICY_MAX_HIDDEN 64u
+
+/* The six entries are declared in nenbody_scenes_policy.h, which this header includes: nb_policy_floats, the stateless
+ * nb_scenes_policy_step_launch and nb_scenes_policy_observe_launch on caller-owned device memory, and nb_scenes_set_policy,
+ * nb_scenes_step_policy and nb_scenes_eyes_policy on a context. */
+#include "nenbody_scenes_policy.h"
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which

@@ -7,6 +7,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -413,6 +414,41 @@ public:
         l.ids.resize(cells), l.depth.resize(cells), l.col.resize(cells), l.rel.resize(cells * 4);
         return l;
     }
+    // The batch's policies (nb_scenes_set_policy): `weights` holds 1 or scenes() policies of
+    // nb_policy_floats(features, hidden) floats each -- w1[f * H + j], b1[j], w2[k * H + j] for k = 0, 1, b2[k] --, scene s using
+    // policy s (or all policy 0).  accel_limit >= 0 clamps the two outputs; infinity: no limit.  May be called again.
+    void set_policy(const std::vector<float> &weights, uint32_t features, uint32_t hidden, float accel_limit = INFINITY)
+    {
+        const size_t one = nb_policy_floats(features, hidden);
+        if (one == 0 || weights.empty() || weights.size() % one != 0)
+            throw std::invalid_argument("weights must hold whole policies of nb_policy_floats(features, hidden) floats");
+        check_sc(nb_scenes_set_policy(ctx_, features, hidden, (uint32_t)(weights.size() / one), weights.data(), accel_limit));
+        features_ = features;
+    }
+    // k steps of every scene under its policy (nb_scenes_step_policy): the pooled eye row through the two-layer network, thrust and
+    // turn along the eye's own axes; one fused launch per step.  width must be a multiple of the policy's features.
+    void step_policy(uint32_t k, const Mat4 &cp, uint32_t width = 1024, const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        check_sc(nb_scenes_step_policy(ctx_, k, up.data(), cp[0].data(), width));
+    }
+    // What that step computes in front of the actuation (nb_scenes_eyes_policy) for scenes [first_scene, first_scene + scene_count):
+    // per eye s * n + i the policy's features and the two outputs behind the limit.
+    struct PolicyObservation {
+        uint32_t features = 0;
+        std::vector<float> feat, act;
+    };
+    PolicyObservation policy_observe(const Mat4 &cp, uint32_t width = 1024, uint32_t first_scene = 0, uint32_t scene_count = UINT32_MAX,
+                                     const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (scene_count == UINT32_MAX) scene_count = first_scene <= scenes_ ? scenes_ - first_scene : 0;
+        PolicyObservation o;
+        o.features = features_;
+        const size_t eyes = (size_t)scene_count * n_, cells = eyes * features_;
+        o.feat.resize(cells ? cells : 1), o.act.resize(eyes ? eyes * 2 : 2);
+        check_sc(nb_scenes_eyes_policy(ctx_, first_scene, scene_count, up.data(), cp[0].data(), width, o.feat.data(), o.act.data()));
+        o.feat.resize(cells), o.act.resize(eyes * 2);
+        return o;
+    }
     void sync() { check_sc(nb_scenes_sync(ctx_)); }
     uint64_t steps_done() const { return nb_scenes_steps(ctx_); }
     void download(std::vector<Vec3> &positions, std::vector<Vec3> &velocities, std::vector<Mat4> &instances)
@@ -451,6 +487,7 @@ private:
     }
     nb_scenes *ctx_ = nullptr;
     uint32_t scenes_ = 0, n_ = 0;
+    uint32_t features_ = 0;   // F of the policy set last; 0: none
 };
 
 // One rank's share of a scene on a multi-GPU host (one process or thread per GPU): nb_shard_* of nenbody.h.  Every rank

@@ -120,6 +120,13 @@ extern "C" {
     fn nb_scenes_eyes_located(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, seen_count: *mut u32, seen_ids: *mut u32, seen_depth: *mut f32, seen_col: *mut u32, seen_rel: *mut f32) -> c_int;
     fn nb_scenes_nbody_located_step_launch(params: *const NbParams, scenes: u32, n: u32, cams_16: *const c_void, inst_16: *const c_void, up_xyz: *const f32, cp16: *const f32, width: u32, pos_in: *const c_void, vel_in: *const c_void, pos_out: *mut c_void, vel_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_located_launch(scenes: u32, n: u32, first_eye: u32, count: u32, cams_16: *const c_void, inst_16: *const c_void, vel_in: *const c_void, up_xyz: *const f32, cp16: *const f32, width: u32, seen_count: *mut c_void, seen_ids: *mut c_void, seen_depth: *mut c_void, seen_col: *mut c_void, seen_rel: *mut c_void, stream: *mut c_void) -> c_int;
+    // a neural policy over each body's eye row (include/nenbody_scenes_policy.h), one fused launch per step, and what it computes per eye
+    fn nb_policy_floats(features: u32, hidden: u32) -> usize;
+    fn nb_scenes_set_policy(ctx: *mut NbScenes, features: u32, hidden: u32, policies: u32, weights_host: *const f32, accel_limit: f32) -> c_int;
+    fn nb_scenes_step_policy(ctx: *mut NbScenes, k: u32, up_xyz: *const f32, cp16: *const f32, width: u32) -> c_int;
+    fn nb_scenes_eyes_policy(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, feat: *mut f32, act: *mut f32) -> c_int;
+    fn nb_scenes_policy_step_launch(params: *const NbParams, scenes: u32, n: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, up_xyz: *const f32, features: u32, hidden: u32, policies: u32, weights: *const c_void, accel_limit: f32, pos_in: *const c_void, vel_in: *const c_void, pos_out: *mut c_void, vel_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_policy_observe_launch(scenes: u32, n: u32, first_eye: u32, count: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, features: u32, hidden: u32, policies: u32, weights: *const c_void, accel_limit: f32, feat_out: *mut c_void, act_out: *mut c_void, stream: *mut c_void) -> c_int;
     // the same on caller-owned device memory, in place
     fn nb_scenes_nbody_step_launch(params: *const NbParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_boids_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
@@ -131,6 +138,14 @@ pub struct NbScenes {
 }
 
 pub const NB_SCENES_MAX_BODIES: u32 = 2048;
+pub const NB_POLICY_MAX_FEATURES: u32 = 256;
+pub const NB_POLICY_MAX_HIDDEN: u32 = 64;
+
+/// The floats of one policy of shape (features, hidden): w1[f * H + j], b1[j], w2[k * H + j] for k = 0, 1, b2[k]; 0 for a shape
+/// outside the limits.
+pub fn policy_floats(features: u32, hidden: u32) -> usize {
+    unsafe { nb_policy_floats(features, hidden) }
+}
 
 pub const NB_FRAME_MAX_DIM: u32 = 4096;
 pub const NB_FRAME_MSAA_MAX_DIM: u32 = 2048;
@@ -754,6 +769,7 @@ pub struct SceneBatch {
     ctx: *mut NbScenes,
     pub scenes: usize,
     pub n: usize,
+    policy_features: usize, // F of the policy set last; 0: none
 }
 
 unsafe impl Send for SceneBatch {}
@@ -780,7 +796,7 @@ impl SceneBatch {
         assert!(positions.len() == scenes * n && velocities.len() == scenes * n, "positions and velocities must hold scenes * n bodies");
         let mut ctx: *mut NbScenes = std::ptr::null_mut();
         check_scenes(unsafe { nb_scenes_create(scenes as u32, n as u32, &params, &mut ctx) }, std::ptr::null())?;
-        let batch = SceneBatch { ctx, scenes, n };
+        let batch = SceneBatch { ctx, scenes, n, policy_features: 0 };
         check_scenes(unsafe { nb_scenes_upload(batch.ctx, positions.as_ptr() as *const f32, velocities.as_ptr() as *const f32) }, batch.ctx)?;
         Ok(batch)
     }
@@ -859,6 +875,49 @@ impl SceneBatch {
         l.col.truncate(cells);
         l.rel.truncate(cells);
         Ok(l)
+    }
+
+    /// the batch's policies (nb_scenes_set_policy): `weights` holds 1 or `scenes` policies of policy_floats(features, hidden) floats
+    /// each, scene s using policy s (or all policy 0); `accel_limit` >= 0 clamps the two outputs, f32::INFINITY: no limit
+    pub fn set_policy(&mut self, weights: &[f32], features: u32, hidden: u32, accel_limit: f32) -> Result<(), SceneError> {
+        let one = policy_floats(features, hidden);
+        if one == 0 || weights.is_empty() || weights.len() % one != 0 {
+            return Err(SceneError(-1, "weights must hold whole policies of policy_floats(features, hidden) floats".to_string())); // NB_ERR_INVALID
+        }
+        check_scenes(
+            unsafe { nb_scenes_set_policy(self.ctx, features, hidden, (weights.len() / one) as u32, weights.as_ptr(), accel_limit) },
+            self.ctx,
+        )?;
+        self.policy_features = features as usize;
+        Ok(())
+    }
+
+    /// k steps of every scene under its policy (nb_scenes_step_policy): the pooled eye row through the two-layer network, thrust and
+    /// turn along the eye's own axes; one fused launch per step.  `width` must be a multiple of the policy's features.
+    pub fn step_policy(&mut self, k: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<(), SceneError> {
+        let up = [0.0f32, 0.0, 1.0];
+        check_scenes(
+            unsafe { nb_scenes_step_policy(self.ctx, k, up.as_ptr(), cp.as_ptr() as *const f32, width) },
+            self.ctx,
+        )
+    }
+
+    /// what that step computes in front of the actuation, for scenes [first_scene, first_scene + scene_count): per eye the policy's
+    /// features and the two outputs behind the limit
+    pub fn policy_observe(&mut self, first_scene: u32, scene_count: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<(Vec<f32>, Vec<[f32; 2]>), SceneError> {
+        let up = [0.0f32, 0.0, 1.0];
+        let eyes = scene_count as usize * self.n;
+        let mut feat = vec![0f32; (eyes * self.policy_features).max(1)];
+        let mut act = vec![[0f32; 2]; eyes.max(1)];
+        check_scenes(
+            unsafe {
+                nb_scenes_eyes_policy(self.ctx, first_scene, scene_count, up.as_ptr(), cp.as_ptr() as *const f32, width, feat.as_mut_ptr(), act.as_mut_ptr() as *mut f32)
+            },
+            self.ctx,
+        )?;
+        feat.truncate(eyes * self.policy_features);
+        act.truncate(eyes);
+        Ok((feat, act))
     }
 
     /// positions, velocities and model matrices of every body, scene after scene

@@ -32,6 +32,8 @@ NB_PHASE_REST = 1
 NB_RING_OWN, NB_RING_REST, NB_RING_SUMS, NB_RING_OWN_READY = 1, 2, 3, 4
 # every entity's eye view (nb_eyes / nb_launch_eyes)
 NB_SCENES_MAX_BODIES = 2048
+NB_POLICY_MAX_FEATURES = 256
+NB_POLICY_MAX_HIDDEN = 64
 NB_EYES_NONE = 0xFFFFFFFF
 NB_EYES_SEE_SELF = 1
 NB_EYES_MAX_WIDTH = 4096
@@ -247,6 +249,18 @@ SCENES_LOCATED_PROTOTYPES = {
                                        c_void_p]),
 }
 
+# include/nenbody_scenes_policy.h: a neural policy over each eye row of scene batches, bound likewise
+SCENES_POLICY_PROTOTYPES = {
+    "nb_policy_floats": (c_size_t, [c_uint32, c_uint32]),
+    "nb_scenes_policy_step_launch": (c_int, [POINTER(NbParams), c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32,
+                                             c_uint32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_policy_observe_launch": (c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32,
+                                                c_uint32, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_set_policy": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_float]),
+    "nb_scenes_step_policy": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]),
+    "nb_scenes_eyes_policy": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+}
+
 # every symbol include/nenbody_diag.h declares (self-tests, the test suite's switches): not part of the drop-in boundary
 DIAG_PROTOTYPES = {
     "nb_selftest_ladder": (c_int, [c_uint32, c_uint32, POINTER(c_uint64), c_void_p]),
@@ -309,7 +323,7 @@ def _bind(path: str) -> ctypes.CDLL:
     _preload_torch_hip_runtime()
     lib = ctypes.CDLL(path)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SCENES_SEEN_PROTOTYPES.items()) + list(SCENES_LOCATED_PROTOTYPES.items()) \
-            + list(DIAG_PROTOTYPES.items()):
+            + list(SCENES_POLICY_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

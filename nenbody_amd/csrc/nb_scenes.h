@@ -66,4 +66,35 @@ hipError_t launch_scenes_nbody_located(const ScenesLocatedArgs &a, hipStream_t s
 // The located sets that step folds over: the words nb_eyes_located gives a context holding the eye's scene, indexed from first_eye.
 hipError_t launch_scenes_located(const ScenesLocatedArgs &a, hipStream_t s);
 
+// A neural policy over each body's eye row (nb_scenes_policy.inc): one workgroup per eye, the eye's row, its
+// pooled features and the hidden layer in LDS only -- 8 width + 4 features + 4 hidden bytes, at most 34 048.  The launch shape follows
+// kScenesSeenWaveBodies as above; the bits are the same.  The caller has checked the arguments (1 <= n <= kScenesMaxBodies,
+// 1 <= width <= NB_EYES_MAX_WIDTH, count >= 1, 1 <= features <= kPolicyMaxFeatures dividing width, 1 <= hidden <= kPolicyMaxHidden,
+// limit >= 0).
+constexpr uint32_t kPolicyMaxFeatures = 256;  // NB_POLICY_MAX_FEATURES
+constexpr uint32_t kPolicyMaxHidden = 64;     // NB_POLICY_MAX_HIDDEN: one lane per hidden unit of a 64-lane workgroup
+// the floats of one policy: w1[f H + j], b1[j], w2[k H + j] (k = 0, 1), b2[k]
+constexpr size_t policy_floats(uint32_t features, uint32_t hidden) { return (size_t)features * hidden + hidden + 2u * (size_t)hidden + 2u; }
+struct ScenesPolicyArgs {
+    uint32_t n, first_eye, count, width;     // eyes [first_eye, first_eye + count) of the batch; eye b is body b % n of scene b / n
+    const float4 *__restrict__ cams;         // 4 / 4 float4 per body of the WHOLE batch, as launch_cameras / launch_instances leave them
+    const float4 *__restrict__ inst;
+    uint32_t features, hidden;               // the policy shape (F, H)
+    uint32_t stride;                         // floats from scene s's policy to scene s + 1's: policy_floats, or 0 where all share policy 0
+    const float *__restrict__ weights;
+    float limit;                             // L >= 0; +inf: none
+    const float4 *__restrict__ pos_in;       // the step's: the batch's records
+    const float4 *__restrict__ vel_in;
+    float ux, uy, uz;
+    float dt;                                // main.rs:411
+    float4 *__restrict__ pos_out;            // the step's: record b written
+    float4 *__restrict__ vel_out;
+    uint32_t *__restrict__ feat_out;         // the observable's (P8): count x features words of x, count x 2 words of o; either may be NULL
+    uint32_t *__restrict__ act_out;
+};
+// ONE step, out of place, for every eye the arguments name (the entries pass the whole batch).
+hipError_t launch_scenes_policy(const ScenesPolicyArgs &a, hipStream_t s);
+// What that step computes per eye in front of the actuation: the features and the limited outputs, indexed from first_eye.
+hipError_t launch_scenes_policy_observe(const ScenesPolicyArgs &a, hipStream_t s);
+
 }  // namespace nbk

@@ -2,7 +2,9 @@
 // nb_scenes_boids_step_launch) step caller-owned records in place; the context nb_scenes owns a batch and a stream.  Section 14.1 adds
 // the boids step over what each body sees: nb_scenes_boids_seen_step_launch and nb_scenes_seen_launch, stateless, and the context's
 // nb_scenes_step_boids_seen and nb_scenes_eyes_seen.  Section 14.2 adds gravity from located vision in the same four shapes:
-// nb_scenes_nbody_located_step_launch, nb_scenes_located_launch, nb_scenes_step_nbody_located and nb_scenes_eyes_located.  Included by
+// nb_scenes_nbody_located_step_launch, nb_scenes_located_launch, nb_scenes_step_nbody_located and nb_scenes_eyes_located.  Section 14.4
+// adds a neural policy over each eye row: nb_policy_floats, nb_scenes_policy_step_launch and nb_scenes_policy_observe_launch, stateless,
+// and the context's nb_scenes_set_policy, nb_scenes_step_policy and nb_scenes_eyes_policy.  Included by
 // nb_api.hip behind nb_vision_api.inc.  Every check runs before anything touches the device and has its own message naming the entry.
 
 static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
@@ -316,6 +318,10 @@ struct nb_scenes {
     DeviceBuffer<uint32_t> seen_count, seen_ids;   // nb_scenes_eyes_seen's lists for one range of scenes, likewise and grown on demand
     DeviceBuffer<uint32_t> seen_depth, seen_col;   // nb_scenes_eyes_located's further lists, likewise: depth bits and columns
     DeviceBuffer<uint32_t> seen_rel;               // and its located points, four words a slot
+    DeviceBuffer<float> policy;                    // nb_scenes_set_policy's weights: policies * nb_policy_floats floats
+    uint32_t features = 0, hidden = 0, policies = 0;   // their shape; policies = 0: no policy set
+    float accel_limit = 0.f;
+    DeviceBuffer<uint32_t> pol_feat, pol_act;      // nb_scenes_eyes_policy's features and outputs for one range of scenes, grown on demand
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
@@ -592,6 +598,199 @@ NB_EXPORT int nb_scenes_eyes_located(nb_scenes *ctx, uint32_t first_scene, uint3
         return NB_OK;
     };
     return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, lists, kNoScenesLocatedOutputs, launch);
+}
+
+// ---- a neural policy over each eye row (DESIGN.md section 14.4) ---------------------------------------------------------------------------
+static_assert(NB_POLICY_MAX_FEATURES == nbk::kPolicyMaxFeatures && NB_POLICY_MAX_HIDDEN == nbk::kPolicyMaxHidden, "the header's limits are the kernels'");
+static const char kNoPolicyOutputs[] = ": feat_out and act_out are both NULL";
+static const char kCallSetPolicy[] = ": no policy set (call nb_scenes_set_policy first)";
+
+NB_EXPORT size_t nb_policy_floats(uint32_t features, uint32_t hidden)
+{
+    if (features == 0 || features > NB_POLICY_MAX_FEATURES || hidden == 0 || hidden > NB_POLICY_MAX_HIDDEN) return 0;
+    return nbk::policy_floats(features, hidden);
+}
+
+// the shape of a policy against the eye's width (0: the entry has no width yet), the number of policies against the batch's scenes
+// and the limit
+static int policy_check(const char *fn, uint32_t features, uint32_t hidden, uint32_t width, uint32_t policies, uint32_t scenes,
+                        float accel_limit, std::string *err)
+{
+    if (features == 0 || features > NB_POLICY_MAX_FEATURES) {
+        *err = std::string(fn) + ": features must be 1 .. NB_POLICY_MAX_FEATURES (256)";
+        return NB_ERR_INVALID;
+    }
+    if (hidden == 0 || hidden > NB_POLICY_MAX_HIDDEN) {
+        *err = std::string(fn) + ": hidden must be 1 .. NB_POLICY_MAX_HIDDEN (64)";
+        return NB_ERR_INVALID;
+    }
+    if (width % features != 0) {
+        *err = std::string(fn) + ": width must be a multiple of features";
+        return NB_ERR_INVALID;
+    }
+    if (policies != 1 && policies != scenes) {
+        *err = std::string(fn) + ": policies must be 1 or scenes";
+        return NB_ERR_INVALID;
+    }
+    if (!(accel_limit >= 0.0f)) {
+        *err = std::string(fn) + ": accel_limit must be at least 0 (+inf: no limit)";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+static int policy_weights_check(const char *fn, const void *weights, std::string *err)
+{
+    if ((uintptr_t)weights & 3u) {
+        *err = std::string(fn) + ": weights must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// the kernel's arguments but for its buffers: the eye set-up and the policies
+static nbk::ScenesPolicyArgs scenes_policy_args(uint32_t n, uint32_t first_eye, uint32_t count, const void *cams, const void *inst,
+                                                uint32_t width, uint32_t features, uint32_t hidden, uint32_t policies, const void *weights,
+                                                float accel_limit)
+{
+    nbk::ScenesPolicyArgs a{};
+    a.n = n, a.first_eye = first_eye, a.count = count, a.width = width;
+    a.cams = (const float4 *)cams, a.inst = (const float4 *)inst;
+    a.features = features, a.hidden = hidden;
+    a.stride = policies == 1 ? 0u : (uint32_t)nbk::policy_floats(features, hidden);
+    a.weights = (const float *)weights, a.limit = accel_limit;
+    return a;
+}
+
+NB_EXPORT int nb_scenes_policy_step_launch(const nb_params *params, uint32_t scenes, uint32_t n, const void *cams_16, const void *inst_16,
+                                           uint32_t width, const float *up_xyz, uint32_t features, uint32_t hidden, uint32_t policies,
+                                           const void *weights, float accel_limit, const void *pos_in, const void *vel_in, void *pos_out,
+                                           void *vel_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_policy_step_launch";
+    if (!cams_16 || !inst_16 || !up_xyz || !weights || !pos_in || !vel_in || !pos_out || !vel_out) {
+        g_tls_error = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    const nb_params p = params_or_default(params);
+    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    if (rc == NB_OK) rc = policy_check(fn, features, hidden, width, policies, scenes, accel_limit, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_params_check(fn, p, &g_tls_error);
+    if (rc == NB_OK) rc = policy_weights_check(fn, weights, &g_tls_error);
+    const size_t records = (size_t)scenes * n;
+    if (rc == NB_OK) rc = scenes_step_buffers_check(fn, records, cams_16, inst_16, pos_in, vel_in, pos_out, vel_out, up_xyz, nullptr, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    const size_t wbytes = (size_t)policies * nbk::policy_floats(features, hidden) * sizeof(float);
+    if (ranges_overlap(pos_out, records * sizeof(float4), weights, wbytes) || ranges_overlap(vel_out, records * sizeof(float4), weights, wbytes)) {
+        g_tls_error = std::string(fn) + kScenesSeenAlias;
+        return NB_ERR_INVALID;
+    }
+    rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    nbk::ScenesPolicyArgs a = scenes_policy_args(n, 0u, (uint32_t)records, cams_16, inst_16, width, features, hidden, policies, weights, accel_limit);
+    a.pos_in = (const float4 *)pos_in, a.vel_in = (const float4 *)vel_in, a.pos_out = (float4 *)pos_out, a.vel_out = (float4 *)vel_out;
+    a.ux = up_xyz[0], a.uy = up_xyz[1], a.uz = up_xyz[2], a.dt = p.dt;
+    return launch_status(nbk::launch_scenes_policy(a, (hipStream_t)stream), "nb: policy kernel launch failed (scene batch): ", &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_policy_observe_launch(uint32_t scenes, uint32_t n, uint32_t first_eye, uint32_t count, const void *cams_16,
+                                              const void *inst_16, uint32_t width, uint32_t features, uint32_t hidden, uint32_t policies,
+                                              const void *weights, float accel_limit, void *feat_out, void *act_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_policy_observe_launch";
+    if (!cams_16 || !inst_16 || !weights) {
+        g_tls_error = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    if (rc == NB_OK) rc = policy_check(fn, features, hidden, width, policies, scenes, accel_limit, &g_tls_error);
+    if (rc == NB_OK) rc = policy_weights_check(fn, weights, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned16_check(fn, {cams_16, inst_16}, "cams_16 and inst_16", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_eye_range_check(fn, scenes, n, first_eye, count, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    const size_t matrices = (size_t)scenes * n * 16 * sizeof(float);
+    const ByteRange in[3] = {{cams_16, matrices}, {inst_16, matrices}, {weights, (size_t)policies * nbk::policy_floats(features, hidden) * sizeof(float)}};
+    const ByteRange out[2] = {{feat_out, (size_t)count * features * 4u}, {act_out, (size_t)count * 8u}};
+    rc = outputs_check(fn, out, 0x3u, kNoPolicyOutputs, true, in, 3, kScenesSeenAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = device_for_launch(inst_16, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    nbk::ScenesPolicyArgs a = scenes_policy_args(n, first_eye, count, cams_16, inst_16, width, features, hidden, policies, weights, accel_limit);
+    a.feat_out = (uint32_t *)feat_out, a.act_out = (uint32_t *)act_out;
+    return launch_status(nbk::launch_scenes_policy_observe(a, (hipStream_t)stream), "nb: policy kernel launch failed (scene batch, observe form): ",
+                         &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_set_policy(nb_scenes *ctx, uint32_t features, uint32_t hidden, uint32_t policies, const float *weights_host,
+                                   float accel_limit)
+{
+    static const char fn[] = "nb_scenes_set_policy";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (!weights_host) {
+        ctx->err = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    rc = policy_check(fn, features, hidden, 0u, policies, ctx->scenes, accel_limit, &ctx->err);
+    if (rc != NB_OK) return rc;
+    const size_t floats = (size_t)policies * nbk::policy_floats(features, hidden);
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step in flight may still read the policies in place
+    ctx->policies = 0;
+    NB_HIP(ctx, ctx->policy.reserve(floats));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->policy.p, weights_host, floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
+    ctx->features = features, ctx->hidden = hidden, ctx->policies = policies, ctx->accel_limit = accel_limit;
+    return NB_OK;
+}
+
+// what the context's two policy entries check behind their eye set-up: a policy is there and its features divide the width
+static int scenes_policy_set_check(nb_scenes *ctx, const char *fn, uint32_t width)
+{
+    if (ctx->policies == 0) {
+        ctx->err = std::string(fn) + kCallSetPolicy;
+        return NB_ERR_STATE;
+    }
+    return policy_check(fn, ctx->features, ctx->hidden, width, ctx->policies, ctx->scenes, ctx->accel_limit, &ctx->err);
+}
+
+NB_EXPORT int nb_scenes_step_policy(nb_scenes *ctx, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
+{
+    static const char fn[] = "nb_scenes_step_policy";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
+    if (rc == NB_OK) rc = scenes_policy_set_check(ctx, fn, width);
+    if (rc != NB_OK) return rc;
+    return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [=](nb_scenes *ctx) -> int {
+        nbk::ScenesPolicyArgs a = scenes_policy_args(ctx->n, 0u, ctx->scenes * ctx->n, ctx->cams.p, ctx->inst.p, width, ctx->features,
+                                                     ctx->hidden, ctx->policies, ctx->policy.p, ctx->accel_limit);
+        a.pos_in = ctx->pos.p, a.vel_in = ctx->vel.p, a.pos_out = ctx->pos_alt.p, a.vel_out = ctx->vel_alt.p;
+        a.ux = up_xyz[0], a.uy = up_xyz[1], a.uz = up_xyz[2], a.dt = ctx->p.dt;
+        NB_HIP(ctx, nbk::launch_scenes_policy(a, ctx->stream));
+        return NB_OK;
+    });
+}
+
+NB_EXPORT int nb_scenes_eyes_policy(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
+                                    uint32_t width, float *feat, float *act)
+{
+    static const char fn[] = "nb_scenes_eyes_policy";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    if (rc == NB_OK) rc = scenes_policy_set_check(ctx, fn, width);
+    if (rc != NB_OK) return rc;
+    const ScenesEyesOutput rows[2] = {{feat, &ctx->pol_feat, ctx->features}, {act, &ctx->pol_act, 2}};
+    const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
+        nbk::ScenesPolicyArgs a = scenes_policy_args(ctx->n, first_eye, cnt, ctx->cams.p, ctx->inst.p, width, ctx->features, ctx->hidden,
+                                                     ctx->policies, ctx->policy.p, ctx->accel_limit);
+        a.feat_out = feat ? ctx->pol_feat.p : nullptr, a.act_out = act ? ctx->pol_act.p : nullptr;
+        NB_HIP(ctx, nbk::launch_scenes_policy_observe(a, ctx->stream));
+        return NB_OK;
+    };
+    return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, rows, kNoPolicyOutputs, launch);
 }
 
 NB_EXPORT int nb_scenes_device_state(nb_scenes *ctx, const void **pos_rec, const void **vel_rec, const void **inst_16n)

@@ -421,6 +421,26 @@ class Scene:
         return False
 
 
+def policy_floats(features: int, hidden: int) -> int:
+    """The floats of one policy of shape (features, hidden) (nb_policy_floats): 0 for a shape outside the limits."""
+    if features < 0 or hidden < 0 or features > 0xFFFFFFFF or hidden > 0xFFFFFFFF:
+        return 0
+    return int(_lib.load().nb_policy_floats(int(features), int(hidden)))
+
+
+def pack_policy(w1, b1, w2, b2) -> np.ndarray:
+    """One policy in the layout :meth:`SceneBatch.set_policy` takes: w1 (F, H) feature-major, b1 (H,), w2 (2, H), b2 (2,) ->
+    F*H + H + 2*H + 2 float32."""
+    w1 = np.ascontiguousarray(w1, np.float32)
+    if w1.ndim != 2:
+        raise ValueError("w1 must have shape (features, hidden)")
+    hidden = w1.shape[1]
+    b1, w2, b2 = (np.ascontiguousarray(a, np.float32) for a in (b1, w2, b2))
+    if b1.shape != (hidden,) or w2.shape != (2, hidden) or b2.shape != (2,):
+        raise ValueError("b1 must have shape (hidden,), w2 (2, hidden) and b2 (2,)")
+    return np.concatenate([w1.reshape(-1), b1, w2.reshape(-1), b2])
+
+
 class SceneBatch:
     """B independent scenes of n <= NB_SCENES_MAX_BODIES bodies, device-resident, stepped k times by ONE launch with one workgroup
     per scene.  Every scene gets the bits a :class:`Scene` of its n bodies gets.  ``positions`` and
@@ -518,6 +538,38 @@ class SceneBatch:
                                                      count.ctypes.data, ids.ctypes.data, depth.ctypes.data, col.ctypes.data,
                                                      rel.ctypes.data))
         return count, ids, depth, col, rel
+
+    def set_policy(self, weights, features: int, hidden: int, accel_limit: float = float("inf")) -> None:
+        """The batch's policies (nb_scenes_set_policy): ``weights`` of shape (P, policy_floats(features,
+        hidden)), P = 1 (every scene uses policy 0) or the number of scenes (scene s uses policy s), each row laid out as
+        :func:`pack_policy` lays it out.  ``accel_limit`` >= 0 clamps the two outputs; inf: no limit.  May be called again."""
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.ndim != 2 or w.shape[1] != policy_floats(features, hidden) or w.shape[1] == 0:
+            raise ValueError("weights must have shape (policies, policy_floats(features, hidden))")
+        self._check(self._lib.nb_scenes_set_policy(self._ctx, int(features), int(hidden), int(w.shape[0]), w.ctypes.data, float(accel_limit)))
+        self._policy_shape = (int(features), int(hidden))
+
+    def step_policy(self, k: int = 1, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None) -> None:
+        """k steps of every scene under its policy (nb_scenes_step_policy): each body pools its eye row into the policy's features,
+        runs the two-layer network and is pushed along its eye's forward and side axes by the two outputs; one fused launch per step
+        for the whole batch.  ``width`` must be a multiple of the policy's features."""
+        upv, cpm = self._eye_setup(width, up, cp)
+        self._check(self._lib.nb_scenes_step_policy(self._ctx, int(k), upv.ctypes.data, cpm.ctypes.data, width))
+
+    def policy_observe(self, first_scene: int = 0, scene_count: Optional[int] = None, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None):
+        """What :meth:`step_policy` computes in front of the actuation (nb_scenes_eyes_policy) for scenes [first_scene, first_scene +
+        scene_count) of the current state, without stepping.  Returns (features float32 (S, n, F), outputs float32 (S, n, 2) behind
+        the limit)."""
+        if scene_count is None:
+            scene_count = self.scenes - first_scene
+        if first_scene < 0 or scene_count < 0:
+            raise ValueError("first_scene and scene_count must be >= 0")
+        upv, cpm = self._eye_setup(width, up, cp)
+        feat = np.empty((scene_count, self.n, getattr(self, "_policy_shape", (0, 0))[0]), np.float32)
+        act = np.empty((scene_count, self.n, 2), np.float32)
+        self._check(self._lib.nb_scenes_eyes_policy(self._ctx, first_scene, scene_count, upv.ctypes.data, cpm.ctypes.data, width,
+                                                    feat.ctypes.data, act.ctypes.data))
+        return feat, act
 
     def _download(self, what: int) -> np.ndarray:
         out = np.empty((self.scenes, self.n, 4, 4) if what == 2 else (self.scenes, self.n, 3), np.float32)
