@@ -381,6 +381,44 @@ const char *nb_scenes_last_error(const nb_scenes *ctx);
  * nb_scenes_step_policy and nb_scenes_eyes_policy on a context. */
 #include "nenbody_scenes_policy.h"
 
+/* ---- scene batches: the score of every scene, accumulated on the device -------------------------------
+ * What a tuner compares between the policies of a population: per scene, the current snapshot reduced to a fixed record of metrics
+ * and added to a record the scene keeps in device memory; the host reads 32 bytes a scene when the rollout ends.  Every float
+ * operation below is one binary32 operation, round to nearest, in the order written; there is no contraction, and subnormals are
+ * kept.  There is no square root and no library function.  Which NaN an operation gives is not part of the rule: a field that is a
+ * NaN is a NaN, of any sign and payload.
+ * Inputs: a batch as above; the snapshot (P, V) of scene s, of which only x, y, z of a record enter; radius_sq >= 0 (not a NaN; +inf
+ * admitted) and goal[3], finite.
+ *   Q1:  the tree sum T(u) of n leaves: P is the smallest power of two >= n; u_i = +0 for n <= i < P; for stride = P/2, P/4, .., 1:
+ *        u_i = u_i + u_{i+stride} for every i < stride; T = u_0.  An add whose right operand is padding may be skipped, and a tree
+ *        over a larger power of two may be run: either changes at most the sign of a zero sum, which Q3-Q6 cannot observe
+ *   Q2:  near = the number of unordered pairs i < j with d2 < radius_sq, d2 = ((dx*dx) + (dy*dy)) + (dz*dz), dx = p_i.x - p_j.x and
+ *        likewise dy, dz: bitwise symmetric in i and j; a NaN compares false
+ *   Q3:  spread: c_x = T(p.x) / (float)n, the IEEE quotient, likewise c_y, c_z; e_i = ((ex*ex) + (ey*ey)) + (ez*ez), ex = p_i.x - c_x
+ *        and likewise ey, ez; spread = T(e)
+ *   Q4:  speed2 = T(((vx*vx) + (vy*vy)) + (vz*vz)); m_c = T(v.c) for the three components; momentum2 = ((m_x*m_x) + (m_y*m_y)) +
+ *        (m_z*m_z)
+ *   Q5:  goal2 = T of Q3's squared distance with goal in place of c
+ *   Q6:  nonfinite = the number of bodies with a non-finite component among the six of (P, V)
+ *   Q7:  accumulation into the scene's nb_scene_score: near += near, exact; every float field acc = acc + term, one add, in call
+ *        order; steps += 1 and nonfinite += nonfinite, modulo 2^32.  All-zero bytes are the cleared state.  No scene's record
+ *        depends on another scene, on `scenes`, on the grid, on the workgroup shape, or on how the snapshots are split over calls;
+ *        the same bits from run to run */
+typedef struct nb_score_params {
+    float radius_sq; /* Q2 */
+    float goal[3];   /* Q5 */
+} nb_score_params;
+typedef struct nb_scene_score {
+    uint64_t near;
+    float spread, speed2, momentum2, goal2;
+    uint32_t steps, nonfinite;
+} nb_scene_score; /* 32 bytes */
+
+/* The six entries are declared in nenbody_scenes_score.h, which this header includes: the stateless nb_scenes_score_launch on
+ * caller-owned device memory, and nb_scenes_set_score, nb_scenes_score, nb_scenes_score_reset, nb_scenes_scores and
+ * nb_scenes_step_policy_scored on a context. */
+#include "nenbody_scenes_score.h"
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which

@@ -449,6 +449,32 @@ public:
         o.feat.resize(cells), o.act.resize(eyes * 2);
         return o;
     }
+    // The batch's score (nb_scenes_set_score): radius_sq >= 0 is the squared radius below which a pair counts
+    // as near (infinity: every pair), goal the point whose squared distance is summed.  Allocates one record a scene on first use
+    // and clears the records.  May be called again.
+    void set_score(float radius_sq, const Vec3 &goal = Vec3{0.0f, 0.0f, 0.0f})
+    {
+        const nb_score_params sp = {radius_sq, {goal[0], goal[1], goal[2]}};
+        check_sc(nb_scenes_set_score(ctx_, &sp));
+    }
+    // The current snapshot of every scene added to its record (nb_scenes_score): one kernel, asynchronous.
+    void score() { check_sc(nb_scenes_score(ctx_)); }
+    // The records cleared (nb_scenes_score_reset), asynchronous.  An upload does not clear them.
+    void score_reset() { check_sc(nb_scenes_score_reset(ctx_)); }
+    // The records of scenes [first_scene, first_scene + scene_count) (nb_scenes_scores), 32 bytes a scene.  Waits for the stream.
+    std::vector<nb_scene_score> scores(uint32_t first_scene = 0, uint32_t scene_count = UINT32_MAX)
+    {
+        if (scene_count == UINT32_MAX) scene_count = first_scene <= scenes_ ? scenes_ - first_scene : 0;
+        std::vector<nb_scene_score> out(scene_count ? scene_count : 1);
+        check_sc(nb_scenes_scores(ctx_, first_scene, scene_count, out.data()));
+        out.resize(scene_count);
+        return out;
+    }
+    // k times step_policy(1) then score() (nb_scenes_step_policy_scored): a rollout scored where it runs.
+    void step_policy_scored(uint32_t k, const Mat4 &cp, uint32_t width = 1024, const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        check_sc(nb_scenes_step_policy_scored(ctx_, k, up.data(), cp[0].data(), width));
+    }
     void sync() { check_sc(nb_scenes_sync(ctx_)); }
     uint64_t steps_done() const { return nb_scenes_steps(ctx_); }
     void download(std::vector<Vec3> &positions, std::vector<Vec3> &velocities, std::vector<Mat4> &instances)

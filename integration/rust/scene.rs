@@ -127,6 +127,13 @@ extern "C" {
     fn nb_scenes_eyes_policy(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, feat: *mut f32, act: *mut f32) -> c_int;
     fn nb_scenes_policy_step_launch(params: *const NbParams, scenes: u32, n: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, up_xyz: *const f32, features: u32, hidden: u32, policies: u32, weights: *const c_void, accel_limit: f32, pos_in: *const c_void, vel_in: *const c_void, pos_out: *mut c_void, vel_out: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_policy_observe_launch(scenes: u32, n: u32, first_eye: u32, count: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, features: u32, hidden: u32, policies: u32, weights: *const c_void, accel_limit: f32, feat_out: *mut c_void, act_out: *mut c_void, stream: *mut c_void) -> c_int;
+    // the score of every scene, accumulated on the device (include/nenbody_scenes_score.h)
+    fn nb_scenes_score_launch(sp: *const NbScoreParams, scenes: u32, n: u32, pos: *const c_void, vel: *const c_void, score: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_set_score(ctx: *mut NbScenes, sp: *const NbScoreParams) -> c_int;
+    fn nb_scenes_score(ctx: *mut NbScenes) -> c_int;
+    fn nb_scenes_score_reset(ctx: *mut NbScenes) -> c_int;
+    fn nb_scenes_scores(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, out_host: *mut NbSceneScore) -> c_int;
+    fn nb_scenes_step_policy_scored(ctx: *mut NbScenes, k: u32, up_xyz: *const f32, cp16: *const f32, width: u32) -> c_int;
     // the same on caller-owned device memory, in place
     fn nb_scenes_nbody_step_launch(params: *const NbParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_boids_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
@@ -135,6 +142,27 @@ extern "C" {
 #[repr(C)]
 pub struct NbScenes {
     _private: [u8; 0],
+}
+
+/// nb_score_params: the squared radius of `near` (Q2) and the goal (Q5)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct NbScoreParams {
+    pub radius_sq: f32,
+    pub goal: [f32; 3],
+}
+
+/// nb_scene_score, 32 bytes: what a scene's snapshots have added up to (Q7)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct NbSceneScore {
+    pub near: u64,
+    pub spread: f32,
+    pub speed2: f32,
+    pub momentum2: f32,
+    pub goal2: f32,
+    pub steps: u32,
+    pub nonfinite: u32,
 }
 
 pub const NB_SCENES_MAX_BODIES: u32 = 2048;
@@ -918,6 +946,40 @@ impl SceneBatch {
         feat.truncate(eyes * self.policy_features);
         act.truncate(eyes);
         Ok((feat, act))
+    }
+
+    /// the batch's score (nb_scenes_set_score): `radius_sq` >= 0 is the squared radius below which a pair
+    /// counts as near (f32::INFINITY: every pair), `goal` the point whose squared distance is summed; clears the records
+    pub fn set_score(&mut self, radius_sq: f32, goal: [f32; 3]) -> Result<(), SceneError> {
+        let sp = NbScoreParams { radius_sq, goal };
+        check_scenes(unsafe { nb_scenes_set_score(self.ctx, &sp) }, self.ctx)
+    }
+
+    /// the current snapshot of every scene added to its record (nb_scenes_score): one kernel, asynchronous
+    pub fn score(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_score(self.ctx) }, self.ctx)
+    }
+
+    /// the records cleared (nb_scenes_score_reset), asynchronous; an upload does not clear them
+    pub fn score_reset(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_score_reset(self.ctx) }, self.ctx)
+    }
+
+    /// the records of scenes [first_scene, first_scene + scene_count) (nb_scenes_scores); waits for the stream
+    pub fn scores(&mut self, first_scene: u32, scene_count: u32) -> Result<Vec<NbSceneScore>, SceneError> {
+        let mut out = vec![NbSceneScore::default(); (scene_count as usize).max(1)];
+        check_scenes(unsafe { nb_scenes_scores(self.ctx, first_scene, scene_count, out.as_mut_ptr()) }, self.ctx)?;
+        out.truncate(scene_count as usize);
+        Ok(out)
+    }
+
+    /// k times step_policy(1) then score() (nb_scenes_step_policy_scored): a rollout scored where it runs
+    pub fn step_policy_scored(&mut self, k: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<(), SceneError> {
+        let up = [0.0f32, 0.0, 1.0];
+        check_scenes(
+            unsafe { nb_scenes_step_policy_scored(self.ctx, k, up.as_ptr(), cp.as_ptr() as *const f32, width) },
+            self.ctx,
+        )
     }
 
     /// positions, velocities and model matrices of every body, scene after scene

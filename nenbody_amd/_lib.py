@@ -72,6 +72,12 @@ class NbBoidsParams(ctypes.Structure):
                 ("rule_1_scale", c_float), ("rule_2_scale", c_float), ("rule_3_scale", c_float), ("tile", c_uint32)]
 
 
+class NbScoreParams(ctypes.Structure):
+    """struct nb_score_params (include/nenbody.h, Q2 and Q5): the radius of `near`, squared, and the goal."""
+
+    _fields_ = [("radius_sq", c_float), ("goal", c_float * 3)]
+
+
 class NbError(RuntimeError):
     """A non-zero nb_status from the library."""
 
@@ -261,6 +267,16 @@ SCENES_POLICY_PROTOTYPES = {
     "nb_scenes_eyes_policy": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
 }
 
+# include/nenbody_scenes_score.h: the score of every scene, accumulated on the device, bound likewise
+SCENES_SCORE_PROTOTYPES = {
+    "nb_scenes_score_launch": (c_int, [POINTER(NbScoreParams), c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_set_score": (c_int, [c_void_p, POINTER(NbScoreParams)]),
+    "nb_scenes_score": (c_int, [c_void_p]),
+    "nb_scenes_score_reset": (c_int, [c_void_p]),
+    "nb_scenes_scores": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p]),
+    "nb_scenes_step_policy_scored": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]),
+}
+
 # every symbol include/nenbody_diag.h declares (self-tests, the test suite's switches): not part of the drop-in boundary
 DIAG_PROTOTYPES = {
     "nb_selftest_ladder": (c_int, [c_uint32, c_uint32, POINTER(c_uint64), c_void_p]),
@@ -323,7 +339,7 @@ def _bind(path: str) -> ctypes.CDLL:
     _preload_torch_hip_runtime()
     lib = ctypes.CDLL(path)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SCENES_SEEN_PROTOTYPES.items()) + list(SCENES_LOCATED_PROTOTYPES.items()) \
-            + list(SCENES_POLICY_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
+            + list(SCENES_POLICY_PROTOTYPES.items()) + list(SCENES_SCORE_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

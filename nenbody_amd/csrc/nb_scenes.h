@@ -97,4 +97,23 @@ hipError_t launch_scenes_policy(const ScenesPolicyArgs &a, hipStream_t s);
 // What that step computes per eye in front of the actuation: the features and the limited outputs, indexed from first_eye.
 hipError_t launch_scenes_policy_observe(const ScenesPolicyArgs &a, hipStream_t s);
 
+// The score of a batch (nb_scenes_score.inc): one workgroup per scene in launch_scenes_nbody's shape, the
+// scene's positions and the partial sums in LDS -- 16 n + 32 LANES + 32 bytes, 65 568 at n = 2 048.  Every scene's record takes the
+// metrics of its current snapshot (Q1-Q7).  The caller has checked the arguments (scenes >= 1, 1 <= n <= kScenesMaxBodies,
+// radius_sq >= 0, a finite goal, score clear of pos and vel).
+struct SceneScore {                          // nb_scene_score
+    uint64_t near;
+    float spread, speed2, momentum2, goal2;
+    uint32_t steps, nonfinite;
+};
+struct ScenesScoreArgs {
+    const float4 *__restrict__ pos;          // scenes * n records each, read only
+    const float4 *__restrict__ vel;
+    SceneScore *__restrict__ score;          // scenes records, read, updated and written
+    uint32_t scenes, n;
+    float radius_sq;                         // Q2
+    float gx, gy, gz;                        // Q5
+};
+hipError_t launch_scenes_score(const ScenesScoreArgs &a, hipStream_t s);
+
 }  // namespace nbk

@@ -4,7 +4,9 @@
 // nb_scenes_step_boids_seen and nb_scenes_eyes_seen.  Section 14.2 adds gravity from located vision in the same four shapes:
 // nb_scenes_nbody_located_step_launch, nb_scenes_located_launch, nb_scenes_step_nbody_located and nb_scenes_eyes_located.  Section 14.4
 // adds a neural policy over each eye row: nb_policy_floats, nb_scenes_policy_step_launch and nb_scenes_policy_observe_launch, stateless,
-// and the context's nb_scenes_set_policy, nb_scenes_step_policy and nb_scenes_eyes_policy.  Included by
+// and the context's nb_scenes_set_policy, nb_scenes_step_policy and nb_scenes_eyes_policy.  Section 14.5 adds the score of every scene,
+// accumulated on the device: nb_scenes_score_launch, stateless, and the context's nb_scenes_set_score, nb_scenes_score,
+// nb_scenes_score_reset, nb_scenes_scores and nb_scenes_step_policy_scored.  Included by
 // nb_api.hip behind nb_vision_api.inc.  Every check runs before anything touches the device and has its own message naming the entry.
 
 static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
@@ -322,6 +324,9 @@ struct nb_scenes {
     uint32_t features = 0, hidden = 0, policies = 0;   // their shape; policies = 0: no policy set
     float accel_limit = 0.f;
     DeviceBuffer<uint32_t> pol_feat, pol_act;      // nb_scenes_eyes_policy's features and outputs for one range of scenes, grown on demand
+    DeviceBuffer<nbk::SceneScore> score;           // nb_scenes_set_score's records, one a scene
+    nb_score_params sp{};                          // its parameters
+    bool score_set = false;
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
@@ -754,15 +759,18 @@ static int scenes_policy_set_check(nb_scenes *ctx, const char *fn, uint32_t widt
     return policy_check(fn, ctx->features, ctx->hidden, width, ctx->policies, ctx->scenes, ctx->accel_limit, &ctx->err);
 }
 
-NB_EXPORT int nb_scenes_step_policy(nb_scenes *ctx, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
+// what nb_scenes_step_policy checks behind the context: the eye set-up, a state, a policy
+static int scenes_step_policy_check(nb_scenes *ctx, const char *fn, const float *up_xyz, const float *cp16, uint32_t width)
 {
-    static const char fn[] = "nb_scenes_step_policy";
-    int rc = ctx_check(ctx, fn);
-    if (rc != NB_OK) return rc;
-    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    int rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
     if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
     if (rc == NB_OK) rc = scenes_policy_set_check(ctx, fn, width);
-    if (rc != NB_OK) return rc;
+    return rc;
+}
+
+// k policy steps as nb_scenes_step_policy issues them, the checks done
+static int scenes_policy_steps(nb_scenes *ctx, const char *fn, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
+{
     return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [=](nb_scenes *ctx) -> int {
         nbk::ScenesPolicyArgs a = scenes_policy_args(ctx->n, 0u, ctx->scenes * ctx->n, ctx->cams.p, ctx->inst.p, width, ctx->features,
                                                      ctx->hidden, ctx->policies, ctx->policy.p, ctx->accel_limit);
@@ -771,6 +779,16 @@ NB_EXPORT int nb_scenes_step_policy(nb_scenes *ctx, uint32_t k, const float *up_
         NB_HIP(ctx, nbk::launch_scenes_policy(a, ctx->stream));
         return NB_OK;
     });
+}
+
+NB_EXPORT int nb_scenes_step_policy(nb_scenes *ctx, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
+{
+    static const char fn[] = "nb_scenes_step_policy";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_step_policy_check(ctx, fn, up_xyz, cp16, width);
+    if (rc != NB_OK) return rc;
+    return scenes_policy_steps(ctx, fn, k, up_xyz, cp16, width);
 }
 
 NB_EXPORT int nb_scenes_eyes_policy(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
@@ -791,6 +809,157 @@ NB_EXPORT int nb_scenes_eyes_policy(nb_scenes *ctx, uint32_t first_scene, uint32
         return NB_OK;
     };
     return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, rows, kNoPolicyOutputs, launch);
+}
+
+// ---- the score of every scene, accumulated on the device (DESIGN.md section 14.5) -----------------------------------------------------------
+static_assert(sizeof(nb_scene_score) == 32 && sizeof(nbk::SceneScore) == 32 && alignof(nbk::SceneScore) == 8, "Q7's record");
+static_assert(offsetof(nb_scene_score, spread) == offsetof(nbk::SceneScore, spread) && offsetof(nb_scene_score, steps) == offsetof(nbk::SceneScore, steps) &&
+                  offsetof(nb_scene_score, nonfinite) == offsetof(nbk::SceneScore, nonfinite),
+              "the header's record is the kernel's");
+static const char kCallSetScore[] = ": no score set (call nb_scenes_set_score first)";
+
+// Q2's radius and Q5's goal
+static int score_params_check(const char *fn, const nb_score_params &sp, std::string *err)
+{
+    if (!(sp.radius_sq >= 0.0f)) {
+        *err = std::string(fn) + ": radius_sq must be at least 0 (+inf: every pair)";
+        return NB_ERR_INVALID;
+    }
+    if (!(std::isfinite(sp.goal[0]) && std::isfinite(sp.goal[1]) && std::isfinite(sp.goal[2]))) {
+        *err = std::string(fn) + ": goal must be finite";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+static nbk::ScenesScoreArgs scenes_score_args(const nb_score_params &sp, uint32_t scenes, uint32_t n, const void *pos, const void *vel, void *score)
+{
+    nbk::ScenesScoreArgs a{};
+    a.pos = (const float4 *)pos, a.vel = (const float4 *)vel, a.score = (nbk::SceneScore *)score;
+    a.scenes = scenes, a.n = n;
+    a.radius_sq = sp.radius_sq, a.gx = sp.goal[0], a.gy = sp.goal[1], a.gz = sp.goal[2];
+    return a;
+}
+
+NB_EXPORT int nb_scenes_score_launch(const nb_score_params *sp, uint32_t scenes, uint32_t n, const void *pos, const void *vel, void *score,
+                                     void *stream)
+{
+    static const char fn[] = "nb_scenes_score_launch";
+    if (!sp || !pos || !vel || !score) {
+        g_tls_error = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    if (rc == NB_OK) rc = score_params_check(fn, *sp, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_records_check(fn, scenes, n, pos, vel, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if ((uintptr_t)score & 7u) {
+        g_tls_error = std::string(fn) + ": score must be 8-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t bytes = (size_t)scenes * n * sizeof(float4), sbytes = (size_t)scenes * sizeof(nb_scene_score);
+    if (ranges_overlap(score, sbytes, pos, bytes) || ranges_overlap(score, sbytes, vel, bytes)) {
+        g_tls_error = std::string(fn) + ": score must not overlap pos or vel";
+        return NB_ERR_INVALID;
+    }
+    rc = device_for_launch(pos, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    return launch_status(nbk::launch_scenes_score(scenes_score_args(*sp, scenes, n, pos, vel, score), (hipStream_t)stream),
+                         "nb: score kernel launch failed (scene batch): ", &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_set_score(nb_scenes *ctx, const nb_score_params *sp)
+{
+    static const char fn[] = "nb_scenes_set_score";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (!sp) {
+        ctx->err = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    rc = score_params_check(fn, *sp, &ctx->err);
+    if (rc != NB_OK) return rc;
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a score in flight runs under the parameters it was issued with
+    ctx->score_set = false;
+    NB_HIP(ctx, ctx->score.reserve(ctx->scenes));
+    NB_HIP(ctx, hipMemsetAsync(ctx->score.p, 0, (size_t)ctx->scenes * sizeof(nb_scene_score), ctx->stream));
+    ctx->sp = *sp;
+    ctx->score_set = true;
+    return NB_OK;
+}
+
+// the context holds a score
+static int scenes_score_set_check(nb_scenes *ctx, const char *fn)
+{
+    if (!ctx->score_set) {
+        ctx->err = std::string(fn) + kCallSetScore;
+        return NB_ERR_STATE;
+    }
+    return NB_OK;
+}
+
+// the current snapshot into the context's records, the checks done
+static int scenes_score_now(nb_scenes *ctx)
+{
+    NB_HIP(ctx, nbk::launch_scenes_score(scenes_score_args(ctx->sp, ctx->scenes, ctx->n, ctx->pos.p, ctx->vel.p, ctx->score.p), ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_score(nb_scenes *ctx)
+{
+    static const char fn[] = "nb_scenes_score";
+    int rc = ctx_check(ctx, fn, kCallScenesUpload);
+    if (rc == NB_OK) rc = scenes_score_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    RoctxRange range(fn);
+    return scenes_score_now(ctx);
+}
+
+NB_EXPORT int nb_scenes_score_reset(nb_scenes *ctx)
+{
+    static const char fn[] = "nb_scenes_score_reset";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_score_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    NB_HIP(ctx, hipMemsetAsync(ctx->score.p, 0, (size_t)ctx->scenes * sizeof(nb_scene_score), ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_scores(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, nb_scene_score *out_host)
+{
+    static const char fn[] = "nb_scenes_scores";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (!out_host) {
+        ctx->err = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
+        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
+        return NB_ERR_INVALID;
+    }
+    rc = scenes_score_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (scene_count == 0) return NB_OK;
+    NB_HIP(ctx, hipMemcpyAsync(out_host, ctx->score.p + first_scene, (size_t)scene_count * sizeof(nb_scene_score), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_step_policy_scored(nb_scenes *ctx, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
+{
+    static const char fn[] = "nb_scenes_step_policy_scored";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_step_policy_check(ctx, fn, up_xyz, cp16, width);
+    if (rc == NB_OK) rc = scenes_score_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    for (uint32_t s = 0; s < k; ++s) {
+        rc = scenes_policy_steps(ctx, fn, 1u, up_xyz, cp16, width);
+        if (rc == NB_OK) rc = scenes_score_now(ctx);
+        if (rc != NB_OK) return rc;
+    }
+    return NB_OK;
 }
 
 NB_EXPORT int nb_scenes_device_state(nb_scenes *ctx, const void **pos_rec, const void **vel_rec, const void **inst_16n)

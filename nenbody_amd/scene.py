@@ -441,6 +441,11 @@ def pack_policy(w1, b1, w2, b2) -> np.ndarray:
     return np.concatenate([w1.reshape(-1), b1, w2.reshape(-1), b2])
 
 
+# struct nb_scene_score (include/nenbody.h, Q7): what :meth:`SceneBatch.scores` returns, one record a scene
+SCORE_DTYPE = np.dtype([("near", np.uint64), ("spread", np.float32), ("speed2", np.float32), ("momentum2", np.float32),
+                        ("goal2", np.float32), ("steps", np.uint32), ("nonfinite", np.uint32)])
+
+
 class SceneBatch:
     """B independent scenes of n <= NB_SCENES_MAX_BODIES bodies, device-resident, stepped k times by ONE launch with one workgroup
     per scene.  Every scene gets the bits a :class:`Scene` of its n bodies gets.  ``positions`` and
@@ -570,6 +575,42 @@ class SceneBatch:
         self._check(self._lib.nb_scenes_eyes_policy(self._ctx, first_scene, scene_count, upv.ctypes.data, cpm.ctypes.data, width,
                                                     feat.ctypes.data, act.ctypes.data))
         return feat, act
+
+    def set_score(self, radius_sq: float, goal=(0.0, 0.0, 0.0)) -> None:
+        """The batch's score (nb_scenes_set_score): ``radius_sq`` >= 0 is the squared radius below which a pair
+        counts as near (inf: every pair), ``goal`` the point whose squared distance is summed.  Allocates one record a scene on first
+        use and clears the records.  May be called again."""
+        g = np.ascontiguousarray(goal, np.float32)
+        if g.shape != (3,):
+            raise ValueError("goal must have three components")
+        sp = _lib.NbScoreParams(float(radius_sq), (ctypes.c_float * 3)(*g.tolist()))
+        self._check(self._lib.nb_scenes_set_score(self._ctx, ctypes.byref(sp)))
+
+    def score(self) -> None:
+        """The current snapshot of every scene added to its record (nb_scenes_score): one kernel, asynchronous; every float by a
+        stated binary32 order (Q1-Q7 of include/nenbody.h), the same bits from run to run."""
+        self._check(self._lib.nb_scenes_score(self._ctx))
+
+    def score_reset(self) -> None:
+        """The records cleared (nb_scenes_score_reset), asynchronous.  An upload does not clear them."""
+        self._check(self._lib.nb_scenes_score_reset(self._ctx))
+
+    def scores(self, first_scene: int = 0, scene_count: Optional[int] = None) -> np.ndarray:
+        """The records of scenes [first_scene, first_scene + scene_count) (nb_scenes_scores): a structured array of dtype
+        :data:`SCORE_DTYPE`, 32 bytes a scene.  Waits for the stream."""
+        if scene_count is None:
+            scene_count = self.scenes - first_scene
+        if first_scene < 0 or scene_count < 0:
+            raise ValueError("first_scene and scene_count must be >= 0")
+        out = np.zeros(max(scene_count, 1), SCORE_DTYPE)
+        self._check(self._lib.nb_scenes_scores(self._ctx, first_scene, scene_count, out.ctypes.data))
+        return out[:scene_count]
+
+    def step_policy_scored(self, k: int = 1, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None) -> None:
+        """k times :meth:`step_policy` (1) then :meth:`score` (nb_scenes_step_policy_scored): a rollout scored where it runs; read
+        :meth:`scores` when it ends."""
+        upv, cpm = self._eye_setup(width, up, cp)
+        self._check(self._lib.nb_scenes_step_policy_scored(self._ctx, int(k), upv.ctypes.data, cpm.ctypes.data, width))
 
     def _download(self, what: int) -> np.ndarray:
         out = np.empty((self.scenes, self.n, 4, 4) if what == 2 else (self.scenes, self.n, 3), np.float32)
