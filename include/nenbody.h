@@ -419,6 +419,63 @@ typedef struct nb_scene_score {
  * nb_scenes_step_policy_scored on a context. */
 #include "nenbody_scenes_score.h"
 
+/* ---- scene batches: an evolution-strategies generation on the device ----------------------------------
+ * The tuner behind the policy and the score: the population of a generation drawn from a mean by a counter-based generator, the
+ * scenes' score records ranked, the mean moved along the rank-weighted sum of the draws.  Every step is asynchronous on a stream;
+ * every float operation below is one binary32 operation, round to nearest, in the order written, with no contraction and subnormals
+ * kept; every sum is an exact integer.  The bits depend on (seed, generation, scene, weight index) and on nothing else.
+ * M = nb_policy_floats(F, H) for a policy shape (F, H) within the limits; B = scenes, 1 <= B <= NB_ES_MAX_POPULATION.  Parameters
+ * nb_es_params: sigma >= 0 and finite; step finite; coef[6] finite; seed, 64 bits.  g is the generation, a 32-bit word.  All words
+ * below are unsigned 32-bit words unless said otherwise; hi and lo are the halves of a 64-bit product.
+ *   E1:  the generator is Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011).  M0 = 0xD2511F53, M1 = 0xCD9E8D57; the key (k0, k1) starts
+ *        as (seed & 0xFFFFFFFF, seed >> 32).  One round maps the counter (c0, c1, c2, c3) to
+ *        (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)).  Ten rounds; between two rounds (nine times) the key is
+ *        bumped: k0 += 0x9E3779B9, k1 += 0xBB67AE85, modulo 2^32.  For scene s and weight m the counter is (m >> 1, s >> 1, g, 0);
+ *        the output is (x0, x1, x2, x3).  Counter 0 under key 0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   E2:  the draw: (a, b) = (x0, x1) for even m, (x2, x3) for odd m; k = (a & 0xFFFF) + (a >> 16) + (b & 0xFFFF) + (b >> 16) - 131070,
+ *        an integer in [-131070, 131070], a centred sum of four 16-bit uniforms.  Scenes 2q and 2q+1 are mirrored:
+ *        k(s, m) = (s & 1) ? -k : k.  e = (float)k * C, C the binary32 value with the bits 0x37DDB3D7 (sqrt(3) * 2^-16, one over the
+ *        standard deviation of k); (float)k is exact
+ *   E3:  the population: theta[s*M + m] = mean[m] + (sigma * e): two operations
+ *   E4:  the fitness of scene s from its nb_scene_score, larger is better: phi = +0; then over the fields in the order (float)near,
+ *        spread, speed2, momentum2, goal2, (float)nonfinite: phi = phi + (coef[i] * field_i).  A term whose coefficient is +0 or -0 is
+ *        skipped, so a field the caller does not weigh may be infinite or a NaN.  (float)near and (float)nonfinite are the integer
+ *        rounded to nearest even ONCE; a route through binary64 rounds near twice above 2^53 and is wrong.  As the sum starts from
+ *        +0, phi is never -0: a -0 term gives +0.  Which NaN a NaN phi is, is not part of the rule
+ *   E5:  the rank: key32 = 0 for a NaN phi; otherwise, w being the bits of phi, key32 = ~w where w has its sign bit set and
+ *        w | 0x80000000 where it has not: monotone in phi, -0 below +0, a NaN below everything.  key64 = key32 << 32 | s.
+ *        r_s = the number of scenes t with key64_t < key64_s: a permutation of 0 .. B-1, ties broken by scene index
+ *   E6:  the utility: u_s = 2*r_s - (B - 1), an integer; the utilities sum to 0
+ *   E7:  the update: A_m = the sum over s of u_s * k(s, m), an EXACT integer, |A_m| < 2^42, in any order;
+ *        mean'[m] = mean[m] + (step * ((float)A_m * C)), (float)A_m rounded to nearest even once.  The caller folds the learning
+ *        rate, 1/(B*sigma) and the scale of the utilities into step.  B = 1 has u_0 = 0 and leaves the mean as it is but for -0,
+ *        which becomes +0 under a step of +0 or above
+ *   E8:  theta of scene s does not depend on B; no word depends on the grid, the workgroup shape, on how scenes or weights are split
+ *        over launches, or on the run
+ * The ranking also writes a report: best_scene is the scene of rank B-1, best_fitness its phi, nan_count the number of scenes whose
+ * phi is a NaN, generation the g it ranked.
+ * Decisions where the rule's source left a choice: the stateless update takes the mean it reads and the mean it writes as two
+ * arguments, which may be the same pointer (in place) and may otherwise not overlap; nb_scenes_es_result before the first
+ * nb_scenes_es_update is NB_ERR_STATE; the context's generation counts modulo 2^32. */
+#define NB_ES_MAX_POPULATION 4096u
+typedef struct nb_es_params {
+    float sigma;   /* E3 */
+    float step;    /* E7 */
+    float coef[6]; /* E4: near, spread, speed2, momentum2, goal2, nonfinite */
+    uint64_t seed; /* E1 */
+} nb_es_params;    /* 40 bytes */
+typedef struct nb_es_report {
+    uint32_t best_scene;
+    float best_fitness;
+    uint32_t nan_count;
+    uint32_t generation;
+} nb_es_report; /* 16 bytes */
+
+/* The ten entries are declared in nenbody_scenes_es.h, which this header includes: the stateless nb_scenes_es_perturb_launch and
+ * nb_scenes_es_update_launch on caller-owned device memory, and nb_scenes_es_set, nb_scenes_es_perturb, nb_scenes_es_update,
+ * nb_scenes_es_mean, nb_scenes_es_result, nb_scenes_es_generation, nb_scenes_keep and nb_scenes_rewind on a context. */
+#include "nenbody_scenes_es.h"
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which

@@ -475,6 +475,48 @@ public:
     {
         check_sc(nb_scenes_step_policy_scored(ctx_, k, up.data(), cp[0].data(), width));
     }
+    // The batch's search (nb_scenes_es_set): mean, nb_policy_floats(features, hidden) floats, is the policy the
+    // population -- one policy a scene, at most NB_ES_MAX_POPULATION scenes -- is drawn around; ep holds the draw's scale, the update's
+    // step, the fitness's six coefficients and the seed.  The generation starts at 0.
+    void es_set(const std::vector<float> &mean, uint32_t features, uint32_t hidden, const nb_es_params &ep,
+                float accel_limit = INFINITY)
+    {
+        if (mean.size() != nb_policy_floats(features, hidden) || mean.empty())
+            throw std::invalid_argument("mean must hold nb_policy_floats(features, hidden) floats");
+        check_sc(nb_scenes_es_set(ctx_, features, hidden, mean.data(), accel_limit, &ep));
+        es_floats_ = mean.size();
+        features_ = features;
+    }
+    // The batch's policies become the population of the current generation (nb_scenes_es_perturb), asynchronous.
+    void es_perturb() { check_sc(nb_scenes_es_perturb(ctx_)); }
+    // The score records ranked, the mean updated in place and the generation incremented (nb_scenes_es_update), asynchronous.
+    void es_update() { check_sc(nb_scenes_es_update(ctx_)); }
+    // The mean (nb_scenes_es_mean).  Waits for the stream.
+    std::vector<float> es_mean()
+    {
+        std::vector<float> out(es_floats_ ? es_floats_ : 1);
+        check_sc(nb_scenes_es_mean(ctx_, out.data()));
+        out.resize(es_floats_);
+        return out;
+    }
+    // What the last es_update left (nb_scenes_es_result): the report, the fitnesses and the ranks, 0 the worst.  Waits for the stream.
+    struct EsResult {
+        nb_es_report report;
+        std::vector<float> fitness;
+        std::vector<uint32_t> rank;
+    };
+    EsResult es_result()
+    {
+        EsResult o{};
+        o.fitness.resize(scenes_), o.rank.resize(scenes_);
+        check_sc(nb_scenes_es_result(ctx_, &o.report, o.fitness.data(), o.rank.data()));
+        return o;
+    }
+    uint32_t es_generation() const { return nb_scenes_es_generation(ctx_); }
+    // Positions, velocities and the step counter copied to buffers the batch keeps (nb_scenes_keep), on the device; rewind copies them
+    // back (nb_scenes_rewind), asynchronous.  An upload does not drop the kept state.
+    void keep() { check_sc(nb_scenes_keep(ctx_)); }
+    void rewind() { check_sc(nb_scenes_rewind(ctx_)); }
     void sync() { check_sc(nb_scenes_sync(ctx_)); }
     uint64_t steps_done() const { return nb_scenes_steps(ctx_); }
     void download(std::vector<Vec3> &positions, std::vector<Vec3> &velocities, std::vector<Mat4> &instances)
@@ -514,6 +556,7 @@ private:
     nb_scenes *ctx_ = nullptr;
     uint32_t scenes_ = 0, n_ = 0;
     uint32_t features_ = 0;   // F of the policy set last; 0: none
+    size_t es_floats_ = 0;    // the floats of the search's mean; 0: none
 };
 
 // One rank's share of a scene on a multi-GPU host (one process or thread per GPU): nb_shard_* of nenbody.h.  Every rank

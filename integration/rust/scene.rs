@@ -134,6 +134,17 @@ extern "C" {
     fn nb_scenes_score_reset(ctx: *mut NbScenes) -> c_int;
     fn nb_scenes_scores(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, out_host: *mut NbSceneScore) -> c_int;
     fn nb_scenes_step_policy_scored(ctx: *mut NbScenes, k: u32, up_xyz: *const f32, cp16: *const f32, width: u32) -> c_int;
+    // an evolution-strategies generation on the device (include/nenbody_scenes_es.h)
+    fn nb_scenes_es_perturb_launch(ep: *const NbEsParams, features: u32, hidden: u32, generation: u32, first_scene: u32, count: u32, mean: *const c_void, theta_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_es_update_launch(ep: *const NbEsParams, features: u32, hidden: u32, generation: u32, scenes: u32, score: *const c_void, mean: *const c_void, mean_out: *mut c_void, rank_out: *mut c_void, fitness_out: *mut c_void, report_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_es_set(ctx: *mut NbScenes, features: u32, hidden: u32, mean_host: *const f32, accel_limit: f32, ep: *const NbEsParams) -> c_int;
+    fn nb_scenes_es_perturb(ctx: *mut NbScenes) -> c_int;
+    fn nb_scenes_es_update(ctx: *mut NbScenes) -> c_int;
+    fn nb_scenes_es_mean(ctx: *mut NbScenes, out_host: *mut f32) -> c_int;
+    fn nb_scenes_es_result(ctx: *mut NbScenes, report: *mut NbEsReport, fitness: *mut f32, rank: *mut u32) -> c_int;
+    fn nb_scenes_es_generation(ctx: *const NbScenes) -> u32;
+    fn nb_scenes_keep(ctx: *mut NbScenes) -> c_int;
+    fn nb_scenes_rewind(ctx: *mut NbScenes) -> c_int;
     // the same on caller-owned device memory, in place
     fn nb_scenes_nbody_step_launch(params: *const NbParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_boids_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
@@ -165,6 +176,28 @@ pub struct NbSceneScore {
     pub nonfinite: u32,
 }
 
+/// nb_es_params, 40 bytes: the draw's scale (E3), the update's step (E7), the fitness's coefficients over (near, spread, speed2,
+/// momentum2, goal2, nonfinite) (E4) and the generator's seed (E1)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct NbEsParams {
+    pub sigma: f32,
+    pub step: f32,
+    pub coef: [f32; 6],
+    pub seed: u64,
+}
+
+/// nb_es_report, 16 bytes: what the ranking of a generation leaves
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct NbEsReport {
+    pub best_scene: u32,
+    pub best_fitness: f32,
+    pub nan_count: u32,
+    pub generation: u32,
+}
+
+pub const NB_ES_MAX_POPULATION: u32 = 4096;
 pub const NB_SCENES_MAX_BODIES: u32 = 2048;
 pub const NB_POLICY_MAX_FEATURES: u32 = 256;
 pub const NB_POLICY_MAX_HIDDEN: u32 = 64;
@@ -798,6 +831,7 @@ pub struct SceneBatch {
     pub scenes: usize,
     pub n: usize,
     policy_features: usize, // F of the policy set last; 0: none
+    es_floats: usize,       // the floats of the search's mean; 0: none
 }
 
 unsafe impl Send for SceneBatch {}
@@ -824,7 +858,7 @@ impl SceneBatch {
         assert!(positions.len() == scenes * n && velocities.len() == scenes * n, "positions and velocities must hold scenes * n bodies");
         let mut ctx: *mut NbScenes = std::ptr::null_mut();
         check_scenes(unsafe { nb_scenes_create(scenes as u32, n as u32, &params, &mut ctx) }, std::ptr::null())?;
-        let batch = SceneBatch { ctx, scenes, n, policy_features: 0 };
+        let batch = SceneBatch { ctx, scenes, n, policy_features: 0, es_floats: 0 };
         check_scenes(unsafe { nb_scenes_upload(batch.ctx, positions.as_ptr() as *const f32, velocities.as_ptr() as *const f32) }, batch.ctx)?;
         Ok(batch)
     }
@@ -980,6 +1014,58 @@ impl SceneBatch {
             unsafe { nb_scenes_step_policy_scored(self.ctx, k, up.as_ptr(), cp.as_ptr() as *const f32, width) },
             self.ctx,
         )
+    }
+
+    /// the batch's search (nb_scenes_es_set): `mean` of policy_floats(features, hidden) floats is the policy
+    /// the population -- one policy a scene, at most NB_ES_MAX_POPULATION scenes -- is drawn around; the generation starts at 0
+    pub fn es_set(&mut self, features: u32, hidden: u32, mean: &[f32], accel_limit: f32, ep: &NbEsParams) -> Result<(), SceneError> {
+        assert_eq!(mean.len(), policy_floats(features, hidden), "mean must hold policy_floats(features, hidden) floats");
+        check_scenes(unsafe { nb_scenes_es_set(self.ctx, features, hidden, mean.as_ptr(), accel_limit, ep) }, self.ctx)?;
+        self.es_floats = mean.len();
+        self.policy_features = features as usize;
+        Ok(())
+    }
+
+    /// the batch's policies become the population of the current generation (nb_scenes_es_perturb), asynchronous
+    pub fn es_perturb(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_es_perturb(self.ctx) }, self.ctx)
+    }
+
+    /// the score records ranked, the mean updated in place and the generation incremented (nb_scenes_es_update), asynchronous
+    pub fn es_update(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_es_update(self.ctx) }, self.ctx)
+    }
+
+    /// the mean (nb_scenes_es_mean); waits for the stream
+    pub fn es_mean(&mut self) -> Result<Vec<f32>, SceneError> {
+        let mut out = vec![0.0f32; self.es_floats.max(1)];
+        check_scenes(unsafe { nb_scenes_es_mean(self.ctx, out.as_mut_ptr()) }, self.ctx)?;
+        out.truncate(self.es_floats);
+        Ok(out)
+    }
+
+    /// what the last es_update left (nb_scenes_es_result): the report, the fitnesses and the ranks (0 the worst); waits for the stream
+    pub fn es_result(&mut self) -> Result<(NbEsReport, Vec<f32>, Vec<u32>), SceneError> {
+        let mut report = NbEsReport::default();
+        let mut fitness = vec![0.0f32; self.scenes];
+        let mut rank = vec![0u32; self.scenes];
+        check_scenes(unsafe { nb_scenes_es_result(self.ctx, &mut report, fitness.as_mut_ptr(), rank.as_mut_ptr()) }, self.ctx)?;
+        Ok((report, fitness, rank))
+    }
+
+    /// the generation the next es_perturb draws
+    pub fn es_generation(&self) -> u32 {
+        unsafe { nb_scenes_es_generation(self.ctx) }
+    }
+
+    /// positions, velocities and the step counter copied to buffers the batch keeps (nb_scenes_keep), on the device
+    pub fn keep(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_keep(self.ctx) }, self.ctx)
+    }
+
+    /// the kept state copied back (nb_scenes_rewind), asynchronous
+    pub fn rewind(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_rewind(self.ctx) }, self.ctx)
     }
 
     /// positions, velocities and model matrices of every body, scene after scene

@@ -34,6 +34,7 @@ NB_RING_OWN, NB_RING_REST, NB_RING_SUMS, NB_RING_OWN_READY = 1, 2, 3, 4
 NB_SCENES_MAX_BODIES = 2048
 NB_POLICY_MAX_FEATURES = 256
 NB_POLICY_MAX_HIDDEN = 64
+NB_ES_MAX_POPULATION = 4096
 NB_EYES_NONE = 0xFFFFFFFF
 NB_EYES_SEE_SELF = 1
 NB_EYES_MAX_WIDTH = 4096
@@ -76,6 +77,19 @@ class NbScoreParams(ctypes.Structure):
     """struct nb_score_params (include/nenbody.h, Q2 and Q5): the radius of `near`, squared, and the goal."""
 
     _fields_ = [("radius_sq", c_float), ("goal", c_float * 3)]
+
+
+class NbEsParams(ctypes.Structure):
+    """struct nb_es_params (include/nenbody.h, E1-E7): the draw's scale, the update's step, the fitness's six coefficients over
+    (near, spread, speed2, momentum2, goal2, nonfinite) and the generator's seed."""
+
+    _fields_ = [("sigma", c_float), ("step", c_float), ("coef", c_float * 6), ("seed", c_uint64)]
+
+
+class NbEsReport(ctypes.Structure):
+    """struct nb_es_report (include/nenbody.h): what the ranking of a generation leaves."""
+
+    _fields_ = [("best_scene", c_uint32), ("best_fitness", c_float), ("nan_count", c_uint32), ("generation", c_uint32)]
 
 
 class NbError(RuntimeError):
@@ -277,6 +291,21 @@ SCENES_SCORE_PROTOTYPES = {
     "nb_scenes_step_policy_scored": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]),
 }
 
+# include/nenbody_scenes_es.h: an evolution-strategies generation on the device, bound likewise
+ES_PROTOTYPES = {
+    "nb_scenes_es_perturb_launch": (c_int, [POINTER(NbEsParams), c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_es_update_launch": (c_int, [POINTER(NbEsParams), c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_es_set": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_float, POINTER(NbEsParams)]),
+    "nb_scenes_es_perturb": (c_int, [c_void_p]),
+    "nb_scenes_es_update": (c_int, [c_void_p]),
+    "nb_scenes_es_mean": (c_int, [c_void_p, c_void_p]),
+    "nb_scenes_es_result": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_es_generation": (c_uint32, [c_void_p]),
+    "nb_scenes_keep": (c_int, [c_void_p]),
+    "nb_scenes_rewind": (c_int, [c_void_p]),
+}
+
 # every symbol include/nenbody_diag.h declares (self-tests, the test suite's switches): not part of the drop-in boundary
 DIAG_PROTOTYPES = {
     "nb_selftest_ladder": (c_int, [c_uint32, c_uint32, POINTER(c_uint64), c_void_p]),
@@ -339,7 +368,7 @@ def _bind(path: str) -> ctypes.CDLL:
     _preload_torch_hip_runtime()
     lib = ctypes.CDLL(path)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SCENES_SEEN_PROTOTYPES.items()) + list(SCENES_LOCATED_PROTOTYPES.items()) \
-            + list(SCENES_POLICY_PROTOTYPES.items()) + list(SCENES_SCORE_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
+            + list(SCENES_POLICY_PROTOTYPES.items()) + list(SCENES_SCORE_PROTOTYPES.items()) + list(ES_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

@@ -116,4 +116,22 @@ struct ScenesScoreArgs {
 };
 hipError_t launch_scenes_score(const ScenesScoreArgs &a, hipStream_t s);
 
+// One evolution-strategies generation over a batch (nb_scenes_es.inc): the population of a generation
+// drawn from a mean, the score records ranked, the mean updated.  The caller has checked the arguments (1 <= scenes <=
+// kEsMaxPopulation, m = policy_floats of a valid shape, sigma >= 0 and finite, step and the coefficients finite).
+constexpr uint32_t kEsMaxPopulation = 4096;   // NB_ES_MAX_POPULATION: the keys and counts of one ranking workgroup fit the default LDS
+struct EsArgs {
+    uint64_t seed;
+    uint32_t g;                              // the generation
+    uint32_t scenes, m;                      // B (the perturb kernel does not read it: E8) and M
+    float sigma, step;
+    float c0, c1, c2, c3, c4, c5;            // E4's coefficients, in the order of the fields
+};
+// theta of scenes [first, first + count), count >= 1, first + count <= kEsMaxPopulation: count * m floats
+hipError_t launch_es_perturb(const EsArgs &a, uint32_t first, uint32_t count, const float *mean, float *theta, hipStream_t s);
+// E4-E5 in ONE workgroup: rank, a.scenes words; fitness, as many floats, or NULL; report, the four words of nb_es_report, or NULL
+hipError_t launch_es_rank(const EsArgs &a, const SceneScore *score, uint32_t *rank, float *fitness, uint32_t *report, hipStream_t s);
+// E6-E7 from the ranks: mean_out may be mean_in itself
+hipError_t launch_es_update(const EsArgs &a, const uint32_t *rank, const float *mean_in, float *mean_out, hipStream_t s);
+
 }  // namespace nbk

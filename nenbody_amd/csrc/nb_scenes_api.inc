@@ -6,7 +6,9 @@
 // adds a neural policy over each eye row: nb_policy_floats, nb_scenes_policy_step_launch and nb_scenes_policy_observe_launch, stateless,
 // and the context's nb_scenes_set_policy, nb_scenes_step_policy and nb_scenes_eyes_policy.  Section 14.5 adds the score of every scene,
 // accumulated on the device: nb_scenes_score_launch, stateless, and the context's nb_scenes_set_score, nb_scenes_score,
-// nb_scenes_score_reset, nb_scenes_scores and nb_scenes_step_policy_scored.  Included by
+// nb_scenes_score_reset, nb_scenes_scores and nb_scenes_step_policy_scored.  Section 14.6 adds an evolution-strategies generation:
+// nb_scenes_es_perturb_launch and nb_scenes_es_update_launch, stateless, and the context's nb_scenes_es_set, nb_scenes_es_perturb,
+// nb_scenes_es_update, nb_scenes_es_mean, nb_scenes_es_result, nb_scenes_es_generation, nb_scenes_keep and nb_scenes_rewind.  Included by
 // nb_api.hip behind nb_vision_api.inc.  Every check runs before anything touches the device and has its own message naming the entry.
 
 static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
@@ -327,6 +329,17 @@ struct nb_scenes {
     DeviceBuffer<nbk::SceneScore> score;           // nb_scenes_set_score's records, one a scene
     nb_score_params sp{};                          // its parameters
     bool score_set = false;
+    DeviceBuffer<float> es_mean;                   // nb_scenes_es_set's mean: nb_policy_floats floats, updated in place
+    DeviceBuffer<uint32_t> es_rank;                // what the last nb_scenes_es_update left: scenes ranks,
+    DeviceBuffer<float> es_fitness;                // scenes fitnesses
+    DeviceBuffer<uint32_t> es_report;              // and the four words of nb_es_report
+    nb_es_params ep{};                             // its parameters; the shape and the limit of the population's policies
+    uint32_t es_features = 0, es_hidden = 0, es_generation = 0;
+    float es_limit = 0.f;
+    bool es_set = false, es_updated = false;
+    DeviceBuffer<float4> pos_kept, vel_kept;       // nb_scenes_keep's copy of pos and vel
+    uint64_t steps_kept = 0;                       // and of the step counter
+    bool kept = false;
     bool uploaded = false;
     uint64_t steps = 0;
     std::string err;
@@ -959,6 +972,259 @@ NB_EXPORT int nb_scenes_step_policy_scored(nb_scenes *ctx, uint32_t k, const flo
         if (rc == NB_OK) rc = scenes_score_now(ctx);
         if (rc != NB_OK) return rc;
     }
+    return NB_OK;
+}
+
+// ---- an evolution-strategies generation on the device (DESIGN.md section 14.6) --------------------------------------------------------------
+static_assert(NB_ES_MAX_POPULATION == nbk::kEsMaxPopulation, "the header's limit is the kernels'");
+static_assert(sizeof(nb_es_params) == 40 && offsetof(nb_es_params, seed) == 32 && sizeof(nb_es_report) == 16, "E1-E7's parameters and the report");
+static const char kCallEsSet[] = ": no search set (call nb_scenes_es_set first)";
+static const char kCallEsUpdate[] = ": no generation updated (call nb_scenes_es_update first)";
+static const char kCallKeep[] = ": no state kept (call nb_scenes_keep first)";
+
+// E3's sigma, E7's step and E4's coefficients
+static int es_params_check(const char *fn, const nb_es_params &ep, std::string *err)
+{
+    if (!(ep.sigma >= 0.0f) || std::isinf(ep.sigma)) {
+        *err = std::string(fn) + ": sigma must be at least 0 and finite";
+        return NB_ERR_INVALID;
+    }
+    if (!std::isfinite(ep.step)) {
+        *err = std::string(fn) + ": step must be finite";
+        return NB_ERR_INVALID;
+    }
+    for (const float c : ep.coef)
+        if (!std::isfinite(c)) {
+            *err = std::string(fn) + ": coef must be finite";
+            return NB_ERR_INVALID;
+        }
+    return NB_OK;
+}
+
+// the policy shape of a search: policy_check's two bounds, with nothing else of it in play
+static int es_shape_check(const char *fn, uint32_t features, uint32_t hidden, std::string *err)
+{
+    return policy_check(fn, features, hidden, 0u, 1u, 1u, 0.0f, err);
+}
+
+static nbk::EsArgs es_args(const nb_es_params &ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t scenes)
+{
+    nbk::EsArgs a{};
+    a.seed = ep.seed, a.g = generation, a.scenes = scenes, a.m = (uint32_t)nbk::policy_floats(features, hidden);
+    a.sigma = ep.sigma, a.step = ep.step;
+    a.c0 = ep.coef[0], a.c1 = ep.coef[1], a.c2 = ep.coef[2], a.c3 = ep.coef[3], a.c4 = ep.coef[4], a.c5 = ep.coef[5];
+    return a;
+}
+
+NB_EXPORT int nb_scenes_es_perturb_launch(const nb_es_params *ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t first_scene,
+                                          uint32_t count, const void *mean, void *theta_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_es_perturb_launch";
+    if (!ep || !mean || !theta_out) {
+        g_tls_error = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    int rc = es_shape_check(fn, features, hidden, &g_tls_error);
+    if (rc == NB_OK) rc = es_params_check(fn, *ep, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if ((uint64_t)first_scene + count > NB_ES_MAX_POPULATION) {
+        g_tls_error = std::string(fn) + ": scenes [first_scene, first_scene + count) must lie in 0 .. NB_ES_MAX_POPULATION (4096)";
+        return NB_ERR_INVALID;
+    }
+    if (((uintptr_t)mean | (uintptr_t)theta_out) & 3u) {
+        g_tls_error = std::string(fn) + ": mean and theta_out must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t m = nbk::policy_floats(features, hidden);
+    if (ranges_overlap(theta_out, (size_t)count * m * sizeof(float), mean, m * sizeof(float))) {
+        g_tls_error = std::string(fn) + ": theta_out must not overlap mean";
+        return NB_ERR_INVALID;
+    }
+    if (count == 0) return NB_OK;
+    rc = device_for_launch(mean, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    return launch_status(nbk::launch_es_perturb(es_args(*ep, features, hidden, generation, 0u), first_scene, count, (const float *)mean,
+                                                (float *)theta_out, (hipStream_t)stream),
+                         "nb: perturb kernel launch failed (scene batch, search): ", &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t scenes,
+                                         const void *score, const void *mean, void *mean_out, void *rank_out, void *fitness_out,
+                                         void *report_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_es_update_launch";
+    if (!ep || !score || !mean || !mean_out || !rank_out) {
+        g_tls_error = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    int rc = es_shape_check(fn, features, hidden, &g_tls_error);
+    if (rc == NB_OK) rc = es_params_check(fn, *ep, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (scenes == 0 || scenes > NB_ES_MAX_POPULATION) {
+        g_tls_error = std::string(fn) + ": scenes must be 1 .. NB_ES_MAX_POPULATION (4096)";
+        return NB_ERR_INVALID;
+    }
+    if ((uintptr_t)score & 7u) {
+        g_tls_error = std::string(fn) + ": score must be 8-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    if ((uintptr_t)mean & 3u) {
+        g_tls_error = std::string(fn) + ": mean must be 4-byte aligned";
+        return NB_ERR_INVALID;
+    }
+    const size_t mbytes = nbk::policy_floats(features, hidden) * sizeof(float);
+    const bool in_place = mean_out == mean;   // the update may be in place: a weight's word is read and written by one lane
+    const ByteRange in[2] = {{score, (size_t)scenes * sizeof(nb_scene_score)}, {in_place ? nullptr : mean, mbytes}};
+    const ByteRange out[4] = {{mean_out, mbytes}, {rank_out, (size_t)scenes * 4u}, {fitness_out, (size_t)scenes * 4u}, {report_out, sizeof(nb_es_report)}};
+    rc = outputs_check(fn, out, 0xFu, "", true, in, 2, kScenesSeenAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = device_for_launch(score, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    const nbk::EsArgs a = es_args(*ep, features, hidden, generation, scenes);
+    rc = launch_status(nbk::launch_es_rank(a, (const nbk::SceneScore *)score, (uint32_t *)rank_out, (float *)fitness_out, (uint32_t *)report_out,
+                                           (hipStream_t)stream),
+                       "nb: rank kernel launch failed (scene batch, search): ", &g_tls_error);
+    if (rc != NB_OK) return rc;
+    return launch_status(nbk::launch_es_update(a, (const uint32_t *)rank_out, (const float *)mean, (float *)mean_out, (hipStream_t)stream),
+                         "nb: update kernel launch failed (scene batch, search): ", &g_tls_error);
+}
+
+// the context holds a search
+static int scenes_es_set_check(nb_scenes *ctx, const char *fn)
+{
+    if (!ctx->es_set) {
+        ctx->err = std::string(fn) + kCallEsSet;
+        return NB_ERR_STATE;
+    }
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_es_set(nb_scenes *ctx, uint32_t features, uint32_t hidden, const float *mean_host, float accel_limit, const nb_es_params *ep)
+{
+    static const char fn[] = "nb_scenes_es_set";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (!mean_host || !ep) {
+        ctx->err = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    rc = policy_check(fn, features, hidden, 0u, ctx->scenes, ctx->scenes, accel_limit, &ctx->err);
+    if (rc == NB_OK) rc = es_params_check(fn, *ep, &ctx->err);
+    if (rc != NB_OK) return rc;
+    if (ctx->scenes > NB_ES_MAX_POPULATION) {
+        ctx->err = std::string(fn) + ": a search takes a batch of at most NB_ES_MAX_POPULATION (4096) scenes";
+        return NB_ERR_INVALID;
+    }
+    const size_t m = nbk::policy_floats(features, hidden);
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step or an update in flight may still read the policies and the mean
+    ctx->es_set = ctx->es_updated = false;
+    ctx->policies = 0;                               // the policies' buffer may be replaced: none is set until nb_scenes_es_perturb
+    NB_HIP(ctx, ctx->policy.reserve((size_t)ctx->scenes * m));
+    NB_HIP(ctx, ctx->es_mean.reserve(m));
+    NB_HIP(ctx, ctx->es_rank.reserve(ctx->scenes));
+    NB_HIP(ctx, ctx->es_fitness.reserve(ctx->scenes));
+    NB_HIP(ctx, ctx->es_report.reserve(4));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->es_mean.p, mean_host, m * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
+    ctx->es_features = features, ctx->es_hidden = hidden, ctx->es_limit = accel_limit, ctx->ep = *ep;
+    ctx->es_generation = 0;
+    ctx->es_set = true;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_es_perturb(nb_scenes *ctx)
+{
+    static const char fn[] = "nb_scenes_es_perturb";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    RoctxRange range(fn);
+    NB_HIP(ctx, nbk::launch_es_perturb(es_args(ctx->ep, ctx->es_features, ctx->es_hidden, ctx->es_generation, ctx->scenes), 0u, ctx->scenes,
+                                       ctx->es_mean.p, ctx->policy.p, ctx->stream));
+    ctx->features = ctx->es_features, ctx->hidden = ctx->es_hidden, ctx->policies = ctx->scenes, ctx->accel_limit = ctx->es_limit;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_es_update(nb_scenes *ctx)
+{
+    static const char fn[] = "nb_scenes_es_update";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_score_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    RoctxRange range(fn);
+    const nbk::EsArgs a = es_args(ctx->ep, ctx->es_features, ctx->es_hidden, ctx->es_generation, ctx->scenes);
+    NB_HIP(ctx, nbk::launch_es_rank(a, ctx->score.p, ctx->es_rank.p, ctx->es_fitness.p, ctx->es_report.p, ctx->stream));
+    NB_HIP(ctx, nbk::launch_es_update(a, ctx->es_rank.p, ctx->es_mean.p, ctx->es_mean.p, ctx->stream));
+    ctx->es_generation += 1u;
+    ctx->es_updated = true;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_es_mean(nb_scenes *ctx, float *out_host)
+{
+    static const char fn[] = "nb_scenes_es_mean";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (!out_host) {
+        ctx->err = std::string(fn) + ": null argument";
+        return NB_ERR_INVALID;
+    }
+    rc = scenes_es_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    const size_t m = nbk::policy_floats(ctx->es_features, ctx->es_hidden);
+    NB_HIP(ctx, hipMemcpyAsync(out_host, ctx->es_mean.p, m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_es_result(nb_scenes *ctx, nb_es_report *report, float *fitness, uint32_t *rank)
+{
+    static const char fn[] = "nb_scenes_es_result";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (!ctx->es_updated) {
+        ctx->err = std::string(fn) + kCallEsUpdate;
+        return NB_ERR_STATE;
+    }
+    if (report) NB_HIP(ctx, hipMemcpyAsync(report, ctx->es_report.p, sizeof(nb_es_report), hipMemcpyDeviceToHost, ctx->stream));
+    if (fitness) NB_HIP(ctx, hipMemcpyAsync(fitness, ctx->es_fitness.p, (size_t)ctx->scenes * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (rank) NB_HIP(ctx, hipMemcpyAsync(rank, ctx->es_rank.p, (size_t)ctx->scenes * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT uint32_t nb_scenes_es_generation(const nb_scenes *ctx) { return ctx ? ctx->es_generation : 0u; }
+
+NB_EXPORT int nb_scenes_keep(nb_scenes *ctx)
+{
+    static const char fn[] = "nb_scenes_keep";
+    int rc = ctx_check(ctx, fn, kCallScenesUpload);
+    if (rc != NB_OK) return rc;
+    const size_t records = (size_t)ctx->scenes * ctx->n;
+    NB_HIP(ctx, ctx->pos_kept.reserve(records));   // allocated by the first keep
+    NB_HIP(ctx, ctx->vel_kept.reserve(records));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->pos_kept.p, ctx->pos.p, records * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->vel_kept.p, ctx->vel.p, records * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->steps_kept = ctx->steps;
+    ctx->kept = true;
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_rewind(nb_scenes *ctx)
+{
+    static const char fn[] = "nb_scenes_rewind";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    if (!ctx->kept) {
+        ctx->err = std::string(fn) + kCallKeep;
+        return NB_ERR_STATE;
+    }
+    const size_t records = (size_t)ctx->scenes * ctx->n;
+    NB_HIP(ctx, hipMemcpyAsync(ctx->pos.p, ctx->pos_kept.p, records * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->vel.p, ctx->vel_kept.p, records * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->steps = ctx->steps_kept;
     return NB_OK;
 }
 

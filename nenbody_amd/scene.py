@@ -445,6 +445,9 @@ def pack_policy(w1, b1, w2, b2) -> np.ndarray:
 SCORE_DTYPE = np.dtype([("near", np.uint64), ("spread", np.float32), ("speed2", np.float32), ("momentum2", np.float32),
                         ("goal2", np.float32), ("steps", np.uint32), ("nonfinite", np.uint32)])
 
+# struct nb_es_report (include/nenbody.h, section 14.6): what :meth:`SceneBatch.es_result` returns first
+ES_REPORT_DTYPE = np.dtype([("best_scene", np.uint32), ("best_fitness", np.float32), ("nan_count", np.uint32), ("generation", np.uint32)])
+
 
 class SceneBatch:
     """B independent scenes of n <= NB_SCENES_MAX_BODIES bodies, device-resident, stepped k times by ONE launch with one workgroup
@@ -611,6 +614,59 @@ class SceneBatch:
         :meth:`scores` when it ends."""
         upv, cpm = self._eye_setup(width, up, cp)
         self._check(self._lib.nb_scenes_step_policy_scored(self._ctx, int(k), upv.ctypes.data, cpm.ctypes.data, width))
+
+    def es_set(self, mean, features: int, hidden: int, sigma: float, step: float, coef, seed: int = 0,
+               accel_limit: float = float("inf")) -> None:
+        """The batch's search (nb_scenes_es_set): ``mean`` of policy_floats(features, hidden) floats is the
+        policy the population of at most 4 096 scenes is drawn around, ``sigma`` >= 0 the scale of the draw, ``step`` the update's step
+        (learning rate, 1/(B sigma) and the utilities' scale folded in), ``coef`` the six coefficients of the fitness over (near,
+        spread, speed2, momentum2, goal2, nonfinite), larger is better, ``seed`` 64 bits.  The generation starts at 0."""
+        m = np.ascontiguousarray(mean, np.float32)
+        if m.ndim != 1 or m.shape[0] != policy_floats(features, hidden) or m.shape[0] == 0:
+            raise ValueError("mean must have shape (policy_floats(features, hidden),)")
+        c = np.ascontiguousarray(coef, np.float32)
+        if c.shape != (6,):
+            raise ValueError("coef must have six components")
+        ep = _lib.NbEsParams(float(sigma), float(step), (ctypes.c_float * 6)(*c.tolist()), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._check(self._lib.nb_scenes_es_set(self._ctx, int(features), int(hidden), m.ctypes.data, float(accel_limit), ctypes.byref(ep)))
+        self._es_floats = int(m.shape[0])
+        self._policy_shape = (int(features), int(hidden))
+
+    def es_perturb(self) -> None:
+        """The batch's policies become the population of the current generation (nb_scenes_es_perturb): scene s gets
+        mean + sigma e(seed, generation, s), scenes 2q and 2q + 1 mirrored.  Asynchronous."""
+        self._check(self._lib.nb_scenes_es_perturb(self._ctx))
+
+    def es_update(self) -> None:
+        """The score records ranked, the mean moved along the rank-weighted sum of the draws and the generation incremented
+        (nb_scenes_es_update).  Asynchronous; needs :meth:`set_score`."""
+        self._check(self._lib.nb_scenes_es_update(self._ctx))
+
+    def es_mean(self) -> np.ndarray:
+        """The mean (nb_scenes_es_mean): policy_floats float32.  Waits for the stream."""
+        out = np.zeros(max(getattr(self, "_es_floats", 0), 1), np.float32)
+        self._check(self._lib.nb_scenes_es_mean(self._ctx, out.ctypes.data))
+        return out[:getattr(self, "_es_floats", 0)]
+
+    def es_result(self):
+        """What the last :meth:`es_update` left (nb_scenes_es_result): (report, a record of dtype :data:`ES_REPORT_DTYPE`; fitness
+        float32 (B,); rank uint32 (B,), 0 the worst).  Waits for the stream."""
+        report = np.zeros((), ES_REPORT_DTYPE)
+        fitness, rank = np.zeros(self.scenes, np.float32), np.zeros(self.scenes, np.uint32)
+        self._check(self._lib.nb_scenes_es_result(self._ctx, report.ctypes.data, fitness.ctypes.data, rank.ctypes.data))
+        return report, fitness, rank
+
+    @property
+    def es_generation(self) -> int:
+        return int(self._lib.nb_scenes_es_generation(self._ctx))
+
+    def keep(self) -> None:
+        """The current positions, velocities and step counter copied to buffers the batch keeps (nb_scenes_keep), on the device."""
+        self._check(self._lib.nb_scenes_keep(self._ctx))
+
+    def rewind(self) -> None:
+        """The kept state copied back (nb_scenes_rewind).  Asynchronous."""
+        self._check(self._lib.nb_scenes_rewind(self._ctx))
 
     def _download(self, what: int) -> np.ndarray:
         out = np.empty((self.scenes, self.n, 4, 4) if what == 2 else (self.scenes, self.n, 3), np.float32)
