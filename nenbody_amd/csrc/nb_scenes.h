@@ -31,23 +31,30 @@ hipError_t launch_scenes_boids(const BoidsArgs &c, float4 *pos, float4 *vel, uin
 // The seen boids step of a batch (nb_scenes_seen.inc): one workgroup per eye, the eye's row and its seen set
 // in LDS only.  A scene of at most kScenesSeenWaveBodies bodies takes one wave per eye, a larger one four; the bits are the same.
 constexpr uint32_t kScenesSeenWaveBodies = 128;
-// ONE step, out of place.  `c`: the constants of a set of n bodies as make_boids_args forms them (n_total = n, first = 0), with the
-// four record pointers set to the batch's scenes * n records.  cams, inst: the 4 / 4 float4 of every body of the batch as
-// launch_cameras / launch_instances leave them for those records.
-hipError_t launch_scenes_boids_seen(const BoidsArgs &c, uint32_t scenes, const float *cams, const float *inst, uint32_t width, hipStream_t s);
-// The seen sets that step folds over (S1-S3) for eyes [first_eye, first_eye + count) of the batch: seen_count, count words;
-// seen_ids, count x width words; either may be NULL.  cams and inst as above, indexed by the eye's number in the batch.
-hipError_t launch_scenes_seen(uint32_t n, uint32_t first_eye, uint32_t count, const float *cams, const float *inst, uint32_t width,
-                              uint32_t *seen_count, uint32_t *seen_ids, hipStream_t s);
+// The eyes a one-workgroup-per-eye scenes kernel walks, the head of its arguments (scenes_eye_begin, nb_scenes_seen.inc).
+struct ScenesEyes {
+    uint32_t n, first_eye, count, width;     // eyes [first_eye, first_eye + count) of the batch; eye b is body b % n of scene b / n
+    const float4 *__restrict__ cams;         // 4 / 4 float4 per body of the WHOLE batch, as launch_cameras / launch_instances leave them
+    const float4 *__restrict__ inst;
+};
+struct ScenesSeenArgs {                       // the launchers'; the kernel keeps a loose parameter list
+    ScenesEyes eye;
+    BoidsArgs c;                             // the step's: the constants of a set of n bodies as make_boids_args forms them (n_total = n,
+                                             // first = 0), the four record pointers set to the batch's scenes * n records
+    uint32_t *__restrict__ seen_count;       // the sets' (S1-S3): count words, and count x width words; either may be NULL
+    uint32_t *__restrict__ seen_ids;
+};
+// ONE step, out of place, for every eye the arguments name (the entries pass the whole batch).
+hipError_t launch_scenes_boids_seen(const ScenesSeenArgs &a, hipStream_t s);
+// The seen sets that step folds over, indexed from first_eye; `c` is not read.
+hipError_t launch_scenes_seen(const ScenesSeenArgs &a, hipStream_t s);
 
 // Gravity from located vision for a batch (nb_scenes_located.inc): one workgroup per eye, the eye's row, its
 // members' nearest depths and columns and the quotients in LDS only -- 8 width + 12 n + 256 bytes, at most 57 600.  The launch shape
 // follows kScenesSeenWaveBodies as above; the bits are the same.  The caller has checked the arguments (1 <= n <= kScenesMaxBodies,
 // 1 <= width <= NB_EYES_MAX_WIDTH, count >= 1, a constant that L2 inverts: L6).
 struct ScenesLocatedArgs {
-    uint32_t n, first_eye, count, width;     // eyes [first_eye, first_eye + count) of the batch; eye b is body b % n of scene b / n
-    const float4 *__restrict__ cams;         // 4 / 4 float4 per body of the WHOLE batch, as launch_cameras / launch_instances leave them
-    const float4 *__restrict__ inst;
+    ScenesEyes eye;
     const float4 *__restrict__ pos_in;       // the batch's records; the step reads both, the sets vel_in alone (the eye's direction)
     const float4 *__restrict__ vel_in;
     float ux, uy, uz;
@@ -76,9 +83,7 @@ constexpr uint32_t kPolicyMaxHidden = 64;     // NB_POLICY_MAX_HIDDEN: one lane 
 // the floats of one policy: w1[f H + j], b1[j], w2[k H + j] (k = 0, 1), b2[k]
 constexpr size_t policy_floats(uint32_t features, uint32_t hidden) { return (size_t)features * hidden + hidden + 2u * (size_t)hidden + 2u; }
 struct ScenesPolicyArgs {
-    uint32_t n, first_eye, count, width;     // eyes [first_eye, first_eye + count) of the batch; eye b is body b % n of scene b / n
-    const float4 *__restrict__ cams;         // 4 / 4 float4 per body of the WHOLE batch, as launch_cameras / launch_instances leave them
-    const float4 *__restrict__ inst;
+    ScenesEyes eye;
     uint32_t features, hidden;               // the policy shape (F, H)
     uint32_t stride;                         // floats from scene s's policy to scene s + 1's: policy_floats, or 0 where all share policy 0
     const float *__restrict__ weights;

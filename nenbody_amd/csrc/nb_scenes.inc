@@ -153,10 +153,18 @@ static hipError_t scenes_by_size(uint32_t n, F f)
     return f.template operator()<1024, true>();
 }
 
-// above 64 KiB of LDS a function's dynamic limit has to be raised first (as nb_eyes_msaa.inc's launcher does)
-static hipError_t scenes_lds_limit(const void *kernel, size_t lds)
+// The launch of a one-workgroup-per-scene kernel of LANES lanes: above 64 KiB of LDS the function's dynamic limit is raised first (as
+// nb_eyes_msaa.inc's launcher does); more scenes than kScenesMaxGrid are the kernel's grid-stride loop's
+template <int LANES, class K, class... A>
+static hipError_t launch_scenes_scene(K kernel, uint32_t scenes, size_t lds, hipStream_t s, A... args)
 {
-    return lds > 65536u ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+    if (lds > 65536u) {
+        const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const uint32_t grid = scenes < kScenesMaxGrid ? scenes : kScenesMaxGrid;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(LANES), lds, s, args...);
+    return hipGetLastError();
 }
 
 struct ScenesNbodyLaunch {
@@ -166,11 +174,7 @@ struct ScenesNbodyLaunch {
     hipError_t operator()() const
     {
         const size_t lds = (size_t)a.n * 2u * sizeof(float4) + 2u * (LANES / 64) * sizeof(uint32_t);   // 64 KiB + 128 B at n = 2 048
-        const hipError_t e = scenes_lds_limit((const void *)scenes_nbody_kernel<LANES, TWO>, lds);
-        if (e != hipSuccess) return e;
-        const uint32_t grid = a.scenes < kScenesMaxGrid ? a.scenes : kScenesMaxGrid;
-        hipLaunchKernelGGL((scenes_nbody_kernel<LANES, TWO>), dim3(grid), dim3(LANES), lds, s, a);
-        return hipGetLastError();
+        return launch_scenes_scene<LANES>(scenes_nbody_kernel<LANES, TWO>, a.scenes, lds, s, a);
     }
 };
 hipError_t launch_scenes_nbody(const ScenesNbodyArgs &a, hipStream_t s) { return scenes_by_size(a.n, ScenesNbodyLaunch{a, s}); }
@@ -184,11 +188,7 @@ struct ScenesBoidsLaunch {
     hipError_t operator()() const
     {
         const size_t lds = (size_t)c.n_total * 2u * (sizeof(float4) + sizeof(float2));   // 96 KiB at n = 2 048
-        const hipError_t e = scenes_lds_limit((const void *)scenes_boids_kernel<LANES, TWO>, lds);
-        if (e != hipSuccess) return e;
-        const uint32_t grid = scenes < kScenesMaxGrid ? scenes : kScenesMaxGrid;
-        hipLaunchKernelGGL((scenes_boids_kernel<LANES, TWO>), dim3(grid), dim3(LANES), lds, s, c, pos, vel, scenes, k);
-        return hipGetLastError();
+        return launch_scenes_scene<LANES>(scenes_boids_kernel<LANES, TWO>, scenes, lds, s, c, pos, vel, scenes, k);
     }
 };
 hipError_t launch_scenes_boids(const BoidsArgs &c, float4 *pos, float4 *vel, uint32_t scenes, uint32_t k, hipStream_t s)

@@ -1,15 +1,10 @@
-// nb_scenes_api.inc -- the C ABI of DESIGN.md section 14: scene batches.  The two stateless entries (nb_scenes_nbody_step_launch,
-// nb_scenes_boids_step_launch) step caller-owned records in place; the context nb_scenes owns a batch and a stream.  Section 14.1 adds
-// the boids step over what each body sees: nb_scenes_boids_seen_step_launch and nb_scenes_seen_launch, stateless, and the context's
-// nb_scenes_step_boids_seen and nb_scenes_eyes_seen.  Section 14.2 adds gravity from located vision in the same four shapes:
-// nb_scenes_nbody_located_step_launch, nb_scenes_located_launch, nb_scenes_step_nbody_located and nb_scenes_eyes_located.  Section 14.4
-// adds a neural policy over each eye row: nb_policy_floats, nb_scenes_policy_step_launch and nb_scenes_policy_observe_launch, stateless,
-// and the context's nb_scenes_set_policy, nb_scenes_step_policy and nb_scenes_eyes_policy.  Section 14.5 adds the score of every scene,
-// accumulated on the device: nb_scenes_score_launch, stateless, and the context's nb_scenes_set_score, nb_scenes_score,
-// nb_scenes_score_reset, nb_scenes_scores and nb_scenes_step_policy_scored.  Section 14.6 adds an evolution-strategies generation:
-// nb_scenes_es_perturb_launch and nb_scenes_es_update_launch, stateless, and the context's nb_scenes_es_set, nb_scenes_es_perturb,
-// nb_scenes_es_update, nb_scenes_es_mean, nb_scenes_es_result, nb_scenes_es_generation, nb_scenes_keep and nb_scenes_rewind.  Included by
-// nb_api.hip behind nb_vision_api.inc.  Every check runs before anything touches the device and has its own message naming the entry.
+// nb_scenes_api.inc -- the C ABI of DESIGN.md section 14: scene batches; include/nenbody.h and the nenbody_scenes_*.h behind it name
+// and document every entry.  Section 14: k gravity or boids steps of caller-owned records in place, stateless, and the context
+// nb_scenes, which owns a batch and a stream.  Section 14.1: the boids step over what each body sees, and the seen sets.  Section 14.2:
+// gravity from located vision, and the located sets.  Section 14.4: a neural policy over each eye row, and its observable.  Section
+// 14.5: the score of every scene, accumulated on the device.  Section 14.6: an evolution-strategies generation, with keep and rewind.
+// Sections 14.3 and 14.7: the helpers the entries share.  Included by nb_api.hip behind nb_vision_api.inc.  Every check runs before
+// anything touches the device and has its own message naming the entry.
 
 static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
 constexpr uint64_t kScenesMaxRecords = 1ull << 27;   // scenes * n
@@ -60,13 +55,24 @@ static int scenes_boids_params_check(const char *fn, const nb_boids_params &p, s
     return NB_OK;
 }
 
-// every pointer of the list 16-byte aligned; `subject` names them in the message
-static int scenes_aligned16_check(const char *fn, std::initializer_list<const void *> ptrs, const char *subject, std::string *err)
+// every pointer of the list there; `tail` is the message behind the entry's name
+static int scenes_null_check(const char *fn, std::initializer_list<const void *> ptrs, std::string *err, const char *tail = ": null argument")
+{
+    for (const void *p : ptrs)
+        if (!p) {
+            *err = std::string(fn) + tail;
+            return NB_ERR_INVALID;
+        }
+    return NB_OK;
+}
+
+// every pointer of the list aligned to `align` bytes, a power of two; `subject` names them in the message
+static int scenes_aligned_check(const char *fn, uint32_t align, std::initializer_list<const void *> ptrs, const char *subject, std::string *err)
 {
     uintptr_t bits = 0;
     for (const void *p : ptrs) bits |= (uintptr_t)p;
-    if (bits & 15u) {
-        *err = std::string(fn) + ": " + subject + " must be 16-byte aligned";
+    if (bits & (align - 1u)) {
+        *err = std::string(fn) + ": " + subject + " must be " + std::to_string(align) + "-byte aligned";
         return NB_ERR_INVALID;
     }
     return NB_OK;
@@ -75,7 +81,7 @@ static int scenes_aligned16_check(const char *fn, std::initializer_list<const vo
 // the records of a stateless entry: there, 16-byte aligned, not overlapping
 static int scenes_records_check(const char *fn, uint32_t scenes, uint32_t n, const void *pos, const void *vel, std::string *err)
 {
-    const int rc = scenes_aligned16_check(fn, {pos, vel}, "pos and vel", err);
+    const int rc = scenes_aligned_check(fn, 16, {pos, vel}, "pos and vel", err);
     if (rc != NB_OK) return rc;
     const size_t bytes = (size_t)scenes * n * sizeof(float4);
     if (ranges_overlap(pos, bytes, vel, bytes)) {
@@ -106,12 +112,9 @@ static int scenes_nbody_args(const nb_params &p, uint32_t scenes, uint32_t n, ui
 NB_EXPORT int nb_scenes_nbody_step_launch(const nb_params *params, uint32_t scenes, uint32_t n, uint32_t k, void *pos, void *vel, void *stream)
 {
     static const char fn[] = "nb_scenes_nbody_step_launch";
-    if (!pos || !vel) {
-        g_tls_error = std::string(fn) + ": pos and vel must be non-null";
-        return NB_ERR_INVALID;
-    }
     const nb_params p = params_or_default(params);
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    int rc = scenes_null_check(fn, {pos, vel}, &g_tls_error, ": pos and vel must be non-null");
+    if (rc == NB_OK) rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
     if (rc == NB_OK) rc = scenes_params_check(fn, p, &g_tls_error);
     if (rc == NB_OK) rc = scenes_records_check(fn, scenes, n, pos, vel, &g_tls_error);
     nbk::ScenesNbodyArgs a;
@@ -127,12 +130,9 @@ NB_EXPORT int nb_scenes_boids_step_launch(const nb_boids_params *params, uint32_
                                           void *stream)
 {
     static const char fn[] = "nb_scenes_boids_step_launch";
-    if (!pos || !vel) {
-        g_tls_error = std::string(fn) + ": pos and vel must be non-null";
-        return NB_ERR_INVALID;
-    }
     const nb_boids_params p = boids_params_or_default(params);
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    int rc = scenes_null_check(fn, {pos, vel}, &g_tls_error, ": pos and vel must be non-null");
+    if (rc == NB_OK) rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
     if (rc == NB_OK) rc = scenes_boids_params_check(fn, p, &g_tls_error);
     if (rc == NB_OK) rc = scenes_records_check(fn, scenes, n, pos, vel, &g_tls_error);
     nbk::BoidsArgs c;
@@ -184,7 +184,7 @@ static int scenes_step_buffers_check(const char *fn, size_t records, const void 
                                      const void *vel_in, const void *pos_out, const void *vel_out, const float *up_xyz, const float *cp16,
                                      std::string *err)
 {
-    const int rc = scenes_aligned16_check(fn, {cams_16, inst_16, pos_in, vel_in, pos_out, vel_out}, "cams_16, inst_16 and the four record buffers", err);
+    const int rc = scenes_aligned_check(fn, 16, {cams_16, inst_16, pos_in, vel_in, pos_out, vel_out}, "cams_16, inst_16 and the four record buffers", err);
     if (rc != NB_OK) return rc;
     const size_t bytes = records * sizeof(float4);
     const ByteRange in[6] = {{cams_16, bytes * 4u}, {inst_16, bytes * 4u},          {pos_in, bytes},
@@ -193,40 +193,41 @@ static int scenes_step_buffers_check(const char *fn, size_t records, const void 
     return outputs_check(fn, out, 0x3u, "", false, in, 6, kScenesSeenAlias, err);
 }
 
+// the eyes a per-eye kernel walks: [first_eye, first_eye + count) of a batch whose cameras and model matrices lie at cams and inst
+static nbk::ScenesEyes scenes_eyes(uint32_t n, uint32_t first_eye, uint32_t count, const void *cams, const void *inst, uint32_t width)
+{
+    return {n, first_eye, count, width, (const float4 *)cams, (const float4 *)inst};
+}
+
 NB_EXPORT int nb_scenes_boids_seen_step_launch(const nb_boids_params *params, uint32_t scenes, uint32_t n, const void *cams_16,
                                                const void *inst_16, uint32_t width, const void *pos_in, const void *vel_in, void *pos_out,
                                                void *vel_out, void *stream)
 {
     static const char fn[] = "nb_scenes_boids_seen_step_launch";
-    if (!cams_16 || !inst_16 || !pos_in || !vel_in || !pos_out || !vel_out) {
-        g_tls_error = std::string(fn) + ": cams_16, inst_16 and the four record buffers must be non-null";
-        return NB_ERR_INVALID;
-    }
     const nb_boids_params p = boids_params_or_default(params);
-    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    int rc = scenes_null_check(fn, {cams_16, inst_16, pos_in, vel_in, pos_out, vel_out}, &g_tls_error,
+                               ": cams_16, inst_16 and the four record buffers must be non-null");
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
     if (rc == NB_OK) rc = scenes_boids_params_check(fn, p, &g_tls_error);
     if (rc == NB_OK)
         rc = scenes_step_buffers_check(fn, (size_t)scenes * n, cams_16, inst_16, pos_in, vel_in, pos_out, vel_out, nullptr, nullptr, &g_tls_error);
-    nbk::BoidsArgs c;
+    nbk::ScenesSeenArgs a{};
     uint32_t tile = 0;
-    if (rc == NB_OK) rc = make_boids_args(p, n, 0, n, &c, &tile, &g_tls_error);
+    if (rc == NB_OK) rc = make_boids_args(p, n, 0, n, &a.c, &tile, &g_tls_error);
     if (rc == NB_OK) rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    c.pos_in = (const float4 *)pos_in, c.vel_in = (const float4 *)vel_in, c.pos_out = (float4 *)pos_out, c.vel_out = (float4 *)vel_out;
-    return launch_status(nbk::launch_scenes_boids_seen(c, scenes, (const float *)cams_16, (const float *)inst_16, width, (hipStream_t)stream),
-                         "nb: boids kernel launch failed (scene batch, seen form): ", &g_tls_error);
+    a.eye = scenes_eyes(n, 0u, scenes * n, cams_16, inst_16, width);
+    a.c.pos_in = (const float4 *)pos_in, a.c.vel_in = (const float4 *)vel_in, a.c.pos_out = (float4 *)pos_out, a.c.vel_out = (float4 *)vel_out;
+    return launch_status(nbk::launch_scenes_boids_seen(a, (hipStream_t)stream), "nb: boids kernel launch failed (scene batch, seen form): ", &g_tls_error);
 }
 
 NB_EXPORT int nb_scenes_seen_launch(uint32_t scenes, uint32_t n, uint32_t first_eye, uint32_t count, const void *cams_16, const void *inst_16,
                                     uint32_t width, void *seen_count, void *seen_ids, void *stream)
 {
     static const char fn[] = "nb_scenes_seen_launch";
-    if (!cams_16 || !inst_16) {
-        g_tls_error = std::string(fn) + ": cams_16 and inst_16 must be non-null";
-        return NB_ERR_INVALID;
-    }
-    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
-    if (rc == NB_OK) rc = scenes_aligned16_check(fn, {cams_16, inst_16}, "cams_16 and inst_16", &g_tls_error);
+    int rc = scenes_null_check(fn, {cams_16, inst_16}, &g_tls_error, ": cams_16 and inst_16 must be non-null");
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 16, {cams_16, inst_16}, "cams_16 and inst_16", &g_tls_error);
     if (rc == NB_OK) rc = scenes_eye_range_check(fn, scenes, n, first_eye, count, &g_tls_error);
     if (rc != NB_OK) return rc;
     const size_t matrices = (size_t)scenes * n * 16 * sizeof(float);
@@ -237,21 +238,20 @@ NB_EXPORT int nb_scenes_seen_launch(uint32_t scenes, uint32_t n, uint32_t first_
     if (count == 0) return NB_OK;
     rc = device_for_launch(inst_16, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    return launch_status(nbk::launch_scenes_seen(n, first_eye, count, (const float *)cams_16, (const float *)inst_16, width,
-                                                 (uint32_t *)seen_count, (uint32_t *)seen_ids, (hipStream_t)stream),
-                         "nb: seen kernel launch failed (scene batch): ", &g_tls_error);
+    nbk::ScenesSeenArgs a{};
+    a.eye = scenes_eyes(n, first_eye, count, cams_16, inst_16, width);
+    a.seen_count = (uint32_t *)seen_count, a.seen_ids = (uint32_t *)seen_ids;
+    return launch_status(nbk::launch_scenes_seen(a, (hipStream_t)stream), "nb: seen kernel launch failed (scene batch): ", &g_tls_error);
 }
 
 // ---- gravity from located vision (DESIGN.md section 14.2): the stateless entries ----------------------------------------------------------
 static const char kNoScenesLocatedOutputs[] = ": seen_count, seen_ids, seen_depth, seen_col and seen_rel are all NULL";
 
 // the kernel's arguments but for its buffers: the eye set-up and the law's constants
-static nbk::ScenesLocatedArgs scenes_located_args(const nb_params &p, uint32_t n, uint32_t first_eye, uint32_t count, const void *cams,
-                                                  const void *inst, const float *up_xyz, const float *cp16, uint32_t width)
+static nbk::ScenesLocatedArgs scenes_located_args(const nb_params &p, const nbk::ScenesEyes &eye, const float *up_xyz, const float *cp16)
 {
     nbk::ScenesLocatedArgs a{};
-    a.n = n, a.first_eye = first_eye, a.count = count, a.width = width;
-    a.cams = (const float4 *)cams, a.inst = (const float4 *)inst;
+    a.eye = eye;
     a.ux = up_xyz[0], a.uy = up_xyz[1], a.uz = up_xyz[2];
     a.cp0 = cp16[0], a.cp10 = cp16[10], a.cp14 = cp16[14];
     a.dt = p.dt, a.G = p.G, a.bias = p.bias;
@@ -263,17 +263,14 @@ NB_EXPORT int nb_scenes_nbody_located_step_launch(const nb_params *params, uint3
                                                   const void *pos_in, const void *vel_in, void *pos_out, void *vel_out, void *stream)
 {
     static const char fn[] = "nb_scenes_nbody_located_step_launch";
-    if (!cams_16 || !inst_16 || !up_xyz || !cp16 || !pos_in || !vel_in || !pos_out || !vel_out) {
-        g_tls_error = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
     const nb_params p = params_or_default(params);
-    int rc = scenes_vision_check(fn, scenes, n, width, cp16, &g_tls_error);
+    int rc = scenes_null_check(fn, {cams_16, inst_16, up_xyz, cp16, pos_in, vel_in, pos_out, vel_out}, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, cp16, &g_tls_error);
     const size_t records = (size_t)scenes * n;
     if (rc == NB_OK) rc = scenes_step_buffers_check(fn, records, cams_16, inst_16, pos_in, vel_in, pos_out, vel_out, up_xyz, cp16, &g_tls_error);
     if (rc == NB_OK) rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    nbk::ScenesLocatedArgs a = scenes_located_args(p, n, 0u, (uint32_t)records, cams_16, inst_16, up_xyz, cp16, width);
+    nbk::ScenesLocatedArgs a = scenes_located_args(p, scenes_eyes(n, 0u, (uint32_t)records, cams_16, inst_16, width), up_xyz, cp16);
     a.pos_in = (const float4 *)pos_in, a.vel_in = (const float4 *)vel_in, a.pos_out = (float4 *)pos_out, a.vel_out = (float4 *)vel_out;
     return launch_status(nbk::launch_scenes_nbody_located(a, (hipStream_t)stream),
                          "nb: gravity kernel launch failed (scene batch, located form): ", &g_tls_error);
@@ -284,12 +281,9 @@ NB_EXPORT int nb_scenes_located_launch(uint32_t scenes, uint32_t n, uint32_t fir
                                        void *seen_count, void *seen_ids, void *seen_depth, void *seen_col, void *seen_rel, void *stream)
 {
     static const char fn[] = "nb_scenes_located_launch";
-    if (!cams_16 || !inst_16 || !vel_in || !up_xyz || !cp16) {
-        g_tls_error = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    int rc = scenes_vision_check(fn, scenes, n, width, cp16, &g_tls_error);
-    if (rc == NB_OK) rc = scenes_aligned16_check(fn, {cams_16, inst_16, vel_in, seen_rel}, "cams_16, inst_16, vel_in and seen_rel", &g_tls_error);
+    int rc = scenes_null_check(fn, {cams_16, inst_16, vel_in, up_xyz, cp16}, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, cp16, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 16, {cams_16, inst_16, vel_in, seen_rel}, "cams_16, inst_16, vel_in and seen_rel", &g_tls_error);
     if (rc == NB_OK) rc = scenes_eye_range_check(fn, scenes, n, first_eye, count, &g_tls_error);
     if (rc != NB_OK) return rc;
     const size_t records = (size_t)scenes * n, cells = (size_t)count * width;
@@ -302,7 +296,7 @@ NB_EXPORT int nb_scenes_located_launch(uint32_t scenes, uint32_t n, uint32_t fir
     if (count == 0) return NB_OK;
     rc = device_for_launch(inst_16, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    nbk::ScenesLocatedArgs a = scenes_located_args(nb_params{}, n, first_eye, count, cams_16, inst_16, up_xyz, cp16, width);
+    nbk::ScenesLocatedArgs a = scenes_located_args(nb_params{}, scenes_eyes(n, first_eye, count, cams_16, inst_16, width), up_xyz, cp16);
     a.vel_in = (const float4 *)vel_in;
     a.seen_count = (uint32_t *)seen_count, a.seen_ids = (uint32_t *)seen_ids, a.seen_depth = (uint32_t *)seen_depth;
     a.seen_col = (uint32_t *)seen_col, a.seen_rel = (float4 *)seen_rel;
@@ -310,6 +304,11 @@ NB_EXPORT int nb_scenes_located_launch(uint32_t scenes, uint32_t n, uint32_t fir
 }
 
 // ---- the context --------------------------------------------------------------------------------------------------------------------------
+struct ScenesPolicyShape {                   // a policy's (F, H) and the limit of its outputs
+    uint32_t features = 0, hidden = 0;
+    float accel_limit = 0.f;
+};
+
 struct nb_scenes {
     uint32_t scenes = 0, n = 0;
     nb_params p{};
@@ -323,8 +322,8 @@ struct nb_scenes {
     DeviceBuffer<uint32_t> seen_depth, seen_col;   // nb_scenes_eyes_located's further lists, likewise: depth bits and columns
     DeviceBuffer<uint32_t> seen_rel;               // and its located points, four words a slot
     DeviceBuffer<float> policy;                    // nb_scenes_set_policy's weights: policies * nb_policy_floats floats
-    uint32_t features = 0, hidden = 0, policies = 0;   // their shape; policies = 0: no policy set
-    float accel_limit = 0.f;
+    ScenesPolicyShape pol;                         // their shape
+    uint32_t policies = 0;                         // 0: no policy set
     DeviceBuffer<uint32_t> pol_feat, pol_act;      // nb_scenes_eyes_policy's features and outputs for one range of scenes, grown on demand
     DeviceBuffer<nbk::SceneScore> score;           // nb_scenes_set_score's records, one a scene
     nb_score_params sp{};                          // its parameters
@@ -333,9 +332,9 @@ struct nb_scenes {
     DeviceBuffer<uint32_t> es_rank;                // what the last nb_scenes_es_update left: scenes ranks,
     DeviceBuffer<float> es_fitness;                // scenes fitnesses
     DeviceBuffer<uint32_t> es_report;              // and the four words of nb_es_report
-    nb_es_params ep{};                             // its parameters; the shape and the limit of the population's policies
-    uint32_t es_features = 0, es_hidden = 0, es_generation = 0;
-    float es_limit = 0.f;
+    nb_es_params ep{};                             // its parameters; the shape of the population's policies
+    ScenesPolicyShape es_pol;
+    uint32_t es_generation = 0;
     bool es_set = false, es_updated = false;
     DeviceBuffer<float4> pos_kept, vel_kept;       // nb_scenes_keep's copy of pos and vel
     uint64_t steps_kept = 0;                       // and of the step counter
@@ -369,13 +368,11 @@ static int scenes_create_impl(nb_scenes *c)
 NB_EXPORT int nb_scenes_create(uint32_t scenes, uint32_t n, const nb_params *params, nb_scenes **out)
 {
     static const char fn[] = "nb_scenes_create";
-    if (!out) {
-        g_tls_error = std::string(fn) + ": out is null";
-        return NB_ERR_INVALID;
-    }
+    int rc = scenes_null_check(fn, {out}, &g_tls_error, ": out is null");
+    if (rc != NB_OK) return rc;
     *out = nullptr;
     const nb_params p = params_or_default(params);
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
     if (rc == NB_OK) rc = scenes_params_check(fn, p, &g_tls_error);
     if (rc == NB_OK) rc = check_device(&g_tls_error);
     if (rc != NB_OK) return rc;
@@ -398,11 +395,8 @@ NB_EXPORT int nb_scenes_create(uint32_t scenes, uint32_t n, const nb_params *par
 NB_EXPORT int nb_scenes_upload(nb_scenes *ctx, const float *pos_xyz, const float *vel_xyz)
 {
     int rc = ctx_check(ctx, "nb_scenes_upload");
+    if (rc == NB_OK) rc = scenes_null_check("nb_scenes_upload", {pos_xyz, vel_xyz}, &ctx->err, ": null array");
     if (rc != NB_OK) return rc;
-    if (!pos_xyz || !vel_xyz) {
-        ctx->err = "nb_scenes_upload: null array";
-        return NB_ERR_INVALID;
-    }
     const size_t records = (size_t)ctx->scenes * ctx->n, bytes = records * 3 * sizeof(float);
     NB_HIP(ctx, hipMemcpyAsync(ctx->stage.p, pos_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
     NB_HIP(ctx, hipMemcpyAsync(ctx->stage.p + 3 * records, vel_xyz, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -449,11 +443,34 @@ NB_EXPORT int nb_scenes_step_boids(nb_scenes *ctx, uint32_t k, const nb_boids_pa
 // the eye set-up of the context's two seen entries: there, and the width
 static int scenes_eye_setup_check(nb_scenes *ctx, const char *fn, const float *up_xyz, const float *cp16, uint32_t width)
 {
-    if (!up_xyz || !cp16) {
-        ctx->err = std::string(fn) + ": null argument";
+    const int rc = scenes_null_check(fn, {up_xyz, cp16}, &ctx->err);
+    return rc != NB_OK ? rc : scenes_width_check(fn, width, &ctx->err);
+}
+
+// a check of the context's state: `have`, or NB_ERR_STATE with `tail` behind the entry's name
+static int scenes_state_check(nb_scenes *ctx, const char *fn, bool have, const char *tail)
+{
+    if (!have) {
+        ctx->err = std::string(fn) + tail;
+        return NB_ERR_STATE;
+    }
+    return NB_OK;
+}
+
+// scenes [first_scene, first_scene + scene_count) lie in the context's batch
+static int scenes_range_check(nb_scenes *ctx, const char *fn, uint32_t first_scene, uint32_t scene_count)
+{
+    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
+        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
         return NB_ERR_INVALID;
     }
-    return scenes_width_check(fn, width, &ctx->err);
+    return NB_OK;
+}
+
+// eyes [first_eye, first_eye + count) of the context's batch, as scenes_stage_eyes leaves their cameras and matrices
+static nbk::ScenesEyes scenes_eyes(const nb_scenes *ctx, uint32_t first_eye, uint32_t count, uint32_t width)
+{
+    return scenes_eyes(ctx->n, first_eye, count, ctx->cams.p, ctx->inst.p, width);
 }
 
 // the model matrices and the eye cameras of every body of the current state, on the context's stream
@@ -503,14 +520,12 @@ template <int N, typename Launch>
 static int scenes_eyes_download(nb_scenes *ctx, const char *fn, uint32_t first_scene, uint32_t scene_count, const float *up_xyz,
                                 const float *cp16, const ScenesEyesOutput (&out)[N], const char *none_msg, Launch launch)
 {
-    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
-        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
-        return NB_ERR_INVALID;
-    }
+    int rc = scenes_range_check(ctx, fn, first_scene, scene_count);
+    if (rc != NB_OK) return rc;
     const ByteRange in[2] = {{up_xyz, 3 * sizeof(float)}, {cp16, 16 * sizeof(float)}};
     ByteRange user[N];
     for (int r = 0; r < N; ++r) user[r] = {out[r].host, (size_t)scene_count * ctx->n * out[r].words * 4u};
-    int rc = outputs_check(fn, user, (1u << N) - 1u, none_msg, false, in, 2, kScenesSeenAlias, &ctx->err);
+    rc = outputs_check(fn, user, (1u << N) - 1u, none_msg, false, in, 2, kScenesSeenAlias, &ctx->err);
     if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
     if (rc != NB_OK) return rc;
     if (scene_count == 0) return NB_OK;
@@ -546,13 +561,14 @@ NB_EXPORT int nb_scenes_step_boids_seen(nb_scenes *ctx, uint32_t k, const nb_boi
     rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
     if (rc == NB_OK) rc = scenes_boids_params_check(fn, p, &ctx->err);
     if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
-    nbk::BoidsArgs c;
+    nbk::ScenesSeenArgs a{};
     uint32_t tile = 0;
-    if (rc == NB_OK) rc = make_boids_args(p, ctx->n, 0, ctx->n, &c, &tile, &ctx->err);
+    if (rc == NB_OK) rc = make_boids_args(p, ctx->n, 0, ctx->n, &a.c, &tile, &ctx->err);
     if (rc != NB_OK) return rc;
-    return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [&c, width](nb_scenes *ctx) -> int {
-        c.pos_in = ctx->pos.p, c.vel_in = ctx->vel.p, c.pos_out = ctx->pos_alt.p, c.vel_out = ctx->vel_alt.p;
-        NB_HIP(ctx, nbk::launch_scenes_boids_seen(c, ctx->scenes, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width, ctx->stream));
+    return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [&a, width](nb_scenes *ctx) -> int {
+        a.eye = scenes_eyes(ctx, 0u, ctx->scenes * ctx->n, width);
+        a.c.pos_in = ctx->pos.p, a.c.vel_in = ctx->vel.p, a.c.pos_out = ctx->pos_alt.p, a.c.vel_out = ctx->vel_alt.p;
+        NB_HIP(ctx, nbk::launch_scenes_boids_seen(a, ctx->stream));
         return NB_OK;
     });
 }
@@ -567,8 +583,10 @@ NB_EXPORT int nb_scenes_eyes_seen(nb_scenes *ctx, uint32_t first_scene, uint32_t
     if (rc != NB_OK) return rc;
     const ScenesEyesOutput lists[2] = {{seen_count, &ctx->seen_count, 1}, {seen_ids, &ctx->seen_ids, width}};
     const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
-        NB_HIP(ctx, nbk::launch_scenes_seen(ctx->n, first_eye, cnt, (const float *)ctx->cams.p, (const float *)ctx->inst.p, width,
-                                            ctx->seen_count.p, seen_ids ? ctx->seen_ids.p : nullptr, ctx->stream));
+        nbk::ScenesSeenArgs a{};
+        a.eye = scenes_eyes(ctx, first_eye, cnt, width);
+        a.seen_count = ctx->seen_count.p, a.seen_ids = seen_ids ? ctx->seen_ids.p : nullptr;
+        NB_HIP(ctx, nbk::launch_scenes_seen(a, ctx->stream));
         return NB_OK;
     };
     return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, lists, ": seen_count and seen_ids are both NULL", launch);
@@ -585,8 +603,7 @@ NB_EXPORT int nb_scenes_step_nbody_located(nb_scenes *ctx, uint32_t k, const flo
     if (rc == NB_OK) rc = ctx_check(ctx, fn, kCallScenesUpload);
     if (rc != NB_OK) return rc;
     return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [=](nb_scenes *ctx) -> int {
-        nbk::ScenesLocatedArgs a =
-            scenes_located_args(ctx->p, ctx->n, 0u, ctx->scenes * ctx->n, ctx->cams.p, ctx->inst.p, up_xyz, cp16, width);
+        nbk::ScenesLocatedArgs a = scenes_located_args(ctx->p, scenes_eyes(ctx, 0u, ctx->scenes * ctx->n, width), up_xyz, cp16);
         a.pos_in = ctx->pos.p, a.vel_in = ctx->vel.p, a.pos_out = ctx->pos_alt.p, a.vel_out = ctx->vel_alt.p;
         NB_HIP(ctx, nbk::launch_scenes_nbody_located(a, ctx->stream));
         return NB_OK;
@@ -607,7 +624,7 @@ NB_EXPORT int nb_scenes_eyes_located(nb_scenes *ctx, uint32_t first_scene, uint3
                                        {seen_depth, &ctx->seen_depth, width}, {seen_col, &ctx->seen_col, width},
                                        {seen_rel, &ctx->seen_rel, (size_t)width * 4u}};   // 28 width + 4 bytes an eye with all five
     const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
-        nbk::ScenesLocatedArgs a = scenes_located_args(ctx->p, ctx->n, first_eye, cnt, ctx->cams.p, ctx->inst.p, up_xyz, cp16, width);
+        nbk::ScenesLocatedArgs a = scenes_located_args(ctx->p, scenes_eyes(ctx, first_eye, cnt, width), up_xyz, cp16);
         a.vel_in = ctx->vel.p;
         a.seen_count = ctx->seen_count.p, a.seen_ids = seen_ids ? ctx->seen_ids.p : nullptr;
         a.seen_depth = seen_depth ? ctx->seen_depth.p : nullptr, a.seen_col = seen_col ? ctx->seen_col.p : nullptr;
@@ -657,26 +674,14 @@ static int policy_check(const char *fn, uint32_t features, uint32_t hidden, uint
     return NB_OK;
 }
 
-static int policy_weights_check(const char *fn, const void *weights, std::string *err)
-{
-    if ((uintptr_t)weights & 3u) {
-        *err = std::string(fn) + ": weights must be 4-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    return NB_OK;
-}
-
 // the kernel's arguments but for its buffers: the eye set-up and the policies
-static nbk::ScenesPolicyArgs scenes_policy_args(uint32_t n, uint32_t first_eye, uint32_t count, const void *cams, const void *inst,
-                                                uint32_t width, uint32_t features, uint32_t hidden, uint32_t policies, const void *weights,
-                                                float accel_limit)
+static nbk::ScenesPolicyArgs scenes_policy_args(const nbk::ScenesEyes &eye, const ScenesPolicyShape &shape, uint32_t policies, const void *weights)
 {
     nbk::ScenesPolicyArgs a{};
-    a.n = n, a.first_eye = first_eye, a.count = count, a.width = width;
-    a.cams = (const float4 *)cams, a.inst = (const float4 *)inst;
-    a.features = features, a.hidden = hidden;
-    a.stride = policies == 1 ? 0u : (uint32_t)nbk::policy_floats(features, hidden);
-    a.weights = (const float *)weights, a.limit = accel_limit;
+    a.eye = eye;
+    a.features = shape.features, a.hidden = shape.hidden;
+    a.stride = policies == 1 ? 0u : (uint32_t)nbk::policy_floats(shape.features, shape.hidden);
+    a.weights = (const float *)weights, a.limit = shape.accel_limit;
     return a;
 }
 
@@ -686,15 +691,12 @@ NB_EXPORT int nb_scenes_policy_step_launch(const nb_params *params, uint32_t sce
                                            void *vel_out, void *stream)
 {
     static const char fn[] = "nb_scenes_policy_step_launch";
-    if (!cams_16 || !inst_16 || !up_xyz || !weights || !pos_in || !vel_in || !pos_out || !vel_out) {
-        g_tls_error = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
     const nb_params p = params_or_default(params);
-    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    int rc = scenes_null_check(fn, {cams_16, inst_16, up_xyz, weights, pos_in, vel_in, pos_out, vel_out}, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
     if (rc == NB_OK) rc = policy_check(fn, features, hidden, width, policies, scenes, accel_limit, &g_tls_error);
     if (rc == NB_OK) rc = scenes_params_check(fn, p, &g_tls_error);
-    if (rc == NB_OK) rc = policy_weights_check(fn, weights, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {weights}, "weights", &g_tls_error);
     const size_t records = (size_t)scenes * n;
     if (rc == NB_OK) rc = scenes_step_buffers_check(fn, records, cams_16, inst_16, pos_in, vel_in, pos_out, vel_out, up_xyz, nullptr, &g_tls_error);
     if (rc != NB_OK) return rc;
@@ -705,7 +707,8 @@ NB_EXPORT int nb_scenes_policy_step_launch(const nb_params *params, uint32_t sce
     }
     rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    nbk::ScenesPolicyArgs a = scenes_policy_args(n, 0u, (uint32_t)records, cams_16, inst_16, width, features, hidden, policies, weights, accel_limit);
+    nbk::ScenesPolicyArgs a =
+        scenes_policy_args(scenes_eyes(n, 0u, (uint32_t)records, cams_16, inst_16, width), {features, hidden, accel_limit}, policies, weights);
     a.pos_in = (const float4 *)pos_in, a.vel_in = (const float4 *)vel_in, a.pos_out = (float4 *)pos_out, a.vel_out = (float4 *)vel_out;
     a.ux = up_xyz[0], a.uy = up_xyz[1], a.uz = up_xyz[2], a.dt = p.dt;
     return launch_status(nbk::launch_scenes_policy(a, (hipStream_t)stream), "nb: policy kernel launch failed (scene batch): ", &g_tls_error);
@@ -716,14 +719,11 @@ NB_EXPORT int nb_scenes_policy_observe_launch(uint32_t scenes, uint32_t n, uint3
                                               const void *weights, float accel_limit, void *feat_out, void *act_out, void *stream)
 {
     static const char fn[] = "nb_scenes_policy_observe_launch";
-    if (!cams_16 || !inst_16 || !weights) {
-        g_tls_error = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    int rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    int rc = scenes_null_check(fn, {cams_16, inst_16, weights}, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
     if (rc == NB_OK) rc = policy_check(fn, features, hidden, width, policies, scenes, accel_limit, &g_tls_error);
-    if (rc == NB_OK) rc = policy_weights_check(fn, weights, &g_tls_error);
-    if (rc == NB_OK) rc = scenes_aligned16_check(fn, {cams_16, inst_16}, "cams_16 and inst_16", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {weights}, "weights", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 16, {cams_16, inst_16}, "cams_16 and inst_16", &g_tls_error);
     if (rc == NB_OK) rc = scenes_eye_range_check(fn, scenes, n, first_eye, count, &g_tls_error);
     if (rc != NB_OK) return rc;
     const size_t matrices = (size_t)scenes * n * 16 * sizeof(float);
@@ -734,7 +734,8 @@ NB_EXPORT int nb_scenes_policy_observe_launch(uint32_t scenes, uint32_t n, uint3
     if (count == 0) return NB_OK;
     rc = device_for_launch(inst_16, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    nbk::ScenesPolicyArgs a = scenes_policy_args(n, first_eye, count, cams_16, inst_16, width, features, hidden, policies, weights, accel_limit);
+    nbk::ScenesPolicyArgs a =
+        scenes_policy_args(scenes_eyes(n, first_eye, count, cams_16, inst_16, width), {features, hidden, accel_limit}, policies, weights);
     a.feat_out = (uint32_t *)feat_out, a.act_out = (uint32_t *)act_out;
     return launch_status(nbk::launch_scenes_policy_observe(a, (hipStream_t)stream), "nb: policy kernel launch failed (scene batch, observe form): ",
                          &g_tls_error);
@@ -745,12 +746,8 @@ NB_EXPORT int nb_scenes_set_policy(nb_scenes *ctx, uint32_t features, uint32_t h
 {
     static const char fn[] = "nb_scenes_set_policy";
     int rc = ctx_check(ctx, fn);
-    if (rc != NB_OK) return rc;
-    if (!weights_host) {
-        ctx->err = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    rc = policy_check(fn, features, hidden, 0u, policies, ctx->scenes, accel_limit, &ctx->err);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {weights_host}, &ctx->err);
+    if (rc == NB_OK) rc = policy_check(fn, features, hidden, 0u, policies, ctx->scenes, accel_limit, &ctx->err);
     if (rc != NB_OK) return rc;
     const size_t floats = (size_t)policies * nbk::policy_floats(features, hidden);
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step in flight may still read the policies in place
@@ -758,18 +755,15 @@ NB_EXPORT int nb_scenes_set_policy(nb_scenes *ctx, uint32_t features, uint32_t h
     NB_HIP(ctx, ctx->policy.reserve(floats));
     NB_HIP(ctx, hipMemcpyAsync(ctx->policy.p, weights_host, floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
-    ctx->features = features, ctx->hidden = hidden, ctx->policies = policies, ctx->accel_limit = accel_limit;
+    ctx->pol = {features, hidden, accel_limit}, ctx->policies = policies;
     return NB_OK;
 }
 
 // what the context's two policy entries check behind their eye set-up: a policy is there and its features divide the width
 static int scenes_policy_set_check(nb_scenes *ctx, const char *fn, uint32_t width)
 {
-    if (ctx->policies == 0) {
-        ctx->err = std::string(fn) + kCallSetPolicy;
-        return NB_ERR_STATE;
-    }
-    return policy_check(fn, ctx->features, ctx->hidden, width, ctx->policies, ctx->scenes, ctx->accel_limit, &ctx->err);
+    const int rc = scenes_state_check(ctx, fn, ctx->policies != 0, kCallSetPolicy);
+    return rc != NB_OK ? rc : policy_check(fn, ctx->pol.features, ctx->pol.hidden, width, ctx->policies, ctx->scenes, ctx->pol.accel_limit, &ctx->err);
 }
 
 // what nb_scenes_step_policy checks behind the context: the eye set-up, a state, a policy
@@ -785,8 +779,7 @@ static int scenes_step_policy_check(nb_scenes *ctx, const char *fn, const float 
 static int scenes_policy_steps(nb_scenes *ctx, const char *fn, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
 {
     return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [=](nb_scenes *ctx) -> int {
-        nbk::ScenesPolicyArgs a = scenes_policy_args(ctx->n, 0u, ctx->scenes * ctx->n, ctx->cams.p, ctx->inst.p, width, ctx->features,
-                                                     ctx->hidden, ctx->policies, ctx->policy.p, ctx->accel_limit);
+        nbk::ScenesPolicyArgs a = scenes_policy_args(scenes_eyes(ctx, 0u, ctx->scenes * ctx->n, width), ctx->pol, ctx->policies, ctx->policy.p);
         a.pos_in = ctx->pos.p, a.vel_in = ctx->vel.p, a.pos_out = ctx->pos_alt.p, a.vel_out = ctx->vel_alt.p;
         a.ux = up_xyz[0], a.uy = up_xyz[1], a.uz = up_xyz[2], a.dt = ctx->p.dt;
         NB_HIP(ctx, nbk::launch_scenes_policy(a, ctx->stream));
@@ -813,10 +806,9 @@ NB_EXPORT int nb_scenes_eyes_policy(nb_scenes *ctx, uint32_t first_scene, uint32
     rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
     if (rc == NB_OK) rc = scenes_policy_set_check(ctx, fn, width);
     if (rc != NB_OK) return rc;
-    const ScenesEyesOutput rows[2] = {{feat, &ctx->pol_feat, ctx->features}, {act, &ctx->pol_act, 2}};
+    const ScenesEyesOutput rows[2] = {{feat, &ctx->pol_feat, ctx->pol.features}, {act, &ctx->pol_act, 2}};
     const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
-        nbk::ScenesPolicyArgs a = scenes_policy_args(ctx->n, first_eye, cnt, ctx->cams.p, ctx->inst.p, width, ctx->features, ctx->hidden,
-                                                     ctx->policies, ctx->policy.p, ctx->accel_limit);
+        nbk::ScenesPolicyArgs a = scenes_policy_args(scenes_eyes(ctx, first_eye, cnt, width), ctx->pol, ctx->policies, ctx->policy.p);
         a.feat_out = feat ? ctx->pol_feat.p : nullptr, a.act_out = act ? ctx->pol_act.p : nullptr;
         NB_HIP(ctx, nbk::launch_scenes_policy_observe(a, ctx->stream));
         return NB_OK;
@@ -858,18 +850,12 @@ NB_EXPORT int nb_scenes_score_launch(const nb_score_params *sp, uint32_t scenes,
                                      void *stream)
 {
     static const char fn[] = "nb_scenes_score_launch";
-    if (!sp || !pos || !vel || !score) {
-        g_tls_error = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    int rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
+    int rc = scenes_null_check(fn, {sp, pos, vel, score}, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_shape_check(fn, scenes, n, &g_tls_error);
     if (rc == NB_OK) rc = score_params_check(fn, *sp, &g_tls_error);
     if (rc == NB_OK) rc = scenes_records_check(fn, scenes, n, pos, vel, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 8, {score}, "score", &g_tls_error);
     if (rc != NB_OK) return rc;
-    if ((uintptr_t)score & 7u) {
-        g_tls_error = std::string(fn) + ": score must be 8-byte aligned";
-        return NB_ERR_INVALID;
-    }
     const size_t bytes = (size_t)scenes * n * sizeof(float4), sbytes = (size_t)scenes * sizeof(nb_scene_score);
     if (ranges_overlap(score, sbytes, pos, bytes) || ranges_overlap(score, sbytes, vel, bytes)) {
         g_tls_error = std::string(fn) + ": score must not overlap pos or vel";
@@ -885,12 +871,8 @@ NB_EXPORT int nb_scenes_set_score(nb_scenes *ctx, const nb_score_params *sp)
 {
     static const char fn[] = "nb_scenes_set_score";
     int rc = ctx_check(ctx, fn);
-    if (rc != NB_OK) return rc;
-    if (!sp) {
-        ctx->err = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    rc = score_params_check(fn, *sp, &ctx->err);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {sp}, &ctx->err);
+    if (rc == NB_OK) rc = score_params_check(fn, *sp, &ctx->err);
     if (rc != NB_OK) return rc;
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a score in flight runs under the parameters it was issued with
     ctx->score_set = false;
@@ -902,14 +884,7 @@ NB_EXPORT int nb_scenes_set_score(nb_scenes *ctx, const nb_score_params *sp)
 }
 
 // the context holds a score
-static int scenes_score_set_check(nb_scenes *ctx, const char *fn)
-{
-    if (!ctx->score_set) {
-        ctx->err = std::string(fn) + kCallSetScore;
-        return NB_ERR_STATE;
-    }
-    return NB_OK;
-}
+static int scenes_score_set_check(nb_scenes *ctx, const char *fn) { return scenes_state_check(ctx, fn, ctx->score_set, kCallSetScore); }
 
 // the current snapshot into the context's records, the checks done
 static int scenes_score_now(nb_scenes *ctx)
@@ -942,16 +917,9 @@ NB_EXPORT int nb_scenes_scores(nb_scenes *ctx, uint32_t first_scene, uint32_t sc
 {
     static const char fn[] = "nb_scenes_scores";
     int rc = ctx_check(ctx, fn);
-    if (rc != NB_OK) return rc;
-    if (!out_host) {
-        ctx->err = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    if ((uint64_t)first_scene + scene_count > ctx->scenes) {
-        ctx->err = std::string(fn) + ": scenes [first_scene, first_scene + scene_count) exceed the batch";
-        return NB_ERR_INVALID;
-    }
-    rc = scenes_score_set_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {out_host}, &ctx->err);
+    if (rc == NB_OK) rc = scenes_range_check(ctx, fn, first_scene, scene_count);
+    if (rc == NB_OK) rc = scenes_score_set_check(ctx, fn);
     if (rc != NB_OK) return rc;
     if (scene_count == 0) return NB_OK;
     NB_HIP(ctx, hipMemcpyAsync(out_host, ctx->score.p + first_scene, (size_t)scene_count * sizeof(nb_scene_score), hipMemcpyDeviceToHost, ctx->stream));
@@ -1020,21 +988,16 @@ NB_EXPORT int nb_scenes_es_perturb_launch(const nb_es_params *ep, uint32_t featu
                                           uint32_t count, const void *mean, void *theta_out, void *stream)
 {
     static const char fn[] = "nb_scenes_es_perturb_launch";
-    if (!ep || !mean || !theta_out) {
-        g_tls_error = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    int rc = es_shape_check(fn, features, hidden, &g_tls_error);
+    int rc = scenes_null_check(fn, {ep, mean, theta_out}, &g_tls_error);
+    if (rc == NB_OK) rc = es_shape_check(fn, features, hidden, &g_tls_error);
     if (rc == NB_OK) rc = es_params_check(fn, *ep, &g_tls_error);
     if (rc != NB_OK) return rc;
     if ((uint64_t)first_scene + count > NB_ES_MAX_POPULATION) {
         g_tls_error = std::string(fn) + ": scenes [first_scene, first_scene + count) must lie in 0 .. NB_ES_MAX_POPULATION (4096)";
         return NB_ERR_INVALID;
     }
-    if (((uintptr_t)mean | (uintptr_t)theta_out) & 3u) {
-        g_tls_error = std::string(fn) + ": mean and theta_out must be 4-byte aligned";
-        return NB_ERR_INVALID;
-    }
+    rc = scenes_aligned_check(fn, 4, {mean, theta_out}, "mean and theta_out", &g_tls_error);
+    if (rc != NB_OK) return rc;
     const size_t m = nbk::policy_floats(features, hidden);
     if (ranges_overlap(theta_out, (size_t)count * m * sizeof(float), mean, m * sizeof(float))) {
         g_tls_error = std::string(fn) + ": theta_out must not overlap mean";
@@ -1053,25 +1016,17 @@ NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t featur
                                          void *report_out, void *stream)
 {
     static const char fn[] = "nb_scenes_es_update_launch";
-    if (!ep || !score || !mean || !mean_out || !rank_out) {
-        g_tls_error = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    int rc = es_shape_check(fn, features, hidden, &g_tls_error);
+    int rc = scenes_null_check(fn, {ep, score, mean, mean_out, rank_out}, &g_tls_error);
+    if (rc == NB_OK) rc = es_shape_check(fn, features, hidden, &g_tls_error);
     if (rc == NB_OK) rc = es_params_check(fn, *ep, &g_tls_error);
     if (rc != NB_OK) return rc;
     if (scenes == 0 || scenes > NB_ES_MAX_POPULATION) {
         g_tls_error = std::string(fn) + ": scenes must be 1 .. NB_ES_MAX_POPULATION (4096)";
         return NB_ERR_INVALID;
     }
-    if ((uintptr_t)score & 7u) {
-        g_tls_error = std::string(fn) + ": score must be 8-byte aligned";
-        return NB_ERR_INVALID;
-    }
-    if ((uintptr_t)mean & 3u) {
-        g_tls_error = std::string(fn) + ": mean must be 4-byte aligned";
-        return NB_ERR_INVALID;
-    }
+    rc = scenes_aligned_check(fn, 8, {score}, "score", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {mean}, "mean", &g_tls_error);
+    if (rc != NB_OK) return rc;
     const size_t mbytes = nbk::policy_floats(features, hidden) * sizeof(float);
     const bool in_place = mean_out == mean;   // the update may be in place: a weight's word is read and written by one lane
     const ByteRange in[2] = {{score, (size_t)scenes * sizeof(nb_scene_score)}, {in_place ? nullptr : mean, mbytes}};
@@ -1090,25 +1045,14 @@ NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t featur
 }
 
 // the context holds a search
-static int scenes_es_set_check(nb_scenes *ctx, const char *fn)
-{
-    if (!ctx->es_set) {
-        ctx->err = std::string(fn) + kCallEsSet;
-        return NB_ERR_STATE;
-    }
-    return NB_OK;
-}
+static int scenes_es_set_check(nb_scenes *ctx, const char *fn) { return scenes_state_check(ctx, fn, ctx->es_set, kCallEsSet); }
 
 NB_EXPORT int nb_scenes_es_set(nb_scenes *ctx, uint32_t features, uint32_t hidden, const float *mean_host, float accel_limit, const nb_es_params *ep)
 {
     static const char fn[] = "nb_scenes_es_set";
     int rc = ctx_check(ctx, fn);
-    if (rc != NB_OK) return rc;
-    if (!mean_host || !ep) {
-        ctx->err = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    rc = policy_check(fn, features, hidden, 0u, ctx->scenes, ctx->scenes, accel_limit, &ctx->err);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {mean_host, ep}, &ctx->err);
+    if (rc == NB_OK) rc = policy_check(fn, features, hidden, 0u, ctx->scenes, ctx->scenes, accel_limit, &ctx->err);
     if (rc == NB_OK) rc = es_params_check(fn, *ep, &ctx->err);
     if (rc != NB_OK) return rc;
     if (ctx->scenes > NB_ES_MAX_POPULATION) {
@@ -1126,7 +1070,7 @@ NB_EXPORT int nb_scenes_es_set(nb_scenes *ctx, uint32_t features, uint32_t hidde
     NB_HIP(ctx, ctx->es_report.reserve(4));
     NB_HIP(ctx, hipMemcpyAsync(ctx->es_mean.p, mean_host, m * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
-    ctx->es_features = features, ctx->es_hidden = hidden, ctx->es_limit = accel_limit, ctx->ep = *ep;
+    ctx->es_pol = {features, hidden, accel_limit}, ctx->ep = *ep;
     ctx->es_generation = 0;
     ctx->es_set = true;
     return NB_OK;
@@ -1139,9 +1083,9 @@ NB_EXPORT int nb_scenes_es_perturb(nb_scenes *ctx)
     if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
     if (rc != NB_OK) return rc;
     RoctxRange range(fn);
-    NB_HIP(ctx, nbk::launch_es_perturb(es_args(ctx->ep, ctx->es_features, ctx->es_hidden, ctx->es_generation, ctx->scenes), 0u, ctx->scenes,
+    NB_HIP(ctx, nbk::launch_es_perturb(es_args(ctx->ep, ctx->es_pol.features, ctx->es_pol.hidden, ctx->es_generation, ctx->scenes), 0u, ctx->scenes,
                                        ctx->es_mean.p, ctx->policy.p, ctx->stream));
-    ctx->features = ctx->es_features, ctx->hidden = ctx->es_hidden, ctx->policies = ctx->scenes, ctx->accel_limit = ctx->es_limit;
+    ctx->pol = ctx->es_pol, ctx->policies = ctx->scenes;
     return NB_OK;
 }
 
@@ -1153,7 +1097,7 @@ NB_EXPORT int nb_scenes_es_update(nb_scenes *ctx)
     if (rc == NB_OK) rc = scenes_score_set_check(ctx, fn);
     if (rc != NB_OK) return rc;
     RoctxRange range(fn);
-    const nbk::EsArgs a = es_args(ctx->ep, ctx->es_features, ctx->es_hidden, ctx->es_generation, ctx->scenes);
+    const nbk::EsArgs a = es_args(ctx->ep, ctx->es_pol.features, ctx->es_pol.hidden, ctx->es_generation, ctx->scenes);
     NB_HIP(ctx, nbk::launch_es_rank(a, ctx->score.p, ctx->es_rank.p, ctx->es_fitness.p, ctx->es_report.p, ctx->stream));
     NB_HIP(ctx, nbk::launch_es_update(a, ctx->es_rank.p, ctx->es_mean.p, ctx->es_mean.p, ctx->stream));
     ctx->es_generation += 1u;
@@ -1165,14 +1109,10 @@ NB_EXPORT int nb_scenes_es_mean(nb_scenes *ctx, float *out_host)
 {
     static const char fn[] = "nb_scenes_es_mean";
     int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {out_host}, &ctx->err);
+    if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
     if (rc != NB_OK) return rc;
-    if (!out_host) {
-        ctx->err = std::string(fn) + ": null argument";
-        return NB_ERR_INVALID;
-    }
-    rc = scenes_es_set_check(ctx, fn);
-    if (rc != NB_OK) return rc;
-    const size_t m = nbk::policy_floats(ctx->es_features, ctx->es_hidden);
+    const size_t m = nbk::policy_floats(ctx->es_pol.features, ctx->es_pol.hidden);
     NB_HIP(ctx, hipMemcpyAsync(out_host, ctx->es_mean.p, m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;
@@ -1183,11 +1123,8 @@ NB_EXPORT int nb_scenes_es_result(nb_scenes *ctx, nb_es_report *report, float *f
     static const char fn[] = "nb_scenes_es_result";
     int rc = ctx_check(ctx, fn);
     if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_state_check(ctx, fn, ctx->es_updated, kCallEsUpdate);
     if (rc != NB_OK) return rc;
-    if (!ctx->es_updated) {
-        ctx->err = std::string(fn) + kCallEsUpdate;
-        return NB_ERR_STATE;
-    }
     if (report) NB_HIP(ctx, hipMemcpyAsync(report, ctx->es_report.p, sizeof(nb_es_report), hipMemcpyDeviceToHost, ctx->stream));
     if (fitness) NB_HIP(ctx, hipMemcpyAsync(fitness, ctx->es_fitness.p, (size_t)ctx->scenes * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (rank) NB_HIP(ctx, hipMemcpyAsync(rank, ctx->es_rank.p, (size_t)ctx->scenes * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1216,11 +1153,8 @@ NB_EXPORT int nb_scenes_rewind(nb_scenes *ctx)
 {
     static const char fn[] = "nb_scenes_rewind";
     int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_state_check(ctx, fn, ctx->kept, kCallKeep);
     if (rc != NB_OK) return rc;
-    if (!ctx->kept) {
-        ctx->err = std::string(fn) + kCallKeep;
-        return NB_ERR_STATE;
-    }
     const size_t records = (size_t)ctx->scenes * ctx->n;
     NB_HIP(ctx, hipMemcpyAsync(ctx->pos.p, ctx->pos_kept.p, records * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));
     NB_HIP(ctx, hipMemcpyAsync(ctx->vel.p, ctx->vel_kept.p, records * sizeof(float4), hipMemcpyDeviceToDevice, ctx->stream));

@@ -31,9 +31,10 @@
 //   bitmap  256 bytes         kScenesMaxBodies membership bits
 // together 8 width + 12 n + 256 bytes: 9.7 KiB at n = 100, width = 1024; 56.25 KiB at n = 2 048, width = 4 096, the largest -- never
 // above 64 KiB, so the dynamic limit is not raised.  Per eye:
-//   1  clear the keys and the slots to all ones; barrier
-//   2  eye_row_fill over bodies j = 0 .. n-1 of scene s, j = i skipped (see_self = 0), the matrices read at inst + s n; keys carry j
-//   3  barrier; every column whose key is not all ones takes the LDS minimum (ds_min_u64) of (key >> 32) << 32 | c into slot id
+//   1  clear the slots to all ones
+//   2  scenes_eye_begin (nb_scenes_seen.inc, the one copy the three per-eye scenes kernels share): the keys cleared, a barrier, the
+//      row of eye b over the bodies of scene s, a barrier; keys carry j
+//   3  every column whose key is not all ones takes the LDS minimum (ds_min_u64) of (key >> 32) << 32 | c into slot id
 //   4  barrier; lanes take bodies j = t, t + LANES, ...; a __ballot per 64 bodies gives two bitmap words without an atomic.
 //      kEmit = false, the step: a lane whose slot is set forms L2-L4 and G2's three quotients and leaves them in the slot and the
 //      plane; after a barrier lane 0 walks the set bits ascending, adds the quotients, integrates and writes record b.
@@ -45,23 +46,18 @@
 template <int LANES, bool kEmit>
 __global__ __launch_bounds__(LANES) void scenes_nbody_located_kernel(ScenesLocatedArgs a)
 {
-    extern __shared__ uint64_t scenes_loc_keys[];                                      // a.width entries
-    uint64_t *slots = scenes_loc_keys + a.width;                                       // n entries
-    uint32_t *plane = reinterpret_cast<uint32_t *>(slots + a.n);                       // n words
-    uint32_t *bitmap = plane + a.n;                                                    // kScenesSeenWords words
-    const uint32_t n = a.n, width = a.width;
+    extern __shared__ uint64_t scenes_loc_keys[];                                      // width entries
+    const uint32_t n = a.eye.n, width = a.eye.width;
+    uint64_t *slots = scenes_loc_keys + width;                                         // n entries
+    uint32_t *plane = reinterpret_cast<uint32_t *>(slots + n);                         // n words
+    uint32_t *bitmap = plane + n;                                                      // kScenesSeenWords words
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t words = (n + 31u) >> 5;
     const float h = (float)width * 0.5f;     // exact
-    for (uint32_t e = blockIdx.x; e < a.count; e += gridDim.x) {
-        const uint32_t b = a.first_eye + e, s = b / n, self = b - s * n;
-        for (uint32_t c = tid; c < width; c += LANES) scenes_loc_keys[c] = ~0ull;
+    for (uint32_t e = blockIdx.x; e < a.eye.count; e += gridDim.x) {
         for (uint32_t j = tid; j < n; j += LANES) slots[j] = ~0ull;
-        __syncthreads();
-        float C[16];
-        raster_load16(a.cams + (size_t)b * 4, C);
-        eye_row_fill<LANES, EyeCover1>(scenes_loc_keys, C, a.inst + (size_t)s * n * 4, n, self, 0u, h, width);
-        __syncthreads();
+        uint32_t b, s, self;
+        scenes_eye_begin<LANES>(a.eye, scenes_loc_keys, e, b, s, self);
         for (uint32_t c = tid; c < width; c += LANES) {
             const uint64_t key = scenes_loc_keys[c];
             const uint32_t id = (uint32_t)key;
@@ -135,8 +131,8 @@ template <bool kEmit>
 static hipError_t launch_scenes_located_form(const ScenesLocatedArgs &a, hipStream_t s)
 {
     static_assert((size_t)4096 * 8u + (size_t)kScenesMaxBodies * 12u + kScenesSeenWords * 4u <= 65536u, "the dynamic limit is the default");
-    const size_t lds = (size_t)a.width * sizeof(uint64_t) + (size_t)a.n * (sizeof(uint64_t) + sizeof(uint32_t)) + kScenesSeenWords * sizeof(uint32_t);
-    return launch_scenes_eyes(scenes_nbody_located_kernel<64, kEmit>, scenes_nbody_located_kernel<256, kEmit>, a.n, a.count, lds, s, a);
+    const size_t lds = (size_t)a.eye.width * sizeof(uint64_t) + (size_t)a.eye.n * (sizeof(uint64_t) + sizeof(uint32_t)) + kScenesSeenWords * sizeof(uint32_t);
+    return launch_scenes_eyes(scenes_nbody_located_kernel<64, kEmit>, scenes_nbody_located_kernel<256, kEmit>, a.eye.n, a.eye.count, lds, s, a);
 }
 
 hipError_t launch_scenes_nbody_located(const ScenesLocatedArgs &a, hipStream_t s) { return launch_scenes_located_form<false>(a, s); }

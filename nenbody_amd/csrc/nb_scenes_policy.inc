@@ -27,9 +27,10 @@
 //   hid     H x 4 bytes       the hidden layer
 // together 8 width + 4 F + 4 H bytes: 8.4 KiB at width = 1024, (F, H) = (64, 32); 34 048 bytes at the limits -- the default dynamic
 // limit holds.  Per eye:
-//   1  clear the keys to all ones and the bins to 0x3F800000; barrier
-//   2  eye_row_fill over bodies j = 0 .. n-1 of scene s, j = i skipped (see_self = 0), the matrices read at inst + s n
-//   3  barrier; every column whose key is not all ones takes the LDS minimum (ds_min_u32) of its depth bits into bin c / (W/F)
+//   1  clear the bins to 0x3F800000
+//   2  scenes_eye_begin (nb_scenes_seen.inc, the one copy the three per-eye scenes kernels share): the keys cleared, a barrier, the
+//      row of eye b over the bodies of scene s, a barrier
+//   3  every column whose key is not all ones takes the LDS minimum (ds_min_u32) of its depth bits into bin c / (W/F)
 //   4  barrier; lane j < H runs P3: the bins are broadcast reads, w1 is feature-major so that the lanes' loads of one f coalesce
 //      (kEmit = true, P8: the F words of x leave coalesced here)
 //   5  barrier; lanes 0 and 1 run P4.  kEmit = false, the step: lane 0 takes o_1 from lane 1, runs P5-P6 and writes record b.
@@ -93,22 +94,16 @@ template <int LANES, bool kEmit>
 __global__ __launch_bounds__(LANES) void scenes_policy_kernel(ScenesPolicyArgs a)
 {
     static_assert(kPolicyMaxHidden <= (uint32_t)LANES, "one lane per hidden unit");
-    extern __shared__ uint64_t scenes_pol_keys[];                                      // a.width entries
-    uint32_t *bins = reinterpret_cast<uint32_t *>(scenes_pol_keys + a.width);          // a.features words
-    float *hid = reinterpret_cast<float *>(bins + a.features);                         // a.hidden words
-    const uint32_t n = a.n, width = a.width, features = a.features, hidden = a.hidden;
+    extern __shared__ uint64_t scenes_pol_keys[];                                      // width entries
+    const uint32_t width = a.eye.width, features = a.features, hidden = a.hidden;
+    uint32_t *bins = reinterpret_cast<uint32_t *>(scenes_pol_keys + width);            // features words
+    float *hid = reinterpret_cast<float *>(bins + features);                           // hidden words
     const uint32_t per = width / features;                                             // exact: F divides W
     const uint32_t tid = threadIdx.x;
-    const float h = (float)width * 0.5f;     // exact
-    for (uint32_t e = blockIdx.x; e < a.count; e += gridDim.x) {
-        const uint32_t b = a.first_eye + e, s = b / n, self = b - s * n;
-        for (uint32_t c = tid; c < width; c += LANES) scenes_pol_keys[c] = ~0ull;
+    for (uint32_t e = blockIdx.x; e < a.eye.count; e += gridDim.x) {
         for (uint32_t f = tid; f < features; f += LANES) bins[f] = kPolicyEmptyBits;
-        __syncthreads();
-        float C[16];
-        raster_load16(a.cams + (size_t)b * 4, C);
-        eye_row_fill<LANES, EyeCover1>(scenes_pol_keys, C, a.inst + (size_t)s * n * 4, n, self, 0u, h, width);
-        __syncthreads();
+        uint32_t b, s, self;
+        scenes_eye_begin<LANES>(a.eye, scenes_pol_keys, e, b, s, self);
         for (uint32_t c = tid; c < width; c += LANES) policy_pool(bins, c, per, scenes_pol_keys[c]);   // c / per < F
         __syncthreads();
         const float *__restrict__ w1 = a.weights + (size_t)s * a.stride;               // the eye's policy: w1, b1, w2, b2
@@ -145,8 +140,8 @@ template <bool kEmit>
 static hipError_t launch_scenes_policy_form(const ScenesPolicyArgs &a, hipStream_t s)
 {
     static_assert((size_t)4096 * 8u + (size_t)kPolicyMaxFeatures * 4u + (size_t)kPolicyMaxHidden * 4u <= 65536u, "the dynamic limit is the default");
-    const size_t lds = (size_t)a.width * sizeof(uint64_t) + ((size_t)a.features + a.hidden) * sizeof(uint32_t);
-    return launch_scenes_eyes(scenes_policy_kernel<64, kEmit>, scenes_policy_kernel<256, kEmit>, a.n, a.count, lds, s, a);
+    const size_t lds = (size_t)a.eye.width * sizeof(uint64_t) + ((size_t)a.features + a.hidden) * sizeof(uint32_t);
+    return launch_scenes_eyes(scenes_policy_kernel<64, kEmit>, scenes_policy_kernel<256, kEmit>, a.eye.n, a.eye.count, lds, s, a);
 }
 
 hipError_t launch_scenes_policy(const ScenesPolicyArgs &a, hipStream_t s) { return launch_scenes_policy_form<false>(a, s); }

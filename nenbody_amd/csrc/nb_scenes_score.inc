@@ -185,11 +185,7 @@ struct ScenesScoreLaunch {
     {
         static_assert((size_t)kScenesMaxBodies * sizeof(float4) + 8u * 1024u * sizeof(float) + 32u == 65568u, "the LDS of the largest scene");
         const size_t lds = (size_t)a.n * sizeof(float4) + 8u * LANES * sizeof(float) + 32u;   // 65 568 B at n = 2 048: above the default limit
-        const hipError_t e = scenes_lds_limit((const void *)scenes_score_kernel<LANES, TWO>, lds);
-        if (e != hipSuccess) return e;
-        const uint32_t grid = a.scenes < kScenesMaxGrid ? a.scenes : kScenesMaxGrid;
-        hipLaunchKernelGGL((scenes_score_kernel<LANES, TWO>), dim3(grid), dim3(LANES), lds, s, a);
-        return hipGetLastError();
+        return launch_scenes_scene<LANES>(scenes_score_kernel<LANES, TWO>, a.scenes, lds, s, a);
     }
 };
 hipError_t launch_scenes_score(const ScenesScoreArgs &a, hipStream_t s) { return scenes_by_size(a.n, ScenesScoreLaunch{a, s}); }

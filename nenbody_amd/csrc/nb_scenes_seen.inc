@@ -4,8 +4,9 @@
 // memory.  Every scene gets the bits nb_step_boids_seen gives a context of its n bodies (SV1): the row is nb_eyes.inc's eye_row_fill,
 // the pair nb_seen.inc's boids_seen_pair and the epilogue nb_boids.inc's boids_finish, each the one copy the single-scene chain runs.
 // Included by nb_kernels.hip inside namespace nbk, in the SLP-off unit behind nb_eyes.inc, nb_seen.inc and nb_scenes.inc: NOT in the
-// two units whose device code kernel_code_sha() hashes.  Launchers: nb_scenes.h.  The bitmap helpers and the launch shape below are
-// nb_scenes_located.inc's too.
+// two units whose device code kernel_code_sha() hashes.  Launchers: nb_scenes.h.  The bitmap helpers below are nb_scenes_located.inc's
+// too, the launch shape and the eye prologue (scenes_eye_begin) that file's and nb_scenes_policy.inc's; this file's kernel spells the
+// prologue out and takes loose parameters, the form in which it was measured (DESIGN.md section 14.7).
 //
 // Why the bits are the chain's.  The row is an order-independent 64-bit minimum, so neither the workgroup's shape nor the order the
 // candidates arrive in can change a key.  The seen list (S1-S3) is the set of ids in the row, ascending, without duplicates and with
@@ -76,6 +77,22 @@ static hipError_t launch_scenes_eyes(K k64, K k256, uint32_t n, uint32_t count, 
     return hipGetLastError();
 }
 
+// The head of every pass of a one-workgroup-per-eye scenes kernel over the eyes of `y`: eye e of the launch is body `self` of scene s,
+// record b of the batch; its row is resolved into `keys` (y.width entries of LDS) as eyes_kernel resolves it, the eye's own body not
+// drawn.  The kernel has issued the clears of its other LDS; the first barrier here orders them with the keys', the second the row.
+// scenes_boids_seen_kernel below holds the same statements itself.
+template <int LANES>
+__device__ __forceinline__ void scenes_eye_begin(const ScenesEyes &y, uint64_t *keys, uint32_t e, uint32_t &b, uint32_t &s, uint32_t &self)
+{
+    b = y.first_eye + e, s = b / y.n, self = b - s * y.n;
+    for (uint32_t c = threadIdx.x; c < y.width; c += LANES) keys[c] = ~0ull;
+    __syncthreads();
+    float C[16];
+    raster_load16(y.cams + (size_t)b * 4, C);
+    eye_row_fill<LANES, EyeCover1>(keys, C, y.inst + (size_t)s * y.n * 4, y.n, self, 0u, (float)y.width * 0.5f /* exact */, y.width);
+    __syncthreads();
+}
+
 template <int LANES, bool kEmit>
 __global__ __launch_bounds__(LANES) void scenes_boids_seen_kernel(BoidsArgs a, uint32_t n, uint32_t first_eye, uint32_t count,
                                                                  const float4 *__restrict__ cams, const float4 *__restrict__ inst,
@@ -125,22 +142,14 @@ __global__ __launch_bounds__(LANES) void scenes_boids_seen_kernel(BoidsArgs a, u
 }
 
 template <bool kEmit>
-static hipError_t launch_scenes_seen_form(const BoidsArgs &a, uint32_t n, uint32_t first_eye, uint32_t count, const float *cams,
-                                          const float *inst, uint32_t width, uint32_t *seen_count, uint32_t *seen_ids, hipStream_t s)
+static hipError_t launch_scenes_seen_form(const ScenesSeenArgs &a, hipStream_t s)
 {
-    const size_t lds = (size_t)width * sizeof(uint64_t) + kScenesSeenWords * sizeof(uint32_t);   // 32 KiB + 256 B at width 4096
-    return launch_scenes_eyes(scenes_boids_seen_kernel<64, kEmit>, scenes_boids_seen_kernel<256, kEmit>, n, count, lds, s, a, n, first_eye,
-                              count, (const float4 *)cams, (const float4 *)inst, width, seen_count, seen_ids);
+    const size_t lds = (size_t)a.eye.width * sizeof(uint64_t) + kScenesSeenWords * sizeof(uint32_t);   // 32 KiB + 256 B at width 4096
+    return launch_scenes_eyes(scenes_boids_seen_kernel<64, kEmit>, scenes_boids_seen_kernel<256, kEmit>, a.eye.n, a.eye.count, lds, s, a.c,
+                              a.eye.n, a.eye.first_eye, a.eye.count, a.eye.cams, a.eye.inst, a.eye.width, a.seen_count, a.seen_ids);
 }
 
-hipError_t launch_scenes_boids_seen(const BoidsArgs &c, uint32_t scenes, const float *cams, const float *inst, uint32_t width, hipStream_t s)
-{
-    return launch_scenes_seen_form<false>(c, c.n_total, 0u, scenes * c.n_total, cams, inst, width, nullptr, nullptr, s);
-}
+hipError_t launch_scenes_boids_seen(const ScenesSeenArgs &a, hipStream_t s) { return launch_scenes_seen_form<false>(a, s); }
 
-hipError_t launch_scenes_seen(uint32_t n, uint32_t first_eye, uint32_t count, const float *cams, const float *inst, uint32_t width,
-                              uint32_t *seen_count, uint32_t *seen_ids, hipStream_t s)
-{
-    return launch_scenes_seen_form<true>(BoidsArgs{}, n, first_eye, count, cams, inst, width, seen_count, seen_ids, s);
-}
+hipError_t launch_scenes_seen(const ScenesSeenArgs &a, hipStream_t s) { return launch_scenes_seen_form<true>(a, s); }
 #endif   // __HIPCC__

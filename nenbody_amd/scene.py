@@ -464,6 +464,7 @@ class SceneBatch:
         self.params = params if params is not None else _lib.default_params()
         self._lib = lib
         self._ctx = ctypes.c_void_p()
+        self._policy_shape, self._es_floats = (0, 0), 0   # what set_policy and es_set leave
         self._check(lib.nb_scenes_create(self.scenes, self.n, ctypes.byref(self.params), ctypes.byref(self._ctx)), created=False)
         try:
             self._check(lib.nb_scenes_upload(self._ctx, pos.ctypes.data, vel.ctypes.data))
@@ -482,6 +483,16 @@ class SceneBatch:
         if status != _lib.NB_OK:
             msg = self._lib.nb_scenes_last_error(self._ctx if created else None)
             raise NbError(status, msg.decode("utf-8", "replace") if msg else "")
+
+    @staticmethod
+    def _scene_range(batch, first_scene: int, scene_count: Optional[int]) -> int:
+        """scene_count, None: every scene of ``batch`` from first_scene on; a negative bound is refused here, in front of anything
+        that reads the batch"""
+        if scene_count is None:
+            scene_count = batch.scenes - first_scene
+        if first_scene < 0 or scene_count < 0:
+            raise ValueError("first_scene and scene_count must be >= 0")
+        return scene_count
 
     def step(self, k: int = 1) -> None:
         """k update_instance_nbody of every scene (STRICT), one launch"""
@@ -510,10 +521,7 @@ class SceneBatch:
         of the current state: per eye the scene-local ids in its row, ascending.  Returns (count uint32 (S, n), ids uint32
         (S, n, width) -- NB_EYES_NONE behind the first count slots); the words of :meth:`Scene.seen` per scene.  Depths and column
         counts are not kept by the batch's step and are not offered."""
-        if scene_count is None:
-            scene_count = self.scenes - first_scene
-        if first_scene < 0 or scene_count < 0:
-            raise ValueError("first_scene and scene_count must be >= 0")
+        scene_count = SceneBatch._scene_range(self, first_scene, scene_count)
         upv, cpm = self._eye_setup(width, up, cp)
         count = np.empty((scene_count, self.n), np.uint32)
         ids = np.empty((scene_count, self.n, max(int(width), 0)), np.uint32)
@@ -533,10 +541,7 @@ class SceneBatch:
         scene_count) of the current state.  Returns (count uint32 (S, n), ids uint32 (S, n, width), depth float32 (S, n, width), col
         uint32 (S, n, width), rel float32 (S, n, width, 4)): the words of :meth:`Scene.located` per scene, padding included, without
         its column counts, which the batch's step does not keep."""
-        if scene_count is None:
-            scene_count = self.scenes - first_scene
-        if first_scene < 0 or scene_count < 0:
-            raise ValueError("first_scene and scene_count must be >= 0")
+        scene_count = SceneBatch._scene_range(self, first_scene, scene_count)
         upv, cpm = self._eye_setup(width, up, cp)
         shape = (scene_count, self.n, max(int(width), 0))
         count = np.empty(shape[:2], np.uint32)
@@ -568,12 +573,9 @@ class SceneBatch:
         """What :meth:`step_policy` computes in front of the actuation (nb_scenes_eyes_policy) for scenes [first_scene, first_scene +
         scene_count) of the current state, without stepping.  Returns (features float32 (S, n, F), outputs float32 (S, n, 2) behind
         the limit)."""
-        if scene_count is None:
-            scene_count = self.scenes - first_scene
-        if first_scene < 0 or scene_count < 0:
-            raise ValueError("first_scene and scene_count must be >= 0")
+        scene_count = SceneBatch._scene_range(self, first_scene, scene_count)
         upv, cpm = self._eye_setup(width, up, cp)
-        feat = np.empty((scene_count, self.n, getattr(self, "_policy_shape", (0, 0))[0]), np.float32)
+        feat = np.empty((scene_count, self.n, self._policy_shape[0]), np.float32)
         act = np.empty((scene_count, self.n, 2), np.float32)
         self._check(self._lib.nb_scenes_eyes_policy(self._ctx, first_scene, scene_count, upv.ctypes.data, cpm.ctypes.data, width,
                                                     feat.ctypes.data, act.ctypes.data))
@@ -601,10 +603,7 @@ class SceneBatch:
     def scores(self, first_scene: int = 0, scene_count: Optional[int] = None) -> np.ndarray:
         """The records of scenes [first_scene, first_scene + scene_count) (nb_scenes_scores): a structured array of dtype
         :data:`SCORE_DTYPE`, 32 bytes a scene.  Waits for the stream."""
-        if scene_count is None:
-            scene_count = self.scenes - first_scene
-        if first_scene < 0 or scene_count < 0:
-            raise ValueError("first_scene and scene_count must be >= 0")
+        scene_count = SceneBatch._scene_range(self, first_scene, scene_count)
         out = np.zeros(max(scene_count, 1), SCORE_DTYPE)
         self._check(self._lib.nb_scenes_scores(self._ctx, first_scene, scene_count, out.ctypes.data))
         return out[:scene_count]
@@ -644,9 +643,9 @@ class SceneBatch:
 
     def es_mean(self) -> np.ndarray:
         """The mean (nb_scenes_es_mean): policy_floats float32.  Waits for the stream."""
-        out = np.zeros(max(getattr(self, "_es_floats", 0), 1), np.float32)
+        out = np.zeros(max(self._es_floats, 1), np.float32)
         self._check(self._lib.nb_scenes_es_mean(self._ctx, out.ctypes.data))
-        return out[:getattr(self, "_es_floats", 0)]
+        return out[:self._es_floats]
 
     def es_result(self):
         """What the last :meth:`es_update` left (nb_scenes_es_result): (report, a record of dtype :data:`ES_REPORT_DTYPE`; fitness
