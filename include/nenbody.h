@@ -476,6 +476,43 @@ typedef struct nb_es_report {
  * nb_scenes_es_mean, nb_scenes_es_result, nb_scenes_es_generation, nb_scenes_keep and nb_scenes_rewind on a context. */
 #include "nenbody_scenes_es.h"
 
+/* ---- scene batches: a recurrent policy with per-body memory -------------------------------------------
+ * The policy of P1-P8 sees one pooled depth row: bearing and range, no rate, and nothing of a neighbour that has left the slit.
+ * Here every body also owns H words of memory in device memory; the hidden layer reads the features and the memory, and the
+ * memory of the next step is the hidden layer, limited.  One kernel per step for the whole batch, as there.  Every step below is
+ * one binary32 operation, round to nearest, in the order written; there is no contraction: a product is rounded before it is
+ * added.  The notation, the limits on (F, H), the eye set-up and `policies` in {1, scenes} are those of P1-P8.
+ *   R1  one recurrent policy of shape (F, H) is nb_policy_recurrent_floats(F, H) = F*H + H*H + H + 2*H + 2 floats, in this order:
+ *       w1[f*H + j], wr[r*H + j], b1[j], w2[k*H + j] for k = 0, 1, b2[k].  wr[r*H + j] weighs memory word r into hidden unit j: it
+ *       is source-major, as w1 is.  At the limits (256, 64) this is 20 674 floats
+ *   R2  memory: every body owns H binary32 words m_r; the batch's memory is scenes*n*H words, body b = s*n + i at b*H.  It is all +0
+ *       initially and after a reset.  The features x_f are those of P1-P2
+ *   R3  hidden: t_j = b1[j]; then for f = 0 .. F-1 in order t_j = t_j + (w1[f*H + j] * x_f); then for r = 0 .. H-1 in order
+ *       t_j = t_j + (wr[r*H + j] * m_r); then h_j = (t_j > 0) ? t_j : +0, so a NaN gives +0
+ *   R4  new memory: m'_j = (h_j > S) ? S : h_j, with a memory limit S >= 0 (memory_limit; +inf: none).  R3 never yields a NaN, so
+ *       m' lies in [+0, S] whatever the old memory held
+ *   R5  outputs and motion: o_k comes from h (NOT from m') exactly as in P4; the acceleration and the integration are exactly P5-P6.
+ *       A body that coasts under P5 still takes its new memory
+ *   R6  (a consequence, stated and tested) with every word of wr equal to +0 and every memory word finite, positions and velocities
+ *       are those of the P-rule policy (w1, b1, w2, b2), bit for bit: t + (+0 * m) leaves every t except -0 alone, and -0 and +0
+ *       both give h = +0
+ *   R7  P7; additionally k steps in one call equal any split of them over calls with the memory carried.  The memory may be updated
+ *       in place: an eye reads and writes only its own H words
+ *   R8  per eye the F words of x, the two words of o and the H words of m' are observable without stepping and without changing
+ *       the memory
+ * Decisions where the rule left a choice.  nb_scenes_keep and nb_scenes_rewind are unchanged and do NOT touch the memory, so a
+ * generation of a search over a recurrent policy is six asynchronous calls: nb_scenes_rewind, nb_scenes_memory_reset,
+ * nb_scenes_score_reset, nb_scenes_es_perturb, nb_scenes_step_policy_scored(k), nb_scenes_es_update.  nb_scenes_upload does not
+ * clear the memory.  nb_scenes_step and the other laws leave the memory alone. */
+#define NB_ES_MAX_FLOATS 20674u /* nb_policy_recurrent_floats at the limits: the longest mean of a search */
+
+/* The eleven entries are declared in nenbody_scenes_policy_recurrent.h, which this header includes: nb_policy_recurrent_floats,
+ * the stateless nb_scenes_policy_recurrent_step_launch, nb_scenes_policy_recurrent_observe_launch,
+ * nb_scenes_es_perturb_floats_launch and nb_scenes_es_update_floats_launch on caller-owned device memory, and
+ * nb_scenes_set_policy_recurrent, nb_scenes_eyes_policy_memory, nb_scenes_memory_reset, nb_scenes_memory, nb_scenes_set_memory and
+ * nb_scenes_es_set_recurrent on a context. */
+#include "nenbody_scenes_policy_recurrent.h"
+
 /* The scene camera's frame: what the reference's display pass leaves in its width x height target
  * (src/main.rs:948-960) -- every instance's LineStrip triangle through ONE camera, the eye passes' pipeline otherwise: depth test
  * Less against a clear of 1.0, the skin (nb_eyes_skin) under the vignette, the clear colour, a Bgra8UnormSrgb target -- and which

@@ -449,6 +449,58 @@ public:
         o.feat.resize(cells), o.act.resize(eyes * 2);
         return o;
     }
+    // The batch's policies, recurrent (nb_scenes_set_policy_recurrent): `weights` holds 1 or scenes() policies of
+    // nb_policy_recurrent_floats(features, hidden) floats each -- w1[f * H + j], wr[r * H + j], b1[j], w2[k * H + j], b2[k].  Every body
+    // gets `hidden` words of memory, cleared to +0 here; memory_limit >= 0 clamps what a step writes to it; infinity: no limit.
+    // step_policy, step_policy_scored and policy_observe then run the recurrent kernel until set_policy sets a feedforward policy.
+    void set_policy_recurrent(const std::vector<float> &weights, uint32_t features, uint32_t hidden, float accel_limit = INFINITY,
+                              float memory_limit = INFINITY)
+    {
+        const size_t one = nb_policy_recurrent_floats(features, hidden);
+        if (one == 0 || weights.empty() || weights.size() % one != 0)
+            throw std::invalid_argument("weights must hold whole policies of nb_policy_recurrent_floats(features, hidden) floats");
+        check_sc(nb_scenes_set_policy_recurrent(ctx_, features, hidden, (uint32_t)(weights.size() / one), weights.data(), accel_limit,
+                                                memory_limit));
+        features_ = features, hidden_ = hidden;
+    }
+    // The memory of scenes [first_scene, first_scene + scene_count) (nb_scenes_memory): n * hidden floats a scene.  Waits for the stream.
+    std::vector<float> memory(uint32_t first_scene = 0, uint32_t scene_count = UINT32_MAX)
+    {
+        if (scene_count == UINT32_MAX) scene_count = first_scene <= scenes_ ? scenes_ - first_scene : 0;
+        const size_t words = (size_t)scene_count * n_ * hidden_;
+        std::vector<float> out(words ? words : 1);
+        check_sc(nb_scenes_memory(ctx_, first_scene, scene_count, out.data()));
+        out.resize(words);
+        return out;
+    }
+    // The memory of the whole batch from the host (nb_scenes_set_memory): scenes * n * hidden floats, any bit patterns.
+    void set_memory(const std::vector<float> &memory)
+    {
+        if (memory.empty() || memory.size() != (size_t)scenes_ * n_ * hidden_)
+            throw std::invalid_argument("memory must hold scenes * n * hidden floats");
+        check_sc(nb_scenes_set_memory(ctx_, memory.data()));
+    }
+    // The memory of every body set to +0 (nb_scenes_memory_reset), asynchronous.  An upload, keep and rewind do not touch the memory.
+    void memory_reset() { check_sc(nb_scenes_memory_reset(ctx_)); }
+    // policy_observe for a recurrent policy with the memory the step would write (nb_scenes_eyes_policy_memory); the memory is left
+    // as it is.
+    struct PolicyMemoryObservation {
+        uint32_t features = 0, hidden = 0;
+        std::vector<float> feat, act, mem;
+    };
+    PolicyMemoryObservation policy_observe_memory(const Mat4 &cp, uint32_t width = 1024, uint32_t first_scene = 0,
+                                                  uint32_t scene_count = UINT32_MAX, const Vec3 &up = Vec3{0.0f, 0.0f, 1.0f})
+    {
+        if (scene_count == UINT32_MAX) scene_count = first_scene <= scenes_ ? scenes_ - first_scene : 0;
+        PolicyMemoryObservation o;
+        o.features = features_, o.hidden = hidden_;
+        const size_t eyes = (size_t)scene_count * n_, cells = eyes * features_, words = eyes * hidden_;
+        o.feat.resize(cells ? cells : 1), o.act.resize(eyes ? eyes * 2 : 2), o.mem.resize(words ? words : 1);
+        check_sc(nb_scenes_eyes_policy_memory(ctx_, first_scene, scene_count, up.data(), cp[0].data(), width, o.feat.data(), o.act.data(),
+                                              o.mem.data()));
+        o.feat.resize(cells), o.act.resize(eyes * 2), o.mem.resize(words);
+        return o;
+    }
     // The batch's score (nb_scenes_set_score): radius_sq >= 0 is the squared radius below which a pair counts
     // as near (infinity: every pair), goal the point whose squared distance is summed.  Allocates one record a scene on first use
     // and clears the records.  May be called again.
@@ -486,6 +538,17 @@ public:
         check_sc(nb_scenes_es_set(ctx_, features, hidden, mean.data(), accel_limit, &ep));
         es_floats_ = mean.size();
         features_ = features;
+    }
+    // es_set over a recurrent policy (nb_scenes_es_set_recurrent): mean holds nb_policy_recurrent_floats(features, hidden) floats.  A
+    // generation is rewind, memory_reset, score_reset, es_perturb, step_policy_scored, es_update: rewind does not touch the memory.
+    void es_set_recurrent(const std::vector<float> &mean, uint32_t features, uint32_t hidden, const nb_es_params &ep,
+                          float accel_limit = INFINITY, float memory_limit = INFINITY)
+    {
+        if (mean.size() != nb_policy_recurrent_floats(features, hidden) || mean.empty())
+            throw std::invalid_argument("mean must hold nb_policy_recurrent_floats(features, hidden) floats");
+        check_sc(nb_scenes_es_set_recurrent(ctx_, features, hidden, mean.data(), accel_limit, memory_limit, &ep));
+        es_floats_ = mean.size();
+        features_ = features, hidden_ = hidden;
     }
     // The batch's policies become the population of the current generation (nb_scenes_es_perturb), asynchronous.
     void es_perturb() { check_sc(nb_scenes_es_perturb(ctx_)); }
@@ -556,6 +619,7 @@ private:
     nb_scenes *ctx_ = nullptr;
     uint32_t scenes_ = 0, n_ = 0;
     uint32_t features_ = 0;   // F of the policy set last; 0: none
+    uint32_t hidden_ = 0;     // H of the recurrent policy set last; 0: none
     size_t es_floats_ = 0;    // the floats of the search's mean; 0: none
 };
 

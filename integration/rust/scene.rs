@@ -145,6 +145,18 @@ extern "C" {
     fn nb_scenes_es_generation(ctx: *const NbScenes) -> u32;
     fn nb_scenes_keep(ctx: *mut NbScenes) -> c_int;
     fn nb_scenes_rewind(ctx: *mut NbScenes) -> c_int;
+    // a recurrent policy with per-body memory (include/nenbody_scenes_policy_recurrent.h)
+    fn nb_policy_recurrent_floats(features: u32, hidden: u32) -> usize;
+    fn nb_scenes_set_policy_recurrent(ctx: *mut NbScenes, features: u32, hidden: u32, policies: u32, weights_host: *const f32, accel_limit: f32, memory_limit: f32) -> c_int;
+    fn nb_scenes_eyes_policy_memory(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, up_xyz: *const f32, cp16: *const f32, width: u32, feat: *mut f32, act: *mut f32, mem_next: *mut f32) -> c_int;
+    fn nb_scenes_memory_reset(ctx: *mut NbScenes) -> c_int;
+    fn nb_scenes_memory(ctx: *mut NbScenes, first_scene: u32, scene_count: u32, out_host: *mut f32) -> c_int;
+    fn nb_scenes_set_memory(ctx: *mut NbScenes, mem_host: *const f32) -> c_int;
+    fn nb_scenes_es_set_recurrent(ctx: *mut NbScenes, features: u32, hidden: u32, mean_host: *const f32, accel_limit: f32, memory_limit: f32, ep: *const NbEsParams) -> c_int;
+    fn nb_scenes_policy_recurrent_step_launch(params: *const NbParams, scenes: u32, n: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, up_xyz: *const f32, features: u32, hidden: u32, policies: u32, weights: *const c_void, accel_limit: f32, memory_limit: f32, pos_in: *const c_void, vel_in: *const c_void, mem_in: *const c_void, pos_out: *mut c_void, vel_out: *mut c_void, mem_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_policy_recurrent_observe_launch(scenes: u32, n: u32, first_eye: u32, count: u32, cams_16: *const c_void, inst_16: *const c_void, width: u32, features: u32, hidden: u32, policies: u32, weights: *const c_void, accel_limit: f32, memory_limit: f32, mem: *const c_void, feat_out: *mut c_void, act_out: *mut c_void, mem_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_es_perturb_floats_launch(ep: *const NbEsParams, floats: u32, generation: u32, first_scene: u32, count: u32, mean: *const c_void, theta_out: *mut c_void, stream: *mut c_void) -> c_int;
+    fn nb_scenes_es_update_floats_launch(ep: *const NbEsParams, floats: u32, generation: u32, scenes: u32, score: *const c_void, mean: *const c_void, mean_out: *mut c_void, rank_out: *mut c_void, fitness_out: *mut c_void, report_out: *mut c_void, stream: *mut c_void) -> c_int;
     // the same on caller-owned device memory, in place
     fn nb_scenes_nbody_step_launch(params: *const NbParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
     fn nb_scenes_boids_step_launch(params: *const NbBoidsParams, scenes: u32, n: u32, k: u32, pos: *mut c_void, vel: *mut c_void, stream: *mut c_void) -> c_int;
@@ -201,6 +213,12 @@ pub const NB_ES_MAX_POPULATION: u32 = 4096;
 pub const NB_SCENES_MAX_BODIES: u32 = 2048;
 pub const NB_POLICY_MAX_FEATURES: u32 = 256;
 pub const NB_POLICY_MAX_HIDDEN: u32 = 64;
+
+/// The floats of one recurrent policy of shape (features, hidden): w1[f * H + j], wr[r * H + j], b1[j], w2[k * H + j], b2[k]; 0 for a
+/// shape outside the limits.
+pub fn policy_recurrent_floats(features: u32, hidden: u32) -> usize {
+    unsafe { nb_policy_recurrent_floats(features, hidden) }
+}
 
 /// The floats of one policy of shape (features, hidden): w1[f * H + j], b1[j], w2[k * H + j] for k = 0, 1, b2[k]; 0 for a shape
 /// outside the limits.
@@ -831,6 +849,7 @@ pub struct SceneBatch {
     pub scenes: usize,
     pub n: usize,
     policy_features: usize, // F of the policy set last; 0: none
+    policy_hidden: usize,   // H of the recurrent policy set last; 0: none
     es_floats: usize,       // the floats of the search's mean; 0: none
 }
 
@@ -858,7 +877,7 @@ impl SceneBatch {
         assert!(positions.len() == scenes * n && velocities.len() == scenes * n, "positions and velocities must hold scenes * n bodies");
         let mut ctx: *mut NbScenes = std::ptr::null_mut();
         check_scenes(unsafe { nb_scenes_create(scenes as u32, n as u32, &params, &mut ctx) }, std::ptr::null())?;
-        let batch = SceneBatch { ctx, scenes, n, policy_features: 0, es_floats: 0 };
+        let batch = SceneBatch { ctx, scenes, n, policy_features: 0, policy_hidden: 0, es_floats: 0 };
         check_scenes(unsafe { nb_scenes_upload(batch.ctx, positions.as_ptr() as *const f32, velocities.as_ptr() as *const f32) }, batch.ctx)?;
         Ok(batch)
     }
@@ -1023,6 +1042,77 @@ impl SceneBatch {
         check_scenes(unsafe { nb_scenes_es_set(self.ctx, features, hidden, mean.as_ptr(), accel_limit, ep) }, self.ctx)?;
         self.es_floats = mean.len();
         self.policy_features = features as usize;
+        Ok(())
+    }
+
+    /// the batch's policies, recurrent (nb_scenes_set_policy_recurrent): `weights` holds 1 or `scenes` policies
+    /// of policy_recurrent_floats(features, hidden) floats each; every body gets `hidden` words of memory, cleared to +0 here;
+    /// `memory_limit` >= 0 clamps what a step writes to it, f32::INFINITY: no limit.  step_policy, step_policy_scored and
+    /// policy_observe then run the recurrent kernel until set_policy sets a feedforward policy
+    pub fn set_policy_recurrent(&mut self, weights: &[f32], features: u32, hidden: u32, accel_limit: f32, memory_limit: f32) -> Result<(), SceneError> {
+        let one = policy_recurrent_floats(features, hidden);
+        if one == 0 || weights.is_empty() || weights.len() % one != 0 {
+            return Err(SceneError(-1, "weights must hold whole policies of policy_recurrent_floats(features, hidden) floats".to_string())); // NB_ERR_INVALID
+        }
+        check_scenes(
+            unsafe { nb_scenes_set_policy_recurrent(self.ctx, features, hidden, (weights.len() / one) as u32, weights.as_ptr(), accel_limit, memory_limit) },
+            self.ctx,
+        )?;
+        self.policy_features = features as usize;
+        self.policy_hidden = hidden as usize;
+        Ok(())
+    }
+
+    /// the memory of scenes [first_scene, first_scene + scene_count) (nb_scenes_memory): n * hidden floats a scene; waits for the stream
+    pub fn memory(&mut self, first_scene: u32, scene_count: u32) -> Result<Vec<f32>, SceneError> {
+        let words = scene_count as usize * self.n * self.policy_hidden;
+        let mut out = vec![0f32; words.max(1)];
+        check_scenes(unsafe { nb_scenes_memory(self.ctx, first_scene, scene_count, out.as_mut_ptr()) }, self.ctx)?;
+        out.truncate(words);
+        Ok(out)
+    }
+
+    /// the memory of the whole batch from the host (nb_scenes_set_memory): scenes * n * hidden floats, any bit patterns
+    pub fn set_memory(&mut self, memory: &[f32]) -> Result<(), SceneError> {
+        if memory.is_empty() || memory.len() != self.scenes * self.n * self.policy_hidden {
+            return Err(SceneError(-1, "memory must hold scenes * n * hidden floats".to_string())); // NB_ERR_INVALID
+        }
+        check_scenes(unsafe { nb_scenes_set_memory(self.ctx, memory.as_ptr()) }, self.ctx)
+    }
+
+    /// the memory of every body set to +0 (nb_scenes_memory_reset), asynchronous; an upload, keep and rewind do not touch the memory
+    pub fn memory_reset(&mut self) -> Result<(), SceneError> {
+        check_scenes(unsafe { nb_scenes_memory_reset(self.ctx) }, self.ctx)
+    }
+
+    /// policy_observe for a recurrent policy with the memory the step would write (nb_scenes_eyes_policy_memory), the memory left as
+    /// it is: (features, outputs, next memory)
+    pub fn policy_observe_memory(&mut self, first_scene: u32, scene_count: u32, cp: &[[f32; 4]; 4], width: u32) -> Result<(Vec<f32>, Vec<[f32; 2]>, Vec<f32>), SceneError> {
+        let up = [0f32, 0.0, 1.0];
+        let eyes = scene_count as usize * self.n;
+        let mut feat = vec![0f32; (eyes * self.policy_features).max(1)];
+        let mut act = vec![[0f32; 2]; eyes.max(1)];
+        let mut mem = vec![0f32; (eyes * self.policy_hidden).max(1)];
+        check_scenes(
+            unsafe {
+                nb_scenes_eyes_policy_memory(self.ctx, first_scene, scene_count, up.as_ptr(), cp.as_ptr() as *const f32, width, feat.as_mut_ptr(), act.as_mut_ptr() as *mut f32, mem.as_mut_ptr())
+            },
+            self.ctx,
+        )?;
+        feat.truncate(eyes * self.policy_features);
+        act.truncate(eyes);
+        mem.truncate(eyes * self.policy_hidden);
+        Ok((feat, act, mem))
+    }
+
+    /// es_set over a recurrent policy (nb_scenes_es_set_recurrent): `mean` holds policy_recurrent_floats(features, hidden) floats.  A
+    /// generation is rewind, memory_reset, score_reset, es_perturb, step_policy_scored, es_update: rewind does not touch the memory
+    pub fn es_set_recurrent(&mut self, features: u32, hidden: u32, mean: &[f32], accel_limit: f32, memory_limit: f32, ep: &NbEsParams) -> Result<(), SceneError> {
+        assert_eq!(mean.len(), policy_recurrent_floats(features, hidden), "mean must hold policy_recurrent_floats(features, hidden) floats");
+        check_scenes(unsafe { nb_scenes_es_set_recurrent(self.ctx, features, hidden, mean.as_ptr(), accel_limit, memory_limit, ep) }, self.ctx)?;
+        self.es_floats = mean.len();
+        self.policy_features = features as usize;
+        self.policy_hidden = hidden as usize;
         Ok(())
     }
 

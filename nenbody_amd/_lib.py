@@ -35,6 +35,7 @@ NB_SCENES_MAX_BODIES = 2048
 NB_POLICY_MAX_FEATURES = 256
 NB_POLICY_MAX_HIDDEN = 64
 NB_ES_MAX_POPULATION = 4096
+NB_ES_MAX_FLOATS = 20674
 NB_EYES_NONE = 0xFFFFFFFF
 NB_EYES_SEE_SELF = 1
 NB_EYES_MAX_WIDTH = 4096
@@ -306,6 +307,26 @@ ES_PROTOTYPES = {
     "nb_scenes_rewind": (c_int, [c_void_p]),
 }
 
+# include/nenbody_scenes_policy_recurrent.h: a recurrent policy with per-body memory, bound likewise
+SCENES_POLICY_RECURRENT_PROTOTYPES = {
+    "nb_policy_recurrent_floats": (c_size_t, [c_uint32, c_uint32]),
+    "nb_scenes_policy_recurrent_step_launch": (c_int, [POINTER(NbParams), c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32,
+                                                       c_uint32, c_uint32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_policy_recurrent_observe_launch": (c_int, [c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32,
+                                                          c_uint32, c_uint32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p]),
+    "nb_scenes_es_perturb_floats_launch": (c_int, [POINTER(NbEsParams), c_uint32, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_es_update_floats_launch": (c_int, [POINTER(NbEsParams), c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_set_policy_recurrent": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_float, c_float]),
+    "nb_scenes_eyes_policy_memory": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "nb_scenes_memory_reset": (c_int, [c_void_p]),
+    "nb_scenes_memory": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p]),
+    "nb_scenes_set_memory": (c_int, [c_void_p, c_void_p]),
+    "nb_scenes_es_set_recurrent": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_float, c_float, POINTER(NbEsParams)]),
+}
+
 # every symbol include/nenbody_diag.h declares (self-tests, the test suite's switches): not part of the drop-in boundary
 DIAG_PROTOTYPES = {
     "nb_selftest_ladder": (c_int, [c_uint32, c_uint32, POINTER(c_uint64), c_void_p]),
@@ -368,7 +389,8 @@ def _bind(path: str) -> ctypes.CDLL:
     _preload_torch_hip_runtime()
     lib = ctypes.CDLL(path)
     for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SCENES_SEEN_PROTOTYPES.items()) + list(SCENES_LOCATED_PROTOTYPES.items()) \
-            + list(SCENES_POLICY_PROTOTYPES.items()) + list(SCENES_SCORE_PROTOTYPES.items()) + list(ES_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
+            + list(SCENES_POLICY_PROTOTYPES.items()) + list(SCENES_SCORE_PROTOTYPES.items()) + list(ES_PROTOTYPES.items()) \
+            + list(SCENES_POLICY_RECURRENT_PROTOTYPES.items()) + list(DIAG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = restype
         fn.argtypes = argtypes

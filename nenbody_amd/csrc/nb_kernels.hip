@@ -49,6 +49,7 @@
 //   nb_scenes_seen.inc   scene batches: the seen boids step, eye row and seen set in LDS, one workgroup per eye (SLP-off unit; launchers in nb_scenes.h)
 //   nb_scenes_located.inc scene batches: gravity from located vision, row, depths, columns and quotients in LDS, one workgroup per eye (SLP-off unit; launchers in nb_scenes.h)
 //   nb_scenes_policy.inc scene batches: a neural policy over each eye row, row, pooled features and hidden layer in LDS, one workgroup per eye (SLP-off unit; launchers in nb_scenes.h)
+//   nb_scenes_policy_recurrent.inc scene batches: that policy with H words of memory per body kept in device memory between steps, one workgroup per eye (SLP-off unit; launchers in nb_scenes.h)
 //   nb_scenes_score.inc  scene batches: every scene's snapshot reduced to a 32-byte record of metrics, positions and partial sums in LDS, one workgroup per scene (SLP-off unit; launcher in nb_scenes.h)
 //   nb_scenes_es.inc     scene batches: an evolution-strategies generation -- the population drawn by Philox, the records ranked in one workgroup, the mean updated from exact integer sums (SLP-off unit; launchers in nb_scenes.h)
 //   nb_launch.inc        host-side launchers
@@ -95,6 +96,7 @@ static_assert(kMsaaOffsets16 == sample_nibbles(kEyeSampleX16) && kFrameMsaaOffse
 #include "nb_scenes_seen.inc" // the seen boids step of a batch, one workgroup per eye: likewise; uses nb_eyes.inc's eye_row_fill, nb_seen.inc's pair and nb_boids.inc's epilogue
 #include "nb_scenes_located.inc" // gravity from located vision for a batch, one workgroup per eye: likewise; uses nb_eyes.inc's eye_row_fill, nb_located.inc's L2-L4 and G2 helpers, nb_scenes_seen.inc's bitmap helpers and nb_nbody_strict.inc's integrate
 #include "nb_scenes_policy.inc" // a neural policy over each eye row of a batch, one workgroup per eye: likewise; uses nb_eyes.inc's eye_row_fill, nb_located.inc's located_basis, nb_scenes_seen.inc's launch shape and nb_nbody_strict.inc's integrate
+#include "nb_scenes_policy_recurrent.inc" // the recurrent policy of a batch, one workgroup per eye: likewise; uses nb_scenes_policy.inc's pooling, outputs and actuation as they are
 #include "nb_scenes_score.inc" // the score of a batch, one workgroup per scene: likewise; uses nb_scenes.inc's launch ladder and nb_scenes_policy.inc's policy_finite
 #include "nb_scenes_es.inc"   // one evolution-strategies generation over a batch: likewise; uses nb_scenes_score.inc's score_wave_sum
 #else

@@ -102,6 +102,23 @@ hipError_t launch_scenes_policy(const ScenesPolicyArgs &a, hipStream_t s);
 // What that step computes per eye in front of the actuation: the features and the limited outputs, indexed from first_eye.
 hipError_t launch_scenes_policy_observe(const ScenesPolicyArgs &a, hipStream_t s);
 
+// The recurrent policy (nb_scenes_policy_recurrent.inc): the policy above with H words of memory per body in
+// device memory -- 8 width + 4 features + 8 hidden bytes of LDS, at most 34 304.  The caller has checked what the policy above asks
+// and mem_limit >= 0.
+// the floats of one recurrent policy: w1[f H + j], wr[r H + j], b1[j], w2[k H + j] (k = 0, 1), b2[k]
+constexpr size_t policy_recurrent_floats(uint32_t features, uint32_t hidden) { return policy_floats(features, hidden) + (size_t)hidden * hidden; }
+struct ScenesPolicyRecurrentArgs {
+    ScenesPolicyArgs p;                      // as above; stride is policy_recurrent_floats, or 0
+    float mem_limit;                         // S >= 0; +inf: none
+    const float *mem_in;                     // the WHOLE batch's memory, body b at b * hidden: read for the eyes the arguments name
+    float *mem_out;                          // the step's: written at b * hidden; may be mem_in itself
+    uint32_t *mem_obs;                       // the observable's (R8): count x hidden words of m', indexed from first_eye; may be NULL
+};
+// ONE step for every eye the arguments name (the entries pass the whole batch): records out of place, the memory in place or not.
+hipError_t launch_scenes_policy_recurrent(const ScenesPolicyRecurrentArgs &a, hipStream_t s);
+// What that step computes per eye in front of the actuation, the memory left as it is.
+hipError_t launch_scenes_policy_recurrent_observe(const ScenesPolicyRecurrentArgs &a, hipStream_t s);
+
 // The score of a batch (nb_scenes_score.inc): one workgroup per scene in launch_scenes_nbody's shape, the
 // scene's positions and the partial sums in LDS -- 16 n + 32 LANES + 32 bytes, 65 568 at n = 2 048.  Every scene's record takes the
 // metrics of its current snapshot (Q1-Q7).  The caller has checked the arguments (scenes >= 1, 1 <= n <= kScenesMaxBodies,

@@ -3,7 +3,8 @@
 // nb_scenes, which owns a batch and a stream.  Section 14.1: the boids step over what each body sees, and the seen sets.  Section 14.2:
 // gravity from located vision, and the located sets.  Section 14.4: a neural policy over each eye row, and its observable.  Section
 // 14.5: the score of every scene, accumulated on the device.  Section 14.6: an evolution-strategies generation, with keep and rewind.
-// Sections 14.3 and 14.7: the helpers the entries share.  Included by nb_api.hip behind nb_vision_api.inc.  Every check runs before
+// Section 14.8: a recurrent policy with per-body memory, its memory's entries and the search over it.  Sections 14.3 and 14.7: the
+// helpers the entries share.  Included by nb_api.hip behind nb_vision_api.inc.  Every check runs before
 // anything touches the device and has its own message naming the entry.
 
 static_assert(NB_SCENES_MAX_BODIES == nbk::kScenesMaxBodies, "the header's limit is the kernels'");
@@ -304,9 +305,12 @@ NB_EXPORT int nb_scenes_located_launch(uint32_t scenes, uint32_t n, uint32_t fir
 }
 
 // ---- the context --------------------------------------------------------------------------------------------------------------------------
-struct ScenesPolicyShape {                   // a policy's (F, H) and the limit of its outputs
+struct ScenesPolicyShape {                   // a policy's (F, H) and the limit of its outputs; recurrent (section 14.8): R4's limit too
     uint32_t features = 0, hidden = 0;
     float accel_limit = 0.f;
+    bool recurrent = false;
+    float memory_limit = 0.f;
+    size_t floats() const { return recurrent ? nbk::policy_recurrent_floats(features, hidden) : nbk::policy_floats(features, hidden); }
 };
 
 struct nb_scenes {
@@ -325,10 +329,13 @@ struct nb_scenes {
     ScenesPolicyShape pol;                         // their shape
     uint32_t policies = 0;                         // 0: no policy set
     DeviceBuffer<uint32_t> pol_feat, pol_act;      // nb_scenes_eyes_policy's features and outputs for one range of scenes, grown on demand
+    DeviceBuffer<uint32_t> pol_mem;                // nb_scenes_eyes_policy_memory's next memory for one range of scenes, likewise
+    DeviceBuffer<float> memory;                    // a recurrent policy's memory (R2): scenes * n * hidden floats, stepped in place
+    size_t memory_words = 0;                       // the floats of it in use; 0: no recurrent policy or search is set
     DeviceBuffer<nbk::SceneScore> score;           // nb_scenes_set_score's records, one a scene
     nb_score_params sp{};                          // its parameters
     bool score_set = false;
-    DeviceBuffer<float> es_mean;                   // nb_scenes_es_set's mean: nb_policy_floats floats, updated in place
+    DeviceBuffer<float> es_mean;                   // nb_scenes_es_set's mean: es_pol.floats() floats, updated in place
     DeviceBuffer<uint32_t> es_rank;                // what the last nb_scenes_es_update left: scenes ranks,
     DeviceBuffer<float> es_fitness;                // scenes fitnesses
     DeviceBuffer<uint32_t> es_report;              // and the four words of nb_es_report
@@ -741,6 +748,142 @@ NB_EXPORT int nb_scenes_policy_observe_launch(uint32_t scenes, uint32_t n, uint3
                          &g_tls_error);
 }
 
+// ---- a recurrent policy with per-body memory (DESIGN.md section 14.8): the stateless entries ---------------------------------------------
+static const char kNoPolicyMemoryOutputs[] = ": feat_out, act_out and mem_out are all NULL";
+static const char kCallSetPolicyRecurrent[] = ": no recurrent policy set (call nb_scenes_set_policy_recurrent first)";
+static_assert(NB_ES_MAX_FLOATS == nbk::policy_recurrent_floats(NB_POLICY_MAX_FEATURES, NB_POLICY_MAX_HIDDEN), "the longest mean is the largest recurrent policy");
+
+NB_EXPORT size_t nb_policy_recurrent_floats(uint32_t features, uint32_t hidden)
+{
+    if (features == 0 || features > NB_POLICY_MAX_FEATURES || hidden == 0 || hidden > NB_POLICY_MAX_HIDDEN) return 0;
+    return nbk::policy_recurrent_floats(features, hidden);
+}
+
+// policy_check, then R4's limit
+static int policy_recurrent_check(const char *fn, uint32_t features, uint32_t hidden, uint32_t width, uint32_t policies, uint32_t scenes,
+                                  float accel_limit, float memory_limit, std::string *err)
+{
+    const int rc = policy_check(fn, features, hidden, width, policies, scenes, accel_limit, err);
+    if (rc != NB_OK) return rc;
+    if (!(memory_limit >= 0.0f)) {
+        *err = std::string(fn) + ": memory_limit must be at least 0 (+inf: no limit)";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+// the recurrent kernel's arguments but for its buffers: scenes_policy_args with the longer policies, and R4's limit
+static nbk::ScenesPolicyRecurrentArgs scenes_policy_recurrent_args(const nbk::ScenesEyes &eye, const ScenesPolicyShape &shape, uint32_t policies,
+                                                                   const void *weights)
+{
+    nbk::ScenesPolicyRecurrentArgs a{};
+    a.p = scenes_policy_args(eye, shape, policies, weights);
+    a.p.stride = policies == 1 ? 0u : (uint32_t)nbk::policy_recurrent_floats(shape.features, shape.hidden);
+    a.mem_limit = shape.memory_limit;
+    return a;
+}
+
+NB_EXPORT int nb_scenes_policy_recurrent_step_launch(const nb_params *params, uint32_t scenes, uint32_t n, const void *cams_16,
+                                                     const void *inst_16, uint32_t width, const float *up_xyz, uint32_t features,
+                                                     uint32_t hidden, uint32_t policies, const void *weights, float accel_limit,
+                                                     float memory_limit, const void *pos_in, const void *vel_in, const void *mem_in,
+                                                     void *pos_out, void *vel_out, void *mem_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_policy_recurrent_step_launch";
+    const nb_params p = params_or_default(params);
+    int rc = scenes_null_check(fn, {cams_16, inst_16, up_xyz, weights, pos_in, vel_in, mem_in, pos_out, vel_out, mem_out}, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    if (rc == NB_OK) rc = policy_recurrent_check(fn, features, hidden, width, policies, scenes, accel_limit, memory_limit, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_params_check(fn, p, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {weights}, "weights", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {mem_in, mem_out}, "mem_in and mem_out", &g_tls_error);
+    const size_t records = (size_t)scenes * n;
+    if (rc == NB_OK) rc = scenes_step_buffers_check(fn, records, cams_16, inst_16, pos_in, vel_in, pos_out, vel_out, up_xyz, nullptr, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    const size_t wbytes = (size_t)policies * nbk::policy_recurrent_floats(features, hidden) * sizeof(float);
+    const size_t mbytes = records * hidden * sizeof(float), rbytes = records * sizeof(float4);
+    const bool in_place = mem_out == mem_in;   // R7: an eye reads and writes only its own words
+    if (!in_place && ranges_overlap(mem_out, mbytes, mem_in, mbytes)) {
+        g_tls_error = std::string(fn) + ": mem_out must be mem_in itself or clear of it";
+        return NB_ERR_INVALID;
+    }
+    const ByteRange in[7] = {{cams_16, rbytes * 4u}, {inst_16, rbytes * 4u}, {pos_in, rbytes}, {vel_in, rbytes}, {weights, wbytes},
+                             {in_place ? nullptr : mem_in, mbytes}, {up_xyz, 3 * sizeof(float)}};
+    const ByteRange out[3] = {{pos_out, rbytes}, {vel_out, rbytes}, {mem_out, mbytes}};
+    rc = outputs_check(fn, out, 0x7u, "", false, in, 7, kScenesSeenAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    rc = device_for_launch(pos_in, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    ScenesPolicyShape shape{features, hidden, accel_limit, true, memory_limit};
+    nbk::ScenesPolicyRecurrentArgs a = scenes_policy_recurrent_args(scenes_eyes(n, 0u, (uint32_t)records, cams_16, inst_16, width), shape, policies, weights);
+    a.p.pos_in = (const float4 *)pos_in, a.p.vel_in = (const float4 *)vel_in, a.p.pos_out = (float4 *)pos_out, a.p.vel_out = (float4 *)vel_out;
+    a.p.ux = up_xyz[0], a.p.uy = up_xyz[1], a.p.uz = up_xyz[2], a.p.dt = p.dt;
+    a.mem_in = (const float *)mem_in, a.mem_out = (float *)mem_out;
+    return launch_status(nbk::launch_scenes_policy_recurrent(a, (hipStream_t)stream), "nb: recurrent policy kernel launch failed (scene batch): ",
+                         &g_tls_error);
+}
+
+NB_EXPORT int nb_scenes_policy_recurrent_observe_launch(uint32_t scenes, uint32_t n, uint32_t first_eye, uint32_t count, const void *cams_16,
+                                                        const void *inst_16, uint32_t width, uint32_t features, uint32_t hidden,
+                                                        uint32_t policies, const void *weights, float accel_limit, float memory_limit,
+                                                        const void *mem, void *feat_out, void *act_out, void *mem_out, void *stream)
+{
+    static const char fn[] = "nb_scenes_policy_recurrent_observe_launch";
+    int rc = scenes_null_check(fn, {cams_16, inst_16, weights, mem}, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_vision_check(fn, scenes, n, width, nullptr, &g_tls_error);
+    if (rc == NB_OK) rc = policy_recurrent_check(fn, features, hidden, width, policies, scenes, accel_limit, memory_limit, &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {weights}, "weights", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {mem}, "mem", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_aligned_check(fn, 16, {cams_16, inst_16}, "cams_16 and inst_16", &g_tls_error);
+    if (rc == NB_OK) rc = scenes_eye_range_check(fn, scenes, n, first_eye, count, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    const size_t matrices = (size_t)scenes * n * 16 * sizeof(float);
+    const ByteRange in[4] = {{cams_16, matrices},
+                             {inst_16, matrices},
+                             {weights, (size_t)policies * nbk::policy_recurrent_floats(features, hidden) * sizeof(float)},
+                             {mem, (size_t)scenes * n * hidden * sizeof(float)}};
+    const ByteRange out[3] = {{feat_out, (size_t)count * features * 4u}, {act_out, (size_t)count * 8u}, {mem_out, (size_t)count * hidden * 4u}};
+    rc = outputs_check(fn, out, 0x7u, kNoPolicyMemoryOutputs, true, in, 4, kScenesSeenAlias, &g_tls_error);
+    if (rc != NB_OK) return rc;
+    if (count == 0) return NB_OK;
+    rc = device_for_launch(inst_16, stream, SelectDevice::kAlways);
+    if (rc != NB_OK) return rc;
+    ScenesPolicyShape shape{features, hidden, accel_limit, true, memory_limit};
+    nbk::ScenesPolicyRecurrentArgs a = scenes_policy_recurrent_args(scenes_eyes(n, first_eye, count, cams_16, inst_16, width), shape, policies, weights);
+    a.p.feat_out = (uint32_t *)feat_out, a.p.act_out = (uint32_t *)act_out;
+    a.mem_in = (const float *)mem, a.mem_obs = (uint32_t *)mem_out;
+    return launch_status(nbk::launch_scenes_policy_recurrent_observe(a, (hipStream_t)stream),
+                         "nb: recurrent policy kernel launch failed (scene batch, observe form): ", &g_tls_error);
+}
+
+// the context's policies from the host: what nb_scenes_set_policy and nb_scenes_set_policy_recurrent do behind their checks
+static int scenes_policies_upload(nb_scenes *ctx, const ScenesPolicyShape &shape, uint32_t policies, const float *weights_host)
+{
+    const size_t floats = (size_t)policies * shape.floats();
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step in flight may still read the policies in place
+    ctx->policies = 0;
+    NB_HIP(ctx, ctx->policy.reserve(floats));
+    NB_HIP(ctx, hipMemcpyAsync(ctx->policy.p, weights_host, floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
+    ctx->pol = shape, ctx->policies = policies;
+    return NB_OK;
+}
+
+// The context's memory for a recurrent policy of `hidden` units: there and in use.  A memory of another size (none, or another H) is
+// replaced and cleared to +0 on the context's stream; one of this size keeps its words unless `clear`.
+static int scenes_memory_ensure(nb_scenes *ctx, uint32_t hidden, bool clear)
+{
+    const size_t words = (size_t)ctx->scenes * ctx->n * hidden;
+    if (!clear && ctx->memory_words == words && ctx->memory.cells >= words) return NB_OK;
+    if (ctx->memory.cells < words) {
+        NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step in flight may still use the memory that is replaced
+        NB_HIP(ctx, ctx->memory.reserve(words));
+    }
+    NB_HIP(ctx, hipMemsetAsync(ctx->memory.p, 0, words * sizeof(float), ctx->stream));
+    ctx->memory_words = words;
+    return NB_OK;
+}
+
 NB_EXPORT int nb_scenes_set_policy(nb_scenes *ctx, uint32_t features, uint32_t hidden, uint32_t policies, const float *weights_host,
                                    float accel_limit)
 {
@@ -749,14 +892,26 @@ NB_EXPORT int nb_scenes_set_policy(nb_scenes *ctx, uint32_t features, uint32_t h
     if (rc == NB_OK) rc = scenes_null_check(fn, {weights_host}, &ctx->err);
     if (rc == NB_OK) rc = policy_check(fn, features, hidden, 0u, policies, ctx->scenes, accel_limit, &ctx->err);
     if (rc != NB_OK) return rc;
-    const size_t floats = (size_t)policies * nbk::policy_floats(features, hidden);
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step in flight may still read the policies in place
-    ctx->policies = 0;
-    NB_HIP(ctx, ctx->policy.reserve(floats));
-    NB_HIP(ctx, hipMemcpyAsync(ctx->policy.p, weights_host, floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
-    ctx->pol = {features, hidden, accel_limit}, ctx->policies = policies;
-    return NB_OK;
+    rc = scenes_policies_upload(ctx, {features, hidden, accel_limit}, policies, weights_host);
+    // a feedforward policy: the memory's entries are NB_ERR_STATE again, unless a search over a recurrent policy still owns the memory
+    if (rc == NB_OK && !(ctx->es_set && ctx->es_pol.recurrent)) ctx->memory_words = 0;
+    return rc;
+}
+
+NB_EXPORT int nb_scenes_set_policy_recurrent(nb_scenes *ctx, uint32_t features, uint32_t hidden, uint32_t policies, const float *weights_host,
+                                             float accel_limit, float memory_limit)
+{
+    static const char fn[] = "nb_scenes_set_policy_recurrent";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {weights_host}, &ctx->err);
+    if (rc == NB_OK) rc = policy_recurrent_check(fn, features, hidden, 0u, policies, ctx->scenes, accel_limit, memory_limit, &ctx->err);
+    if (rc != NB_OK) return rc;
+    rc = scenes_policies_upload(ctx, {features, hidden, accel_limit, true, memory_limit}, policies, weights_host);
+    if (rc != NB_OK) return rc;
+    ctx->policies = 0;                               // none is set until the memory is there
+    rc = scenes_memory_ensure(ctx, hidden, true);
+    if (rc == NB_OK) ctx->policies = policies;
+    return rc;
 }
 
 // what the context's two policy entries check behind their eye set-up: a policy is there and its features divide the width
@@ -779,10 +934,19 @@ static int scenes_step_policy_check(nb_scenes *ctx, const char *fn, const float 
 static int scenes_policy_steps(nb_scenes *ctx, const char *fn, uint32_t k, const float *up_xyz, const float *cp16, uint32_t width)
 {
     return scenes_vision_step(ctx, fn, k, up_xyz, cp16, [=](nb_scenes *ctx) -> int {
-        nbk::ScenesPolicyArgs a = scenes_policy_args(scenes_eyes(ctx, 0u, ctx->scenes * ctx->n, width), ctx->pol, ctx->policies, ctx->policy.p);
+        const nbk::ScenesEyes eyes = scenes_eyes(ctx, 0u, ctx->scenes * ctx->n, width);
+        nbk::ScenesPolicyRecurrentArgs r{};
+        if (ctx->pol.recurrent) r = scenes_policy_recurrent_args(eyes, ctx->pol, ctx->policies, ctx->policy.p);
+        nbk::ScenesPolicyArgs &a = r.p;
+        if (!ctx->pol.recurrent) a = scenes_policy_args(eyes, ctx->pol, ctx->policies, ctx->policy.p);
         a.pos_in = ctx->pos.p, a.vel_in = ctx->vel.p, a.pos_out = ctx->pos_alt.p, a.vel_out = ctx->vel_alt.p;
         a.ux = up_xyz[0], a.uy = up_xyz[1], a.uz = up_xyz[2], a.dt = ctx->p.dt;
-        NB_HIP(ctx, nbk::launch_scenes_policy(a, ctx->stream));
+        if (ctx->pol.recurrent) {
+            r.mem_in = r.mem_out = ctx->memory.p;    // in place (R7)
+            NB_HIP(ctx, nbk::launch_scenes_policy_recurrent(r, ctx->stream));
+        } else {
+            NB_HIP(ctx, nbk::launch_scenes_policy(a, ctx->stream));
+        }
         return NB_OK;
     });
 }
@@ -797,6 +961,24 @@ NB_EXPORT int nb_scenes_step_policy(nb_scenes *ctx, uint32_t k, const float *up_
     return scenes_policy_steps(ctx, fn, k, up_xyz, cp16, width);
 }
 
+// P8 or R8 for eyes [first_eye, first_eye + cnt) of the staged state into the context's buffers, whichever kind of policy is set
+static int scenes_policy_observe(nb_scenes *ctx, uint32_t first_eye, uint32_t cnt, uint32_t width, bool feat, bool act, bool mem_next)
+{
+    const nbk::ScenesEyes eyes = scenes_eyes(ctx, first_eye, cnt, width);
+    nbk::ScenesPolicyRecurrentArgs r{};
+    if (ctx->pol.recurrent) r = scenes_policy_recurrent_args(eyes, ctx->pol, ctx->policies, ctx->policy.p);
+    nbk::ScenesPolicyArgs &a = r.p;
+    if (!ctx->pol.recurrent) a = scenes_policy_args(eyes, ctx->pol, ctx->policies, ctx->policy.p);
+    a.feat_out = feat ? ctx->pol_feat.p : nullptr, a.act_out = act ? ctx->pol_act.p : nullptr;
+    if (ctx->pol.recurrent) {
+        r.mem_in = ctx->memory.p, r.mem_obs = mem_next ? ctx->pol_mem.p : nullptr;
+        NB_HIP(ctx, nbk::launch_scenes_policy_recurrent_observe(r, ctx->stream));
+    } else {
+        NB_HIP(ctx, nbk::launch_scenes_policy_observe(a, ctx->stream));
+    }
+    return NB_OK;
+}
+
 NB_EXPORT int nb_scenes_eyes_policy(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
                                     uint32_t width, float *feat, float *act)
 {
@@ -808,12 +990,69 @@ NB_EXPORT int nb_scenes_eyes_policy(nb_scenes *ctx, uint32_t first_scene, uint32
     if (rc != NB_OK) return rc;
     const ScenesEyesOutput rows[2] = {{feat, &ctx->pol_feat, ctx->pol.features}, {act, &ctx->pol_act, 2}};
     const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
-        nbk::ScenesPolicyArgs a = scenes_policy_args(scenes_eyes(ctx, first_eye, cnt, width), ctx->pol, ctx->policies, ctx->policy.p);
-        a.feat_out = feat ? ctx->pol_feat.p : nullptr, a.act_out = act ? ctx->pol_act.p : nullptr;
-        NB_HIP(ctx, nbk::launch_scenes_policy_observe(a, ctx->stream));
-        return NB_OK;
+        return scenes_policy_observe(ctx, first_eye, cnt, width, feat != nullptr, act != nullptr, false);
     };
     return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, rows, kNoPolicyOutputs, launch);
+}
+
+// ---- a recurrent policy with per-body memory (DESIGN.md section 14.8): the context's entries -------------------------------------------
+// a memory is in use: a recurrent policy or a search over one is set
+static int scenes_memory_set_check(nb_scenes *ctx, const char *fn) { return scenes_state_check(ctx, fn, ctx->memory_words != 0, kCallSetPolicyRecurrent); }
+
+NB_EXPORT int nb_scenes_eyes_policy_memory(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, const float *up_xyz, const float *cp16,
+                                           uint32_t width, float *feat, float *act, float *mem_next)
+{
+    static const char fn[] = "nb_scenes_eyes_policy_memory";
+    int rc = ctx_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    rc = scenes_eye_setup_check(ctx, fn, up_xyz, cp16, width);
+    if (rc == NB_OK) rc = scenes_state_check(ctx, fn, ctx->policies != 0 && ctx->pol.recurrent, kCallSetPolicyRecurrent);
+    if (rc == NB_OK) rc = scenes_policy_set_check(ctx, fn, width);
+    if (rc != NB_OK) return rc;
+    const ScenesEyesOutput rows[3] = {{feat, &ctx->pol_feat, ctx->pol.features}, {act, &ctx->pol_act, 2}, {mem_next, &ctx->pol_mem, ctx->pol.hidden}};
+    const auto launch = [=](nb_scenes *ctx, uint32_t first_eye, uint32_t cnt) -> int {
+        return scenes_policy_observe(ctx, first_eye, cnt, width, feat != nullptr, act != nullptr, mem_next != nullptr);
+    };
+    return scenes_eyes_download(ctx, fn, first_scene, scene_count, up_xyz, cp16, rows, kNoPolicyMemoryOutputs, launch);
+}
+
+NB_EXPORT int nb_scenes_memory_reset(nb_scenes *ctx)
+{
+    static const char fn[] = "nb_scenes_memory_reset";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_memory_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    NB_HIP(ctx, hipMemsetAsync(ctx->memory.p, 0, ctx->memory_words * sizeof(float), ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_memory(nb_scenes *ctx, uint32_t first_scene, uint32_t scene_count, float *out_host)
+{
+    static const char fn[] = "nb_scenes_memory";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {out_host}, &ctx->err);
+    if (rc == NB_OK) rc = scenes_range_check(ctx, fn, first_scene, scene_count);
+    if (rc == NB_OK) rc = scenes_memory_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    const size_t per_scene = ctx->memory_words / ctx->scenes;   // n * hidden
+    if (scene_count)
+        NB_HIP(ctx, hipMemcpyAsync(out_host, ctx->memory.p + first_scene * per_scene, scene_count * per_scene * sizeof(float), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_set_memory(nb_scenes *ctx, const float *mem_host)
+{
+    static const char fn[] = "nb_scenes_set_memory";
+    int rc = ctx_check(ctx, fn);
+    if (rc == NB_OK) rc = scenes_null_check(fn, {mem_host}, &ctx->err);
+    if (rc == NB_OK) rc = scenes_memory_set_check(ctx, fn);
+    if (rc != NB_OK) return rc;
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step in flight may still use the memory
+    NB_HIP(ctx, hipMemcpyAsync(ctx->memory.p, mem_host, ctx->memory_words * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
+    return NB_OK;
 }
 
 // ---- the score of every scene, accumulated on the device (DESIGN.md section 14.5) -----------------------------------------------------------
@@ -975,21 +1214,38 @@ static int es_shape_check(const char *fn, uint32_t features, uint32_t hidden, st
     return policy_check(fn, features, hidden, 0u, 1u, 1u, 0.0f, err);
 }
 
-static nbk::EsArgs es_args(const nb_es_params &ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t scenes)
+// the length of a stateless launch's mean: by_shape, nb_policy_floats of a policy shape within the limits; otherwise `floats` itself
+static int es_floats_check(const char *fn, bool by_shape, uint32_t features, uint32_t hidden, uint32_t floats, size_t *m, std::string *err)
+{
+    if (by_shape) {
+        *m = nbk::policy_floats(features, hidden);
+        return es_shape_check(fn, features, hidden, err);
+    }
+    *m = floats;
+    if (floats == 0 || floats > NB_ES_MAX_FLOATS) {
+        *err = std::string(fn) + ": floats must be 1 .. NB_ES_MAX_FLOATS (20674)";
+        return NB_ERR_INVALID;
+    }
+    return NB_OK;
+}
+
+static nbk::EsArgs es_args(const nb_es_params &ep, size_t m, uint32_t generation, uint32_t scenes)
 {
     nbk::EsArgs a{};
-    a.seed = ep.seed, a.g = generation, a.scenes = scenes, a.m = (uint32_t)nbk::policy_floats(features, hidden);
+    a.seed = ep.seed, a.g = generation, a.scenes = scenes, a.m = (uint32_t)m;
     a.sigma = ep.sigma, a.step = ep.step;
     a.c0 = ep.coef[0], a.c1 = ep.coef[1], a.c2 = ep.coef[2], a.c3 = ep.coef[3], a.c4 = ep.coef[4], a.c5 = ep.coef[5];
     return a;
 }
 
-NB_EXPORT int nb_scenes_es_perturb_launch(const nb_es_params *ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t first_scene,
-                                          uint32_t count, const void *mean, void *theta_out, void *stream)
+// nb_scenes_es_perturb_launch and nb_scenes_es_perturb_floats_launch: E1-E3 depend on the weight index alone, so the mean's length is
+// all the kernel takes of the shape
+static int es_perturb_launch(const char *fn, const nb_es_params *ep, bool by_shape, uint32_t features, uint32_t hidden, uint32_t floats,
+                             uint32_t generation, uint32_t first_scene, uint32_t count, const void *mean, void *theta_out, void *stream)
 {
-    static const char fn[] = "nb_scenes_es_perturb_launch";
+    size_t m = 0;
     int rc = scenes_null_check(fn, {ep, mean, theta_out}, &g_tls_error);
-    if (rc == NB_OK) rc = es_shape_check(fn, features, hidden, &g_tls_error);
+    if (rc == NB_OK) rc = es_floats_check(fn, by_shape, features, hidden, floats, &m, &g_tls_error);
     if (rc == NB_OK) rc = es_params_check(fn, *ep, &g_tls_error);
     if (rc != NB_OK) return rc;
     if ((uint64_t)first_scene + count > NB_ES_MAX_POPULATION) {
@@ -998,7 +1254,6 @@ NB_EXPORT int nb_scenes_es_perturb_launch(const nb_es_params *ep, uint32_t featu
     }
     rc = scenes_aligned_check(fn, 4, {mean, theta_out}, "mean and theta_out", &g_tls_error);
     if (rc != NB_OK) return rc;
-    const size_t m = nbk::policy_floats(features, hidden);
     if (ranges_overlap(theta_out, (size_t)count * m * sizeof(float), mean, m * sizeof(float))) {
         g_tls_error = std::string(fn) + ": theta_out must not overlap mean";
         return NB_ERR_INVALID;
@@ -1006,18 +1261,32 @@ NB_EXPORT int nb_scenes_es_perturb_launch(const nb_es_params *ep, uint32_t featu
     if (count == 0) return NB_OK;
     rc = device_for_launch(mean, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    return launch_status(nbk::launch_es_perturb(es_args(*ep, features, hidden, generation, 0u), first_scene, count, (const float *)mean,
-                                                (float *)theta_out, (hipStream_t)stream),
+    static_assert((uint64_t)(NB_ES_MAX_POPULATION / 2u) * ((NB_ES_MAX_FLOATS + 1u) / 2u) < (1ull << 25), "the flat perturb grid: 2 048 x 10 337 lanes");
+    return launch_status(nbk::launch_es_perturb(es_args(*ep, m, generation, 0u), first_scene, count, (const float *)mean, (float *)theta_out,
+                                                (hipStream_t)stream),
                          "nb: perturb kernel launch failed (scene batch, search): ", &g_tls_error);
 }
 
-NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t scenes,
-                                         const void *score, const void *mean, void *mean_out, void *rank_out, void *fitness_out,
-                                         void *report_out, void *stream)
+NB_EXPORT int nb_scenes_es_perturb_launch(const nb_es_params *ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t first_scene,
+                                          uint32_t count, const void *mean, void *theta_out, void *stream)
 {
-    static const char fn[] = "nb_scenes_es_update_launch";
+    return es_perturb_launch("nb_scenes_es_perturb_launch", ep, true, features, hidden, 0u, generation, first_scene, count, mean, theta_out, stream);
+}
+
+NB_EXPORT int nb_scenes_es_perturb_floats_launch(const nb_es_params *ep, uint32_t floats, uint32_t generation, uint32_t first_scene, uint32_t count,
+                                                 const void *mean, void *theta_out, void *stream)
+{
+    return es_perturb_launch("nb_scenes_es_perturb_floats_launch", ep, false, 0u, 0u, floats, generation, first_scene, count, mean, theta_out, stream);
+}
+
+// nb_scenes_es_update_launch and nb_scenes_es_update_floats_launch, likewise
+static int es_update_launch(const char *fn, const nb_es_params *ep, bool by_shape, uint32_t features, uint32_t hidden, uint32_t floats,
+                            uint32_t generation, uint32_t scenes, const void *score, const void *mean, void *mean_out, void *rank_out,
+                            void *fitness_out, void *report_out, void *stream)
+{
+    size_t m = 0;
     int rc = scenes_null_check(fn, {ep, score, mean, mean_out, rank_out}, &g_tls_error);
-    if (rc == NB_OK) rc = es_shape_check(fn, features, hidden, &g_tls_error);
+    if (rc == NB_OK) rc = es_floats_check(fn, by_shape, features, hidden, floats, &m, &g_tls_error);
     if (rc == NB_OK) rc = es_params_check(fn, *ep, &g_tls_error);
     if (rc != NB_OK) return rc;
     if (scenes == 0 || scenes > NB_ES_MAX_POPULATION) {
@@ -1027,7 +1296,7 @@ NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t featur
     rc = scenes_aligned_check(fn, 8, {score}, "score", &g_tls_error);
     if (rc == NB_OK) rc = scenes_aligned_check(fn, 4, {mean}, "mean", &g_tls_error);
     if (rc != NB_OK) return rc;
-    const size_t mbytes = nbk::policy_floats(features, hidden) * sizeof(float);
+    const size_t mbytes = m * sizeof(float);
     const bool in_place = mean_out == mean;   // the update may be in place: a weight's word is read and written by one lane
     const ByteRange in[2] = {{score, (size_t)scenes * sizeof(nb_scene_score)}, {in_place ? nullptr : mean, mbytes}};
     const ByteRange out[4] = {{mean_out, mbytes}, {rank_out, (size_t)scenes * 4u}, {fitness_out, (size_t)scenes * 4u}, {report_out, sizeof(nb_es_report)}};
@@ -1035,7 +1304,7 @@ NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t featur
     if (rc != NB_OK) return rc;
     rc = device_for_launch(score, stream, SelectDevice::kAlways);
     if (rc != NB_OK) return rc;
-    const nbk::EsArgs a = es_args(*ep, features, hidden, generation, scenes);
+    const nbk::EsArgs a = es_args(*ep, m, generation, scenes);
     rc = launch_status(nbk::launch_es_rank(a, (const nbk::SceneScore *)score, (uint32_t *)rank_out, (float *)fitness_out, (uint32_t *)report_out,
                                            (hipStream_t)stream),
                        "nb: rank kernel launch failed (scene batch, search): ", &g_tls_error);
@@ -1044,22 +1313,41 @@ NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t featur
                          "nb: update kernel launch failed (scene batch, search): ", &g_tls_error);
 }
 
+NB_EXPORT int nb_scenes_es_update_launch(const nb_es_params *ep, uint32_t features, uint32_t hidden, uint32_t generation, uint32_t scenes,
+                                         const void *score, const void *mean, void *mean_out, void *rank_out, void *fitness_out,
+                                         void *report_out, void *stream)
+{
+    return es_update_launch("nb_scenes_es_update_launch", ep, true, features, hidden, 0u, generation, scenes, score, mean, mean_out, rank_out,
+                            fitness_out, report_out, stream);
+}
+
+NB_EXPORT int nb_scenes_es_update_floats_launch(const nb_es_params *ep, uint32_t floats, uint32_t generation, uint32_t scenes, const void *score,
+                                                const void *mean, void *mean_out, void *rank_out, void *fitness_out, void *report_out,
+                                                void *stream)
+{
+    return es_update_launch("nb_scenes_es_update_floats_launch", ep, false, 0u, 0u, floats, generation, scenes, score, mean, mean_out, rank_out,
+                            fitness_out, report_out, stream);
+}
+
 // the context holds a search
 static int scenes_es_set_check(nb_scenes *ctx, const char *fn) { return scenes_state_check(ctx, fn, ctx->es_set, kCallEsSet); }
 
-NB_EXPORT int nb_scenes_es_set(nb_scenes *ctx, uint32_t features, uint32_t hidden, const float *mean_host, float accel_limit, const nb_es_params *ep)
+// nb_scenes_es_set and nb_scenes_es_set_recurrent: the search over policies of `shape`, whose mean has shape.floats() floats
+static int scenes_es_set(nb_scenes *ctx, const char *fn, const ScenesPolicyShape &shape, const float *mean_host, const nb_es_params *ep)
 {
-    static const char fn[] = "nb_scenes_es_set";
+    const uint32_t features = shape.features, hidden = shape.hidden;
     int rc = ctx_check(ctx, fn);
     if (rc == NB_OK) rc = scenes_null_check(fn, {mean_host, ep}, &ctx->err);
-    if (rc == NB_OK) rc = policy_check(fn, features, hidden, 0u, ctx->scenes, ctx->scenes, accel_limit, &ctx->err);
+    if (rc == NB_OK && !shape.recurrent) rc = policy_check(fn, features, hidden, 0u, ctx->scenes, ctx->scenes, shape.accel_limit, &ctx->err);
+    if (rc == NB_OK && shape.recurrent)
+        rc = policy_recurrent_check(fn, features, hidden, 0u, ctx->scenes, ctx->scenes, shape.accel_limit, shape.memory_limit, &ctx->err);
     if (rc == NB_OK) rc = es_params_check(fn, *ep, &ctx->err);
     if (rc != NB_OK) return rc;
     if (ctx->scenes > NB_ES_MAX_POPULATION) {
         ctx->err = std::string(fn) + ": a search takes a batch of at most NB_ES_MAX_POPULATION (4096) scenes";
         return NB_ERR_INVALID;
     }
-    const size_t m = nbk::policy_floats(features, hidden);
+    const size_t m = shape.floats();
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // a step or an update in flight may still read the policies and the mean
     ctx->es_set = ctx->es_updated = false;
     ctx->policies = 0;                               // the policies' buffer may be replaced: none is set until nb_scenes_es_perturb
@@ -1070,10 +1358,27 @@ NB_EXPORT int nb_scenes_es_set(nb_scenes *ctx, uint32_t features, uint32_t hidde
     NB_HIP(ctx, ctx->es_report.reserve(4));
     NB_HIP(ctx, hipMemcpyAsync(ctx->es_mean.p, mean_host, m * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host array is not retained
-    ctx->es_pol = {features, hidden, accel_limit}, ctx->ep = *ep;
+    ctx->es_pol = shape, ctx->ep = *ep;
     ctx->es_generation = 0;
+    if (shape.recurrent) {                           // the memory the population will step: there from here on, so that a reset may precede the first perturb
+        rc = scenes_memory_ensure(ctx, hidden, false);
+        if (rc != NB_OK) return rc;
+    } else {
+        ctx->memory_words = 0;                       // no policy is set and the search needs none
+    }
     ctx->es_set = true;
     return NB_OK;
+}
+
+NB_EXPORT int nb_scenes_es_set(nb_scenes *ctx, uint32_t features, uint32_t hidden, const float *mean_host, float accel_limit, const nb_es_params *ep)
+{
+    return scenes_es_set(ctx, "nb_scenes_es_set", {features, hidden, accel_limit}, mean_host, ep);
+}
+
+NB_EXPORT int nb_scenes_es_set_recurrent(nb_scenes *ctx, uint32_t features, uint32_t hidden, const float *mean_host, float accel_limit,
+                                         float memory_limit, const nb_es_params *ep)
+{
+    return scenes_es_set(ctx, "nb_scenes_es_set_recurrent", {features, hidden, accel_limit, true, memory_limit}, mean_host, ep);
 }
 
 NB_EXPORT int nb_scenes_es_perturb(nb_scenes *ctx)
@@ -1083,8 +1388,14 @@ NB_EXPORT int nb_scenes_es_perturb(nb_scenes *ctx)
     if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
     if (rc != NB_OK) return rc;
     RoctxRange range(fn);
-    NB_HIP(ctx, nbk::launch_es_perturb(es_args(ctx->ep, ctx->es_pol.features, ctx->es_pol.hidden, ctx->es_generation, ctx->scenes), 0u, ctx->scenes,
-                                       ctx->es_mean.p, ctx->policy.p, ctx->stream));
+    if (ctx->es_pol.recurrent) {                     // the policies become recurrent: their memory, if the context has none of that size
+        rc = scenes_memory_ensure(ctx, ctx->es_pol.hidden, false);
+        if (rc != NB_OK) return rc;
+    } else {
+        ctx->memory_words = 0;
+    }
+    NB_HIP(ctx, nbk::launch_es_perturb(es_args(ctx->ep, ctx->es_pol.floats(), ctx->es_generation, ctx->scenes), 0u, ctx->scenes, ctx->es_mean.p,
+                                       ctx->policy.p, ctx->stream));
     ctx->pol = ctx->es_pol, ctx->policies = ctx->scenes;
     return NB_OK;
 }
@@ -1097,7 +1408,7 @@ NB_EXPORT int nb_scenes_es_update(nb_scenes *ctx)
     if (rc == NB_OK) rc = scenes_score_set_check(ctx, fn);
     if (rc != NB_OK) return rc;
     RoctxRange range(fn);
-    const nbk::EsArgs a = es_args(ctx->ep, ctx->es_pol.features, ctx->es_pol.hidden, ctx->es_generation, ctx->scenes);
+    const nbk::EsArgs a = es_args(ctx->ep, ctx->es_pol.floats(), ctx->es_generation, ctx->scenes);
     NB_HIP(ctx, nbk::launch_es_rank(a, ctx->score.p, ctx->es_rank.p, ctx->es_fitness.p, ctx->es_report.p, ctx->stream));
     NB_HIP(ctx, nbk::launch_es_update(a, ctx->es_rank.p, ctx->es_mean.p, ctx->es_mean.p, ctx->stream));
     ctx->es_generation += 1u;
@@ -1112,7 +1423,7 @@ NB_EXPORT int nb_scenes_es_mean(nb_scenes *ctx, float *out_host)
     if (rc == NB_OK) rc = scenes_null_check(fn, {out_host}, &ctx->err);
     if (rc == NB_OK) rc = scenes_es_set_check(ctx, fn);
     if (rc != NB_OK) return rc;
-    const size_t m = nbk::policy_floats(ctx->es_pol.features, ctx->es_pol.hidden);
+    const size_t m = ctx->es_pol.floats();
     NB_HIP(ctx, hipMemcpyAsync(out_host, ctx->es_mean.p, m * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     NB_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NB_OK;

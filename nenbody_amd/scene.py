@@ -441,6 +441,26 @@ def pack_policy(w1, b1, w2, b2) -> np.ndarray:
     return np.concatenate([w1.reshape(-1), b1, w2.reshape(-1), b2])
 
 
+def policy_recurrent_floats(features: int, hidden: int) -> int:
+    """The floats of one recurrent policy of shape (features, hidden) (nb_policy_recurrent_floats): 0 for a shape outside the limits."""
+    if features < 0 or hidden < 0 or features > 0xFFFFFFFF or hidden > 0xFFFFFFFF:
+        return 0
+    return int(_lib.load().nb_policy_recurrent_floats(int(features), int(hidden)))
+
+
+def pack_policy_recurrent(w1, wr, b1, w2, b2) -> np.ndarray:
+    """One recurrent policy in the layout :meth:`SceneBatch.set_policy_recurrent` takes (R1): w1 (F, H) feature-major, wr (H, H)
+    with wr[r, j] the weight of memory word r into hidden unit j, b1 (H,), w2 (2, H), b2 (2,) -> F*H + H*H + H + 2*H + 2 float32."""
+    w1 = np.ascontiguousarray(w1, np.float32)
+    if w1.ndim != 2:
+        raise ValueError("w1 must have shape (features, hidden)")
+    hidden = w1.shape[1]
+    wr, b1, w2, b2 = (np.ascontiguousarray(a, np.float32) for a in (wr, b1, w2, b2))
+    if wr.shape != (hidden, hidden) or b1.shape != (hidden,) or w2.shape != (2, hidden) or b2.shape != (2,):
+        raise ValueError("wr must have shape (hidden, hidden), b1 (hidden,), w2 (2, hidden) and b2 (2,)")
+    return np.concatenate([w1.reshape(-1), wr.reshape(-1), b1, w2.reshape(-1), b2])
+
+
 # struct nb_scene_score (include/nenbody.h, Q7): what :meth:`SceneBatch.scores` returns, one record a scene
 SCORE_DTYPE = np.dtype([("near", np.uint64), ("spread", np.float32), ("speed2", np.float32), ("momentum2", np.float32),
                         ("goal2", np.float32), ("steps", np.uint32), ("nonfinite", np.uint32)])
@@ -562,6 +582,55 @@ class SceneBatch:
         self._check(self._lib.nb_scenes_set_policy(self._ctx, int(features), int(hidden), int(w.shape[0]), w.ctypes.data, float(accel_limit)))
         self._policy_shape = (int(features), int(hidden))
 
+    def set_policy_recurrent(self, weights, features: int, hidden: int, accel_limit: float = float("inf"),
+                             memory_limit: float = float("inf")) -> None:
+        """The batch's policies, recurrent (nb_scenes_set_policy_recurrent): ``weights`` of shape (P,
+        policy_recurrent_floats(features, hidden)), P = 1 or the number of scenes, each row laid out as
+        :func:`pack_policy_recurrent` lays it out.  Every body gets ``hidden`` words of memory, cleared to +0 here; ``memory_limit``
+        >= 0 clamps what a step writes to it; inf: no limit.  :meth:`step_policy`, :meth:`step_policy_scored` and
+        :meth:`policy_observe` then run the recurrent kernel, until :meth:`set_policy` returns the batch to a feedforward policy."""
+        w = np.ascontiguousarray(weights, np.float32)
+        if w.ndim != 2 or w.shape[1] != policy_recurrent_floats(features, hidden) or w.shape[1] == 0:
+            raise ValueError("weights must have shape (policies, policy_recurrent_floats(features, hidden))")
+        self._check(self._lib.nb_scenes_set_policy_recurrent(self._ctx, int(features), int(hidden), int(w.shape[0]), w.ctypes.data,
+                                                             float(accel_limit), float(memory_limit)))
+        self._policy_shape = (int(features), int(hidden))
+
+    def memory(self, first_scene: int = 0, scene_count: Optional[int] = None) -> np.ndarray:
+        """The memory of scenes [first_scene, first_scene + scene_count) (nb_scenes_memory): float32 (S, n, H).  Waits for the
+        stream."""
+        scene_count = SceneBatch._scene_range(self, first_scene, scene_count)
+        out = np.zeros((scene_count, self.n, self._policy_shape[1]), np.float32)
+        buf = out if out.size else np.zeros(1, np.float32)
+        self._check(self._lib.nb_scenes_memory(self._ctx, first_scene, scene_count, buf.ctypes.data))
+        return out
+
+    def set_memory(self, memory) -> None:
+        """The memory of the whole batch from the host (nb_scenes_set_memory): float32 (B, n, H), any bit patterns."""
+        m = np.ascontiguousarray(memory, np.float32)
+        if m.shape != (self.scenes, self.n, self._policy_shape[1]) or m.size == 0:
+            raise ValueError("memory must have shape (scenes, n, hidden)")
+        self._check(self._lib.nb_scenes_set_memory(self._ctx, m.ctypes.data))
+
+    def memory_reset(self) -> None:
+        """The memory of every body set to +0 (nb_scenes_memory_reset), asynchronous.  An upload, :meth:`keep` and :meth:`rewind` do
+        not touch the memory."""
+        self._check(self._lib.nb_scenes_memory_reset(self._ctx))
+
+    def policy_observe_memory(self, first_scene: int = 0, scene_count: Optional[int] = None, width: int = 1024, up=(0.0, 0.0, 1.0),
+                              cp=None):
+        """:meth:`policy_observe` for a recurrent policy with the memory the step would write (nb_scenes_eyes_policy_memory), the
+        memory itself left as it is.  Returns (features float32 (S, n, F), outputs float32 (S, n, 2), next memory float32
+        (S, n, H))."""
+        scene_count = SceneBatch._scene_range(self, first_scene, scene_count)
+        upv, cpm = self._eye_setup(width, up, cp)
+        feat = np.empty((scene_count, self.n, self._policy_shape[0]), np.float32)
+        act = np.empty((scene_count, self.n, 2), np.float32)
+        mem = np.empty((scene_count, self.n, self._policy_shape[1]), np.float32)
+        self._check(self._lib.nb_scenes_eyes_policy_memory(self._ctx, first_scene, scene_count, upv.ctypes.data, cpm.ctypes.data, width,
+                                                           feat.ctypes.data, act.ctypes.data, mem.ctypes.data))
+        return feat, act, mem
+
     def step_policy(self, k: int = 1, width: int = 1024, up=(0.0, 0.0, 1.0), cp=None) -> None:
         """k steps of every scene under its policy (nb_scenes_step_policy): each body pools its eye row into the policy's features,
         runs the two-layer network and is pushed along its eye's forward and side axes by the two outputs; one fused launch per step
@@ -628,6 +697,23 @@ class SceneBatch:
             raise ValueError("coef must have six components")
         ep = _lib.NbEsParams(float(sigma), float(step), (ctypes.c_float * 6)(*c.tolist()), int(seed) & 0xFFFFFFFFFFFFFFFF)
         self._check(self._lib.nb_scenes_es_set(self._ctx, int(features), int(hidden), m.ctypes.data, float(accel_limit), ctypes.byref(ep)))
+        self._es_floats = int(m.shape[0])
+        self._policy_shape = (int(features), int(hidden))
+
+    def es_set_recurrent(self, mean, features: int, hidden: int, sigma: float, step: float, coef, seed: int = 0,
+                         accel_limit: float = float("inf"), memory_limit: float = float("inf")) -> None:
+        """:meth:`es_set` over a recurrent policy (nb_scenes_es_set_recurrent): ``mean`` has policy_recurrent_floats(features, hidden)
+        floats.  A generation is :meth:`rewind`, :meth:`memory_reset`, :meth:`score_reset`, :meth:`es_perturb`,
+        :meth:`step_policy_scored`, :meth:`es_update`: :meth:`rewind` does not touch the memory."""
+        m = np.ascontiguousarray(mean, np.float32)
+        if m.ndim != 1 or m.shape[0] != policy_recurrent_floats(features, hidden) or m.shape[0] == 0:
+            raise ValueError("mean must have shape (policy_recurrent_floats(features, hidden),)")
+        c = np.ascontiguousarray(coef, np.float32)
+        if c.shape != (6,):
+            raise ValueError("coef must have six components")
+        ep = _lib.NbEsParams(float(sigma), float(step), (ctypes.c_float * 6)(*c.tolist()), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._check(self._lib.nb_scenes_es_set_recurrent(self._ctx, int(features), int(hidden), m.ctypes.data, float(accel_limit),
+                                                         float(memory_limit), ctypes.byref(ep)))
         self._es_floats = int(m.shape[0])
         self._policy_shape = (int(features), int(hidden))
 
